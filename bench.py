@@ -10,7 +10,14 @@ mismatch count, 2 B per pair) and host threads expand them into the caller's pin
 int32 arrays: packed chunks expanded while the next chunk scores, and the last ~20 % of
 the pairs stored as int32 straight into the arrays.
 
-    python bench.py [--gpus N --steps K --warmup W --config target]
+    python bench.py [--gpus N --steps K --warmup W --config target] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: it builds the workload, warms up, times ``--steps``
+steps, writes the last timed step's results when ``--dump-outputs DIR`` is given (``DIR/score.npy`` and
+``DIR/end.npy``, float64; a fixed seeded sample of the pairs when the list is too long for 48 MiB) and prints
+the result line (metric, value, unit, higher_is_better, dtype, ms_per_step, the configuration).  Everything
+else described below -- rooflines, the kernel alone, CPU baselines, the other configs and entry points, the
+end-to-end graph build, parity checks against one GPU, the secondary N > 1 shapes -- runs only with ``--full``.
 
 ``--gpus N`` > 1 without a launcher: this process starts ``python -m torch.distributed.run
 --nproc-per-node N bench.py ...`` as a CHILD before touching the GPU, waits for it and exits
@@ -24,7 +31,7 @@ embarrassingly across the GPUs"): every rank holds the same read set and enumera
 list, scores its contiguous shard (balanced by sum n*m) and its kernels store the shard's
 (score, end) into rank 0's shared pinned host buffer (ovlgraph.sharded.ShardedStep, a step
 fence in shared memory, no collective per step); value = the list's pairs / max-over-ranks
-time.  The N > 1 line also carries: the same list scored by rank 0's GPU alone in the same
+time.  With --full the N > 1 line also carries: the same list scored by rank 0's GPU alone in the same
 run (one_gpu_ms_per_step, speedup_vs_one_gpu, matches_one_gpu), rank 0's in-step roofline,
 the same shards collected by an RCCL gather into rank 0's HBM (rccl_gather), a read set per
 rank (weak_scaling: the reference's joblib shape), BASELINE configs[3] pair-sharded
@@ -73,6 +80,32 @@ def algorithmic_bytes(lens: np.ndarray, a: np.ndarray, b: np.ndarray) -> int:
     """ceil(n/4) + ceil(m/4) 2-bit read bytes + 8 B indices + 8 B (score, end) per pair."""
     q = (lens + 3) // 4
     return int(q[a].sum() + q[b].sum() + 16 * a.shape[0])
+
+
+DUMP_BUDGET_BYTES = 48 << 20  # --dump-outputs: the float64 arrays of one dump together stay below this
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_outputs(dirpath: str, arrays: dict) -> dict:
+    """--dump-outputs: write the step's result arrays (equal lengths, one entry per pair) as
+    ``dirpath/<name>.npy`` in float64 (exact for int32).  When they would exceed DUMP_BUDGET_BYTES together,
+    every array keeps the same seeded sample of the pairs (sorted indices drawn without replacement, a function
+    of the list's length alone), so two builds run with the same arguments write the same pairs.  Returns what
+    was written, for the result line."""
+    os.makedirs(dirpath, exist_ok=True)
+    n = len(next(iter(arrays.values())))
+    assert all(len(v) == n for v in arrays.values())
+    cap = DUMP_BUDGET_BYTES // (8 * len(arrays))
+    idx = None
+    if n > cap:
+        idx = np.sort(np.random.Generator(np.random.PCG64(DUMP_SAMPLE_SEED)).choice(n, size=cap, replace=False))
+    info = {"dir": dirpath, "dtype": "float64", "pairs": n, "pairs_written": n if idx is None else cap,
+            "sampled": idx is not None, "files": []}
+    for name, v in arrays.items():
+        v = np.asarray(v)
+        np.save(os.path.join(dirpath, name + ".npy"), (v if idx is None else v[idx]).astype(np.float64))
+        info["files"].append(name + ".npy")
+    return info
 
 
 def _short_kernel(name: str) -> str:
@@ -950,7 +983,7 @@ def sharded_list(name: str, world: int, rank: int, dev, backend: str, args):
     from ovlgraph.hostmem import pinned_empty
     from ovlgraph.sharded import ShardedStep
     t0 = time.perf_counter()
-    w = Workload(name, seed=args.seed, dev=dev)
+    w = Workload(name, seed=args.seed, dev=dev, host_list=args.full)
     st = ShardedStep(w.reads, k=w.cfg["k"], engine=w.eng, dest="host")
     assert st.n_pairs == w.n_pairs
     w.refresh_device_list()
@@ -959,6 +992,17 @@ def sharded_list(name: str, world: int, rank: int, dev, backend: str, args):
     el = timed_steps(st.step, args.steps, args.warmup, dev, world)
     rows = gather_floats([el, st.hi - st.lo], world, dev, backend)
     el_max = max(r[0] for r in rows)
+    res = {"w": w, "el_max": el_max, "pairs_per_rank": [int(r[1]) for r in rows],
+           "per_rank_ms_per_step": [r[0] / args.steps * 1e3 for r in rows], "setup_s": round(setup, 2)}
+    if rank == 0 and args.dump_outputs:
+        # rank 0 returned from the last timed step when every slice of it had landed, and has not released it
+        got = st.results()
+        res["dump_outputs"] = dump_outputs(args.dump_outputs, {"score": got[0], "end": got[1]})
+    if not args.full:
+        dist.barrier()
+        w.out = w.own_out  # drop the views of the shared buffer, so that it can be unmapped and unlinked
+        st.close()
+        return res
     # every rank's in-step launches at once (each its own shard, as in the step); rank 0 reports its own
     roof, table, step_roof = in_step_rooflines(w, el / args.steps * 1e3)
     dist.barrier()
@@ -982,9 +1026,7 @@ def sharded_list(name: str, world: int, rank: int, dev, backend: str, args):
         g_ok = bool(np.array_equal(got[0], out[0]) and np.array_equal(got[1], out[1]))
     g.close()
     w.refresh_device_list()
-    res = {"w": w, "el_max": el_max, "pairs_per_rank": [int(r[1]) for r in rows],
-           "per_rank_ms_per_step": [r[0] / args.steps * 1e3 for r in rows],
-           "roofline": roof, "in_step_kernels": table, "step_roofline": step_roof, "setup_s": round(setup, 2)}
+    res.update(roofline=roof, in_step_kernels=table, step_roofline=step_roof)
     if rank == 0:
         res.update(one_gpu_ms_per_step=one / args.steps * 1e3, one_gpu_pairs_per_s=w.n_pairs * args.steps / one,
                    speedup_vs_one_gpu=one / el_max, matches_one_gpu=ok,
@@ -1053,6 +1095,8 @@ def multi_line(args, world: int, ident: dict, top: dict, extras: dict) -> dict:
         "step_roofline": top.get("step_roofline"),
         "rccl_gather": top.get("rccl_gather"),
         "setup_s": top.get("setup_s"),
+        "full": bool(args.full),
+        "dump_outputs": top.get("dump_outputs"),
         "cpu_baseline": None,
         "cpu_baseline_note": "the CPU baseline runs on rank 0 at N = 1 only (bench contract); see the N = 1 line",
     }
@@ -1063,8 +1107,8 @@ def multi_line(args, world: int, ident: dict, top: dict, extras: dict) -> dict:
 
 
 def extra_plan(args, world: int):
-    """The secondary N > 1 measurements this run makes, in order (empty with --no-extra)."""
-    if args.no_extra:
+    """The secondary N > 1 measurements this run makes, in order (none without --full, or with --no-extra)."""
+    if args.no_extra or not args.full:
         return []
     name = args.config or "target"
     plan = ["weak_scaling"]
@@ -1223,8 +1267,14 @@ def parse_args(argv=None):
                     help="workload at every N (default: the north_star target point)")
     ap.add_argument("--seed", type=int, default=0,
                     help="read-set seed (the secondary weak-scaling field: rank r uses seed + r)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra configs and stages")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: rooflines, the kernel alone, CPU baselines, the other configs "
+                         "and entry points, end-to-end timings, parity checks and the secondary N > 1 shapes")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's (score, end) as DIR/score.npy and "
+                         "DIR/end.npy (float64; a fixed seeded sample of the pairs when they exceed 48 MiB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the extra configs and stages")
     ap.add_argument("--no-numa-bind", action="store_true",
                     help="leave the CPU affinity alone (default: each process on its GPU's NUMA node)")
     ap.add_argument("--cpu-budget", type=float, default=10.0, help="seconds of all-core CPU-baseline work")
@@ -1251,6 +1301,10 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.band_sweep and not args.full:
+        ap.error("--band-sweep is one of the measurements of --full")
     return args
 
 
@@ -1365,24 +1419,20 @@ def main() -> int:
         return 0
 
     name = args.config or "target"
-    w = Workload(name, seed=args.seed, dev=dev, indel=args.indel, band=args.band)
+    # (the host copy of the candidate list serves the rooflines and the CPU baseline only)
+    w = Workload(name, seed=args.seed, dev=dev, indel=args.indel, band=args.band,
+                 host_list=args.full or bool(args.shard))
     if args.shard:
         r, n = (int(x) for x in args.shard.split("/"))
         cuts = w.eng.candidate_shards(n)
         w.set_shard(r, n, cuts[r], cuts[r + 1])
     elapsed = timed_steps(w.step, args.steps, args.warmup, dev, 1)
     ms_step = elapsed / args.steps * 1e3
-    roof, table, step_roof = in_step_rooflines(w, ms_step)
-    if args.shard:
-        print(json.dumps({"shard": args.shard, "workload": w.profile_key, "pairs": w.hi - w.lo,
-                          "ms_per_step": ms_step, "pairs_per_s": (w.hi - w.lo) * args.steps / elapsed,
-                          "roofline": roof, "in_step_kernels": table, "step_roofline": step_roof}), flush=True)
-        return 0
-    kernel_ms = kernel_timing(w, max(args.steps, 20), dev)
-    algo = w.algo_bytes()
-    achieved = algo / (kernel_ms * 1e-3) / 1e9
-    value = w.n_pairs * args.steps / elapsed
-    line = {
+    value = (w.hi - w.lo) * args.steps / elapsed
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, {"score": w.out[0][w.lo:w.hi], "end": w.out[1][w.lo:w.hi]})
+    head = {
         "metric": METRIC,
         "value": value,
         "unit": "overlap-pairs/s",
@@ -1395,6 +1445,7 @@ def main() -> int:
         "vs_baseline": None,
         "dtype": "int32",
         "data": "synthetic",
+        "full": bool(args.full),
         "config": {
             "workload": f"{name}: {WORKLOAD_DESC[name]}",
             "reads": len(w.reads),
@@ -1410,6 +1461,25 @@ def main() -> int:
             "kernel": w.kernel,
             "scoring": {"match": 10, "mismatch": -1, "indel": w.indel, "band": w.band},
         },
+        "dump_outputs": dumped,
+        "host_setup_s": dict(w.t_stages, read_simulation=round(w.t_sim, 4)),
+    }
+    if not args.full and not args.shard:
+        w.close()
+        print(json.dumps(head), flush=True)
+        return 0
+    roof, table, step_roof = in_step_rooflines(w, ms_step)
+    if args.shard:
+        print(json.dumps({"shard": args.shard, "workload": w.profile_key, "pairs": w.hi - w.lo,
+                          "ms_per_step": ms_step, "pairs_per_s": (w.hi - w.lo) * args.steps / elapsed,
+                          "roofline": roof, "in_step_kernels": table, "step_roofline": step_roof}), flush=True)
+        return 0
+    kernel_ms = kernel_timing(w, max(args.steps, 20), dev)
+    algo = w.algo_bytes()
+    achieved = algo / (kernel_ms * 1e-3) / 1e9
+    host_setup = head.pop("host_setup_s")
+    line = {
+        **head,
         "roofline": roof,
         "in_step_kernels": table,
         "step_roofline": step_roof,
@@ -1423,7 +1493,7 @@ def main() -> int:
         "kernel_only_pairs_per_s": w.n_pairs / (kernel_ms * 1e-3),
         "step_breakdown": step_breakdown(w, ms_step),
         "occupancy": load_profile(name, kernel_name(w, 0, w.n_pairs)).get("occupancy"),
-        "host_setup_s": dict(w.t_stages, read_simulation=round(w.t_sim, 4)),
+        "host_setup_s": host_setup,
     }
     if not args.no_extra:
         line["abi_one_shot"] = abi_one_shot(w)

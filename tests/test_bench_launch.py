@@ -57,14 +57,14 @@ def test_n2_stages_are_bounded_and_heard():
     names the running stage while a long stage runs (two ranks over gloo; each stage sleeps 1.5 s, budget 2.5 s,
     a heartbeat every 0.5 s)."""
     err = []
-    got = _dry(2, "--dry-run-stage-s", "1.5", "--extra-budget", "2.5", "--heartbeat", "0.5", stderr=err)
+    got = _dry(2, "--full", "--dry-run-stage-s", "1.5", "--extra-budget", "2.5", "--heartbeat", "0.5", stderr=err)
     plan = ["weak_scaling", "cfg4_strong", "cfg5_sharded_band_sweep", "single_process_all_gpus"]
     ran = [k for k in plan if got[k] is None]
     skipped = [k for k in plan if isinstance(got[k], dict) and "skipped" in got[k]]
     assert ran == plan[:2] and skipped == plan[2:], got
     assert "weak_scaling still running" in err[0] and "cfg4_strong done" in err[0], err[0][-2000:]
     # no budget pressure: every stage runs
-    got = _dry(2, "--dry-run-stage-s", "0.2")
+    got = _dry(2, "--full", "--dry-run-stage-s", "0.2")
     assert all(got[k] is None for k in plan)
 
 
@@ -79,7 +79,8 @@ def test_n2_line_is_the_sharded_target_list():
     """at N > 1 the line's value is the north_star target list sharded over the ranks (strong
     scaling against the N = 1 line's list), with the same-run one-GPU time, parity flag, rank 0's roofline and
     the gather used; the weak shape, cfg4 pair-sharded and the cfg5 band sweep sharded ride beside it."""
-    got = _dry(2)
+    got = _dry(2, "--full")
+    assert got["full"] is True
     assert got["metric"] == bench.METRIC and got["unit"] == "overlap-pairs/s" and got["scaling"] == "strong"
     assert got["config"]["workload"].startswith("target: PhiX N=50000 l=100")
     assert "pair-sharded x2" in got["config"]["parallelism"]
@@ -89,8 +90,53 @@ def test_n2_line_is_the_sharded_target_list():
     assert got["gather"]["dest"] == "host" and got["gather"]["fence"] == "shm"
     assert set(("weak_scaling", "cfg4_strong", "cfg5_sharded_band_sweep", "single_process_all_gpus")) <= set(got)
     # the secondary shapes are skipped with --no-extra, and a cfg4 run does not repeat cfg4 beside itself
-    assert not set(("weak_scaling", "cfg4_strong")) & set(_dry(2, "--no-extra"))
-    assert "cfg4_strong" not in _dry(2, "--config", "cfg4")
+    assert not set(("weak_scaling", "cfg4_strong")) & set(_dry(2, "--full", "--no-extra"))
+    assert "cfg4_strong" not in _dry(2, "--full", "--config", "cfg4")
+
+
+def test_plain_run_carries_the_headline_only():
+    """Without --full the N > 1 run plans no secondary stage and says so on its line; the headline fields stay."""
+    plain = bench.parse_args(["--gpus", "2"])
+    assert plain.full is False and plain.dump_outputs is None
+    assert bench.extra_plan(plain, 2) == []
+    assert bench.extra_plan(bench.parse_args(["--gpus", "2", "--full"]), 2) == [
+        "weak_scaling", "cfg4_strong", "cfg5_sharded_band_sweep", "single_process_all_gpus"]
+    got = _dry(2)
+    assert got["full"] is False
+    assert not set(("weak_scaling", "cfg4_strong", "cfg5_sharded_band_sweep", "single_process_all_gpus")) & set(got)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in got, k
+    assert (got["unit"], got["higher_is_better"], got["dtype"]) == ("overlap-pairs/s", True, "int32")
+
+
+def test_steps_must_be_positive():
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+
+def test_dump_outputs_writes_float64_within_budget(tmp_path):
+    """--dump-outputs' writer: int32 results as float64 .npy, whole when they fit, else the same seeded sample
+    (sorted, without replacement) of every array, identical from call to call."""
+    import numpy as np
+    sc = np.arange(1000, dtype=np.int32) - 500
+    en = (np.arange(1000, dtype=np.int32) * 7) % 101
+    info = bench.dump_outputs(str(tmp_path / "a"), {"score": sc, "end": en})
+    assert info["sampled"] is False and info["pairs_written"] == 1000 and info["files"] == ["score.npy", "end.npy"]
+    got = np.load(tmp_path / "a" / "score.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, sc) and np.array_equal(np.load(tmp_path / "a" / "end.npy"), en)
+    old = bench.DUMP_BUDGET_BYTES
+    bench.DUMP_BUDGET_BYTES = 2 * 8 * 100  # room for 100 pairs of two arrays
+    try:
+        one = bench.dump_outputs(str(tmp_path / "b"), {"score": sc, "end": en})
+        bench.dump_outputs(str(tmp_path / "c"), {"score": sc, "end": en})
+    finally:
+        bench.DUMP_BUDGET_BYTES = old
+    assert one["sampled"] is True and one["pairs_written"] == 100 and one["pairs"] == 1000
+    b_sc, b_en = np.load(tmp_path / "b" / "score.npy"), np.load(tmp_path / "b" / "end.npy")
+    assert b_sc.shape == b_en.shape == (100,) and np.all(np.diff(b_sc) > 0)  # sc is increasing: sorted, distinct
+    idx = (b_sc + 500).astype(np.int64)
+    assert np.array_equal(b_en, en[idx])  # both arrays hold the same pairs
+    assert np.array_equal(b_sc, np.load(tmp_path / "c" / "score.npy"))
 
 
 def test_n1_and_n2_lines_share_metric_and_workload():

@@ -9,7 +9,7 @@ O=gpurun_out/${1:-unrollab}; mkdir -p $O; export TMPDIR=/tmp
 V=genome-assembly-using-overlap-graphs_amd/build/ablate_unroll1/libovl.so
 timeout -k 10 600 python3 -u -m pytest tests/test_gpu_banded.py -x -q --timeout 300 --timeout-method thread -p no:cacheprovider > $O/t.log 2>&1 || { tail -30 $O/t.log; exit 1; }
 tail -1 $O/t.log
-ARGS="--config cfg5 --band-sweep=64,32,8,4 --sweep-steps 5 --steps 3 --warmup 1 --no-cpu-baseline --no-extra"
+ARGS="--config cfg5 --band-sweep=64,32,8,4 --sweep-steps 5 --steps 3 --warmup 1 --full --no-cpu-baseline --no-extra"
 for pass in 1 2; do
   timeout -k 10 300 python3 bench.py $ARGS > $O/u2_$pass.log 2>&1 || { tail -20 $O/u2_$pass.log; exit 1; }
   OVL_LIB_PATH=$V timeout -k 10 300 python3 bench.py $ARGS > $O/u1_$pass.log 2>&1 || { tail -20 $O/u1_$pass.log; exit 1; }

@@ -8,7 +8,7 @@ set -o pipefail
 cd "$GRAFT_REPO_ROOT" || exit 1
 O=gpurun_out/${1:-gridab}; mkdir -p $O; export TMPDIR=/tmp
 V=genome-assembly-using-overlap-graphs_amd/build/ablate_gridall/libovl.so
-ARGS="--config cfg5 --band-sweep=-1,64,32,8 --sweep-steps 5 --steps 3 --warmup 1 --no-cpu-baseline --no-extra"
+ARGS="--config cfg5 --band-sweep=-1,64,32,8 --sweep-steps 5 --steps 3 --warmup 1 --full --no-cpu-baseline --no-extra"
 for pass in 1 2; do
   OVL_LANE_FORM=3 timeout -k 10 300 python3 bench.py $ARGS > $O/def$pass.log 2>&1 || { tail -20 $O/def$pass.log; exit 1; }
   OVL_LANE_FORM=3 OVL_LIB_PATH=$V timeout -k 10 300 python3 bench.py $ARGS > $O/all$pass.log 2>&1 || { tail -20 $O/all$pass.log; exit 1; }
@@ -25,7 +25,7 @@ V2=genome-assembly-using-overlap-graphs_amd/build/ablate_h2hbm/libovl.so
 if [ -f $V2 ]; then
   OVL_LIB_PATH=$V2 timeout -k 10 300 python3 -u -m pytest tests/test_gpu_dp_lane.py -x -q -k "h2" --timeout 200 --timeout-method thread -p no:cacheprovider > $O/hbm_tests.log 2>&1 || { tail -20 $O/hbm_tests.log; exit 1; }
   tail -1 $O/hbm_tests.log
-  A2="--config cfg5 --band-sweep=-1 --sweep-steps 5 --steps 3 --warmup 1 --no-cpu-baseline --no-extra"
+  A2="--config cfg5 --band-sweep=-1 --sweep-steps 5 --steps 3 --warmup 1 --full --no-cpu-baseline --no-extra"
   for pass in 1 2; do
     timeout -k 10 300 python3 bench.py $A2 > $O/h2lds$pass.log 2>&1 || { tail -20 $O/h2lds$pass.log; exit 1; }
     OVL_LIB_PATH=$V2 timeout -k 10 300 python3 bench.py $A2 > $O/h2hbm$pass.log 2>&1 || { tail -20 $O/h2hbm$pass.log; exit 1; }

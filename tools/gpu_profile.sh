@@ -14,7 +14,7 @@ OUT="$GRAFT_REPO_ROOT/gpurun_out/$TAG"
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 B="$GRAFT_REPO_ROOT/bench.py"
-ARGS="--config $CFG --steps 20 --warmup 5 --no-cpu-baseline --no-extra"
+ARGS="--config $CFG --steps 20 --warmup 5 --full --no-cpu-baseline --no-extra"
 [ -n "$SHARD" ] && ARGS="$ARGS --shard $SHARD"
 echo "== kernel trace + stats ($ARGS)"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/kt" -o kt --output-format csv -- python3 "$B" $ARGS > "$OUT/kt.log" 2>&1 || { echo "kt failed"; tail -20 "$OUT/kt.log"; exit 1; }

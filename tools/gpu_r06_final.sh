@@ -16,17 +16,17 @@ timeout -k 10 300 python3 -u -c "import __graft_entry__ as g; g.smoke()" > "$OUT
   || { echo "smoke failed"; tail -30 "$OUT/smoke.log"; exit 1; }
 tail -2 "$OUT/smoke.log"
 echo "== bench N = 1"
-timeout -k 10 900 python3 -u bench.py > "$OUT/bench.log" 2>&1 || { echo "bench failed"; tail -30 "$OUT/bench.log"; exit 1; }
+timeout -k 10 900 python3 -u bench.py --full > "$OUT/bench.log" 2>&1 || { echo "bench failed"; tail -30 "$OUT/bench.log"; exit 1; }
 grep '^{"metric"' "$OUT/bench.log" > "$OUT/bench.json"
 python3 -c "
 import json; d = json.load(open('$OUT/bench.json'))
 print('value', d['value'], 'ms/step', d['ms_per_step'], 'frac', d['roofline']['frac'])
 e = d.get('end_to_end') or {}; print('end_to_end', {k: v for k, v in e.items() if 'remove' in k})"
 echo "== bench N = 2 rehearsal (two ranks on one GPU)"
-timeout -k 10 600 python3 -u bench.py --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/bench_n2.log" 2>&1 \
+timeout -k 10 600 python3 -u bench.py --full --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/bench_n2.log" 2>&1 \
   || { echo "bench N=2 failed"; tail -30 "$OUT/bench_n2.log"; exit 1; }
 grep '^{"metric"' "$OUT/bench_n2.log" > "$OUT/bench_n2.json"
 echo "== rocprofv3 kernel trace + stats of the default bench (short)"
-timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o bench --output-format csv -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extra > "$OUT/prof.log" 2>&1 \
+timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o bench --output-format csv -- python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-extra > "$OUT/prof.log" 2>&1 \
   || { echo "profile failed"; tail -30 "$OUT/prof.log"; exit 1; }
 echo all ok

@@ -122,7 +122,7 @@ def main():
         if "hbm_bytes_per_launch" in kernels[ko["kernel"]]:
             kernels[ko["kernel"]]["traffic_over_algorithmic"] = (kernels[ko["kernel"]]["hbm_bytes_per_launch"] /
                                                                  ko["algorithmic_bytes_per_launch"])
-    cmd = "bench.py --config %s --steps 20 --warmup 5 --no-cpu-baseline --no-extra" % cfg
+    cmd = "bench.py --config %s --steps 20 --warmup 5 --full --no-cpu-baseline --no-extra" % cfg
     if shard:
         cmd += " --shard " + shard.replace("shard", "").replace("of", "/")
     out = {"workload": workload, "headline_kernel": bench["roofline"]["kernel"], "command": cmd,
