@@ -1,0 +1,305 @@
+// ovl_cand.cpp — the device candidate list (ovl_ctx.h): its enumeration on every device, its shard bounds, and
+// scoring calls over it, through the resident grid (ovl_resident.h) or the launch pipeline.
+#include "ovl_ctx.h"
+
+namespace {
+
+// Keys, sort, per-read groups and their offsets; the list length comes back in d->cand_tail.
+int cand_count(Dev* c, int32_t k) {
+    HIPCHK(c, hipSetDevice(c->device));
+    c->cand_n = -1;
+    c->heavy_for = -1;
+    const int32_t n = c->n_reads;
+    const size_t nr = (size_t)std::max(n, 1);
+    const int all = k == 0 ? 1 : 0;
+    const int32_t bits = c->planes;  // symbol codes are dense: < 2^planes
+    hipStream_t s = c->stream;
+    HIPCHK(c, ensure(c->k_lo, nr * sizeof(int64_t)));
+    HIPCHK(c, ensure(c->k_hi, nr * sizeof(int64_t)));
+    HIPCHK(c, ensure(c->k_cnt, nr * sizeof(int64_t)));
+    HIPCHK(c, ensure(c->k_offs, nr * sizeof(int64_t)));
+    size_t temp = 0;
+    HIPCHK(c, ovl_cand_temp_bytes(n, &temp));
+    HIPCHK(c, ensure(c->k_temp, temp));
+    if (!all) {
+        HIPCHK(c, ensure(c->k_pre, nr * sizeof(uint64_t)));
+        HIPCHK(c, ensure(c->k_suf, nr * sizeof(uint64_t)));
+        HIPCHK(c, ensure(c->k_sorted, nr * sizeof(uint64_t)));
+        HIPCHK(c, ensure(c->k_iota, nr * sizeof(int32_t)));
+        HIPCHK(c, ensure(c->k_order, nr * sizeof(int32_t)));
+        HIPCHK(c, ovl_cand_keys(as<uint8_t>(c->codes), as<int64_t>(c->off), as<int32_t>(c->len), n, k, bits,
+                                as<uint64_t>(c->k_pre), as<uint64_t>(c->k_suf), as<int32_t>(c->k_iota), s));
+        HIPCHK(c, ovl_cand_sort(c->k_temp.p, c->k_temp.bytes, as<uint64_t>(c->k_pre), as<uint64_t>(c->k_sorted),
+                                as<int32_t>(c->k_iota), as<int32_t>(c->k_order), n, s));
+    }
+    HIPCHK(c, ovl_cand_count(as<uint64_t>(c->k_sorted), as<uint64_t>(c->k_pre), as<uint64_t>(c->k_suf), n, all,
+                             as<int64_t>(c->k_lo), as<int64_t>(c->k_hi), as<int64_t>(c->k_cnt), s));
+    HIPCHK(c, ovl_cand_scan(c->k_temp.p, c->k_temp.bytes, as<int64_t>(c->k_cnt), as<int64_t>(c->k_offs), n, s));
+    c->cand_tail[0] = c->cand_tail[1] = 0;
+    if (n > 0) {
+        HIPCHK(c, hipMemcpyAsync(&c->cand_tail[0], as<int64_t>(c->k_offs) + (n - 1), sizeof(int64_t),
+                                 hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(&c->cand_tail[1], as<int64_t>(c->k_cnt) + (n - 1), sizeof(int64_t),
+                                 hipMemcpyDeviceToHost, s));
+    }
+    return OVL_OK;
+}
+
+int cand_emit(Dev* c, int32_t k) {
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t total = c->cand_tail[0] + c->cand_tail[1];
+    HIPCHK(c, ensure(c->cand_a, (size_t)total * sizeof(int32_t)));
+    HIPCHK(c, ensure(c->cand_b, (size_t)total * sizeof(int32_t)));
+    if (total > 0)
+        HIPCHK(c, ovl_cand_emit(as<int32_t>(c->k_order), as<int64_t>(c->k_lo), as<int64_t>(c->k_hi),
+                                as<int64_t>(c->k_offs), c->n_reads, k == 0 ? 1 : 0, as<int32_t>(c->cand_a),
+                                as<int32_t>(c->cand_b), c->stream));
+    return OVL_OK;
+}
+
+}  // namespace
+
+OVL_API int ovl_candidates(ovl_ctx* ctx, int32_t k, int64_t* out_n_pairs) {
+    if (!ctx) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
+    quiet(ctx);
+    if (!out_n_pairs) return fail(ctx, OVL_E_ARG, "out_n_pairs is NULL");
+    if (k < 0) return fail(ctx, OVL_E_ARG, "k-mer length must be non-negative (k=%d)", k);
+    Dev* d0 = ctx->devs[0];
+    if (d0->n_reads < 0) return fail(ctx, OVL_E_STATE, "no resident reads: call ovl_set_reads first");
+    const int32_t bits = d0->planes;
+    if (k > 0 && (int64_t)k * bits > 58)
+        return fail(ctx, OVL_E_UNSUPPORTED, "k=%d with %d-bit symbols does not fit a 64-bit key (k * bits <= 58)", k,
+                    bits);
+    DeviceGuard guard;
+    CpuShare::get().refresh();
+    // every device enumerates the same list from its own copy of the reads (no list broadcast); the
+    // phases overlap across devices
+    int rc = OVL_OK;
+    for (Dev* d : ctx->devs)
+        if ((rc = cand_count(d, k)) != OVL_OK) break;
+    for (Dev* d : ctx->devs) {
+        (void)hipSetDevice(d->device);
+        hipError_t e = hipStreamSynchronize(d->stream);
+        if (rc == OVL_OK && e != hipSuccess) rc = fail(ctx, OVL_E_HIP, "ovl_candidates: %s", hipGetErrorString(e));
+    }
+    if (rc != OVL_OK) return rc;
+    for (Dev* d : ctx->devs)
+        if ((rc = cand_emit(d, k)) != OVL_OK) break;
+    for (Dev* d : ctx->devs) {
+        (void)hipSetDevice(d->device);
+        hipError_t e = hipStreamSynchronize(d->stream);
+        if (rc == OVL_OK && e != hipSuccess) rc = fail(ctx, OVL_E_HIP, "ovl_candidates: %s", hipGetErrorString(e));
+    }
+    if (rc != OVL_OK) return rc;
+    const int64_t total = d0->cand_tail[0] + d0->cand_tail[1];
+    for (Dev* d : ctx->devs) {
+        d->cand_n = total;
+        d->heavy_for = -1;  // a new list: heavy tiles rebuilt on its first launch
+    }
+    *out_n_pairs = total;
+    return OVL_OK;
+}
+
+OVL_API int ovl_candidates_copy(ovl_ctx* ctx, int32_t* a_idx, int32_t* b_idx) {
+    if (!ctx) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
+    Dev* c = ctx->devs[0];
+    if (c->cand_n < 0) return fail(c, OVL_E_STATE, "no candidate list: call ovl_candidates first");
+    if (c->cand_n == 0) return OVL_OK;
+    if (!a_idx || !b_idx) return fail(c, OVL_E_ARG, "NULL host pointer");
+    DeviceGuard guard;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t bytes = (size_t)c->cand_n * sizeof(int32_t);
+    HIPCHK(c, hipMemcpyAsync(a_idx, c->cand_a.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(b_idx, c->cand_b.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return OVL_OK;
+}
+
+OVL_API int ovl_candidates_device(const ovl_ctx* ctx, const int32_t** d_a_idx, const int32_t** d_b_idx,
+                                  int64_t* n_pairs) {
+    if (!ctx) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
+    const Dev* c = ctx->devs[0];
+    if (c->cand_n < 0) return fail(c, OVL_E_STATE, "no candidate list: call ovl_candidates first");
+    if (d_a_idx) *d_a_idx = reinterpret_cast<const int32_t*>(c->cand_a.p);
+    if (d_b_idx) *d_b_idx = reinterpret_cast<const int32_t*>(c->cand_b.p);
+    if (n_pairs) *n_pairs = c->cand_n;
+    return OVL_OK;
+}
+
+OVL_API int ovl_candidates_shards(ovl_ctx* ctx, int32_t n_shards, int64_t* bounds) {
+    if (!ctx) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
+    quiet(ctx);
+    if (n_shards <= 0 || !bounds) return fail(ctx, OVL_E_ARG, "n_shards <= 0 or bounds is NULL");
+    Dev* d = ctx->devs[0];
+    if (d->cand_n < 0) return fail(ctx, OVL_E_STATE, "no candidate list: call ovl_candidates first");
+    DeviceGuard guard;
+    std::vector<int64_t> cuts;
+    int rc = device_cuts(d, 0, d->cand_n, n_shards, cuts);
+    if (rc != OVL_OK) return rc;
+    std::copy(cuts.begin(), cuts.end(), bounds);
+    return OVL_OK;
+}
+
+namespace {
+
+constexpr int kResidentFellBack = 1000;  // (resident_call: the call goes through the launch pipeline instead)
+
+// A call over the resident candidate list that the resident grid scores: one device, the uniform kernel's form with
+// int32 keys and 2-byte record codes (ends <= 254), timing off (its launch events time the launch pipeline), and a
+// host pool of at least 6 threads to expand the records (fewer: several processes share the CPUs, pack_ok)
+bool resident_ok(const ovl_ctx* c, const Plan& p, int64_t n) {
+    if (devices_used(c, n) != 1 || c->timing || CopyPool::threads() < 6) return false;
+    const Dev* d = c->devs[0];
+    if (d->k.resident == 0 || d->res.broken) return false;
+    if (d->k.resident == 1 && (n < d->k.resident_min || n > d->k.resident_max)) return false;
+    return p.kernel == OVL_KERNEL_UNGAPPED && !p.key64 && d->planes == 2 && d->wmax >= 1 && d->wmax <= 8 &&
+           d->lmax >= 1 && d->lmax <= 254 && d->cand_n >= 0;
+}
+
+int resident_call(ovl_ctx* ctx, int64_t lo, int64_t hi, int32_t match, int32_t mismatch, int32_t* out_s,
+                  int32_t* out_e) {
+    Dev* d = ctx->devs[0];
+    HIPCHK(d, hipSetDevice(d->device));
+    // heavy tiles first when the range starts on a list tile (uniform_kernel's order); built once per list, with the
+    // grid stopped (ensure_heavy may reallocate)
+    ResidentCall rc_;
+    if (lo % 64 == 0) {
+        if (d->heavy_for != d->cand_n) {
+            (void)d->res.stop();
+            const int r = ensure_heavy(d);
+            if (r != OVL_OK) return r;
+        }
+        const int64_t t0 = lo / 64, t1 = t0 + (hi - lo + 63) / 64;
+        const auto k0 = std::lower_bound(d->h_heavy.begin(), d->h_heavy.end(), t0);
+        const auto k1 = std::lower_bound(d->h_heavy.begin(), d->h_heavy.end(), t1);
+        if (k1 > k0) {
+            rc_.heavy_ids = as<int32_t>(d->heavy_ids) + (k0 - d->h_heavy.begin());
+            rc_.heavy_n = (int64_t)(k1 - k0);
+            rc_.tile_base = t0;
+        }
+    }
+    ResidentReads rd;
+    rd.sfx = as<uint32_t>(d->sfx);
+    rd.pfx = as<uint32_t>(d->pfx);
+    rd.len = as<int32_t>(d->len);
+    rd.n_reads = d->n_reads;
+    rd.lw = d->lmax;
+    rd.wmax = d->wmax;
+    rd.full = as<uint32_t>(d->full);
+    rd.tile_flags = rc_.heavy_n > 0 ? as<uint8_t>(d->tile_flags) : nullptr;
+    rc_.d_a = as<int32_t>(d->cand_a) + lo;
+    rc_.d_b = as<int32_t>(d->cand_b) + lo;
+    rc_.n = hi - lo;
+    rc_.match = match;
+    rc_.mismatch = mismatch;
+    rc_.out_s = out_s;
+    rc_.out_e = out_e;
+    const auto t0 = std::chrono::steady_clock::now();
+    int64_t n_bad = 0;
+    hipError_t e = hipSuccess;
+    const int r = d->res.score(rd, rc_, &n_bad, &e);
+    if (r == ResidentGrid::kFallback) return kResidentFellBack;
+    if (r != ResidentGrid::kOk)
+        return fail(ctx, OVL_E_HIP, "resident grid: %s", hipGetErrorString(e));
+    ctx->t_launches.clear();
+    ctx->t_kernel_ms = 0.0;
+    ctx->t_call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    const int64_t n = hi - lo, nt = (n + 63) / 64;
+    ctx->x_res_bytes = 128 * nt + 8 * d->res.last_specials;
+    ctx->x_link_bytes = ctx->x_res_bytes;
+    ctx->x_packed_pairs = n;
+    ctx->x_rec_pairs = n;
+    ctx->x_esc = d->res.last_specials;
+    ctx->x_ix_pairs = ctx->x_dec_pairs = 0;
+    if (n_bad > 0) return fail(ctx, OVL_E_INDEX, "a pair index is outside [0, %d)", d->n_reads);
+    return OVL_OK;
+}
+
+}  // namespace
+
+OVL_API int ovl_devices_for(const ovl_ctx* ctx, int64_t n_pairs, int32_t* out_devices) {
+    if (!ctx || !out_devices) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx or out_devices is NULL");
+    if (n_pairs < 0) return fail(ctx, OVL_E_ARG, "n_pairs < 0");
+    *out_devices = devices_for(ctx, n_pairs);
+    return OVL_OK;
+}
+
+OVL_API int ovl_quiesce(ovl_ctx* ctx) {
+    if (!ctx) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
+    DeviceGuard guard;
+    for (Dev* d : ctx->devs) HIPCHK(ctx, d->res.stop());
+    return OVL_OK;
+}
+
+OVL_API int ovl_resident_stats(const ovl_ctx* ctx, int32_t* alive, int64_t* launches, int64_t* relaunches,
+                               int32_t* broken) {
+    if (!ctx) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
+    int32_t al = 0, br = 0;
+    int64_t l = 0, rl = 0;
+    for (const Dev* d : ctx->devs) {
+        al += d->res.alive() ? 1 : 0;
+        br += d->res.broken ? 1 : 0;
+        l += d->res.n_launches;
+        rl += d->res.n_relaunches;
+    }
+    if (alive) *alive = al;
+    if (launches) *launches = l;
+    if (relaunches) *relaunches = rl;
+    if (broken) *broken = br;
+    return OVL_OK;
+}
+
+OVL_API int ovl_score_candidates_range(ovl_ctx* ctx, int64_t lo, int64_t hi, int32_t match, int32_t mismatch,
+                                       int64_t indel, int32_t band, int32_t* out_score, int32_t* out_end) {
+    if (!ctx) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
+    Dev* d0 = ctx->devs[0];
+    if (d0->cand_n < 0) return fail(ctx, OVL_E_STATE, "no candidate list: call ovl_candidates first");
+    if (lo < 0 || hi < lo || hi > d0->cand_n)
+        return fail(ctx, OVL_E_ARG, "range [%lld, %lld) outside the candidate list [0, %lld)", (long long)lo,
+                    (long long)hi, (long long)d0->cand_n);
+    Plan p;
+    int rc = check_scoring_args(ctx, match, mismatch, indel, band, &p);
+    if (rc != OVL_OK) return rc;
+    if (hi == lo) return OVL_OK;
+    if (!out_score || !out_end) return fail(ctx, OVL_E_ARG, "NULL host pointer");
+    DeviceGuard guard;
+    if (resident_ok(ctx, p, hi - lo)) {
+        rc = resident_call(ctx, lo, hi, match, mismatch, out_score, out_end);
+        if (rc != kResidentFellBack) return rc;
+    }
+    quiet(ctx);
+    const size_t bytes = sizeof(int32_t) * (size_t)(hi - lo);
+    Call C;
+    C.plan = &p;
+    C.match = match;
+    C.mismatch = mismatch;
+    C.indel = indel;
+    C.out_s = out_score;
+    C.out_e = out_end;
+    C.out_base = lo;
+    C.out_pinned = host_pinned(out_score, bytes) && host_pinned(out_end, bytes);
+    C.timing = ctx->timing != 0;
+    const int32_t S = devices_used(ctx, hi - lo);
+    C.pack = pack_ok(ctx, p, hi - lo, C.out_pinned, S);
+    std::vector<int64_t> cuts;
+    rc = device_cuts(d0, lo, hi, S, cuts);
+    if (rc != OVL_OK) return rc;
+    std::vector<Job> jobs((size_t)S);
+    for (int32_t r = 0; r < S; ++r) {
+        Job& J = jobs[(size_t)r];
+        J.d = ctx->devs[(size_t)r];
+        J.lo = cuts[(size_t)r];
+        J.hi = cuts[(size_t)r + 1];
+        J.dev_a = as<int32_t>(J.d->cand_a);
+        J.dev_b = as<int32_t>(J.d->cand_b);
+    }
+    return run_pipeline(ctx, C, jobs);
+}
+
+OVL_API int ovl_score_candidates(ovl_ctx* ctx, int32_t match, int32_t mismatch, int64_t indel, int32_t band,
+                                 int32_t* out_score, int32_t* out_end) {
+    if (!ctx) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
+    const int64_t n = ctx->devs[0]->cand_n;
+    if (n < 0) return fail(ctx, OVL_E_STATE, "no candidate list: call ovl_candidates first");
+    return ovl_score_candidates_range(ctx, 0, n, match, mismatch, indel, band, out_score, out_end);
+}

@@ -1,5 +1,5 @@
 // ovl_digest.h -- the 128-bit digest of a read set's bytes that ovl_set_reads keeps for its resident-set check
-// (ovl_api.cpp same_reads) instead of a host copy of the bytes.  Host code only.
+// (ovl_reads.cpp same_reads) instead of a host copy of the bytes.  Host code only.
 #pragma once
 
 #include <immintrin.h>
@@ -25,7 +25,7 @@ constexpr int kHashLanes = 32;
 inline uint64_t hash_rotl(uint64_t h, int r) { return (h << r) | (h >> (64 - r)); }
 // the lane loop over the whole 256-byte blocks of [q, q + len) in four zmm (vpmullq: the same products as the scalar
 // loop's, so either gives the same digest); returns the bytes done
-__attribute__((target("avx512f,avx512dq"))) size_t hash_lanes_avx512(const uint8_t* q, size_t len, uint64_t* h) {
+__attribute__((target("avx512f,avx512dq"))) inline size_t hash_lanes_avx512(const uint8_t* q, size_t len, uint64_t* h) {
     __m512i v0 = _mm512_loadu_si512(h), v1 = _mm512_loadu_si512(h + 8), v2 = _mm512_loadu_si512(h + 16),
             v3 = _mm512_loadu_si512(h + 24);
     const __m512i m = _mm512_set1_epi64((long long)kHashM);
@@ -43,7 +43,7 @@ __attribute__((target("avx512f,avx512dq"))) size_t hash_lanes_avx512(const uint8
     return k;
 }
 
-void reads_hash(const uint8_t* p, int64_t n, uint64_t out[2]) {
+inline void reads_hash(const uint8_t* p, int64_t n, uint64_t out[2]) {
     constexpr size_t kPart = size_t(1) << 18;  // (the pool's parts: as many as round 5's byte compare had)
     static const bool a512 = ovl_expand::rec_avx512();
     const size_t parts = (size_t)((n + (int64_t)kPart - 1) / (int64_t)kPart);

@@ -888,11 +888,7 @@ static int row_advance(RowCtx* R, int64_t u, int all) {
    what inserting it costs, and the edges whose fate the replay decides last -- the graph's last cycles -- are
    otherwise all built after it has ended; an edge removed after its dict was made only costs that dict (released at
    the end).  Each node once, in node order.  Returns the dicts made (0: every node passed), -1 on error. */
-#ifndef OVL_SPEC_AHEAD
-#define OVL_SPEC_AHEAD 1 /* (0: no dicts made ahead -- an A/B build, tools/stream_ab.py) */
-#endif
 static int64_t spec_advance(RowCtx* R, int64_t* su, int64_t n_nodes, int64_t budget) {
-    if (!OVL_SPEC_AHEAD) return 0;
     const Layout* L = R->P->L;
     int64_t made = 0;
     while (*su < n_nodes && made < budget) {
@@ -1300,7 +1296,7 @@ static PyObject* build_overlap_stream_impl(PyObject* self, PyObject* args) {
                 const int64_t m = spec_advance(&R, &spec_u, N, 256);
                 if (m < 0) goto done;
                 if (m == 0) {
-                    if (OVL_SPEC_AHEAD) (void)spec_reap(&R, &reap_e, E, 16384);
+                    (void)spec_reap(&R, &reap_e, E, 16384);
                     Py_BEGIN_ALLOW_THREADS
                     sched_yield();
                     Py_END_ALLOW_THREADS

@@ -144,22 +144,6 @@ __global__ __launch_bounds__(256, OCC) void dp_lane_kernel(const uint8_t* __rest
             // PROF: a row's profile word w holds s(x, t[j0 + 4w + k]) in byte k (x = the row's symbol); a
             // cell adds its byte with a sign-extending SDWA add
             constexpr int PW = PROF ? CW / 4 : 1;
-#ifdef OVL_LANE_MUX  // A/B reference: four byte profiles per strip, three bit muxes per word per row
-            uint32_t PX[4][PW];
-            if constexpr (PROF) {
-#pragma unroll
-                for (int x = 0; x < 4; ++x) {
-#pragma unroll
-                    for (int w = 0; w < PW; ++w) {
-                        uint32_t word = 0;
-#pragma unroll
-                        for (int k = 0; k < 4; ++k)
-                            word |= ((uint32_t)(tc[4 * w + k] == (uint32_t)x ? s_ma : s_mm) & 0xFFu) << (8 * k);
-                        PX[x][w] = word;
-                    }
-                }
-            }
-#else
             // the strip's t codes as bytes (TW[w] byte k = t[j0 + 4w + k], codes 0..3); a row's profile
             // word is one v_perm_b32 of its 4-byte score table by these codes
             uint32_t TW[PW];
@@ -170,7 +154,6 @@ __global__ __launch_bounds__(256, OCC) void dp_lane_kernel(const uint8_t* __rest
             }
             const uint32_t tbl_base = ((uint32_t)s_mm & 0xFFu) * 0x01010101u;   // every t mismatches
             const uint32_t tbl_diff = ((uint32_t)(s_ma ^ s_mm)) & 0xFFu;        // byte x -> match score
-#endif
             int32_t A[CW], B[CW];
 #pragma unroll
             for (int c = 0; c < CW; ++c) A[c] = -g * (j0 + 1 + c);  // row 0: G[0][j] = -indel * j
@@ -230,22 +213,12 @@ __global__ __launch_bounds__(256, OCC) void dp_lane_kernel(const uint8_t* __rest
                         m1 = (uint32_t)(((int32_t)(sc << 30)) >> 31);
                     }
                     const uint32_t nv = (uint32_t)~((it - sk) >> 31);  // 0 on virtual rows
-#ifdef OVL_LANE_MUX
-#pragma unroll
-                    for (int w = 0; w < PW; ++w) {
-                        const uint32_t lo = __builtin_amdgcn_bitop3_b32(m0, PX[1][w], PX[0][w], 0xCA);  // m0 ? : mux
-                        const uint32_t hi = __builtin_amdgcn_bitop3_b32(m0, PX[3][w], PX[2][w], 0xCA);
-                        P[w] = __builtin_amdgcn_bitop3_b32(m1, hi, lo, 0xCA);
-                        if constexpr (MASKED) P[w] &= nv;  // zero profile: the row repeats row 0
-                    }
-#else
                     // row symbol x = bit0 | bit1 << 1; its table: byte t = s(x, t) in G units
                     const uint32_t x8 = (m0 & 8u) | (m1 & 16u);          // 8 * x
                     uint32_t tbl = tbl_base ^ (tbl_diff << x8);
                     if constexpr (MASKED) tbl &= nv;                       // zero profile: the row repeats row 0
 #pragma unroll
                     for (int w = 0; w < PW; ++w) P[w] = __builtin_amdgcn_perm(tbl, tbl, TW[w]);
-#endif
                 }
 #pragma unroll
                 for (int c = 0; c < CW; ++c) {
@@ -376,8 +349,8 @@ __global__ __launch_bounds__(256, OCC) void dp_lane_kernel(const uint8_t* __rest
 //
 // The hand-off column: 4-bit steps of both pairs, a dword per four rows (pair p in bits 0-15, p + 64 in bits
 // 16-31), in HBM per tile ([tile][row / 4][lane], read two quads ahead; the next strip reads it soon after, from
-// the caches).  In LDS (the OVL_H2_LDS build) its 16 KiB per wavefront capped residency at 2.5 wavefronts per
-// SIMD: 13.0 ms against 11.1 for cfg5's full DP.  A step's f16 value plus 1024 has the step in its low mantissa
+// the caches).  In LDS (a build variant since removed) its 16 KiB per wavefront capped residency at 2.5 wavefronts
+// per SIMD: 13.0 ms against 11.1 for cfg5's full DP.  A step's f16 value plus 1024 has the step in its low mantissa
 // bits, which is how steps move between f16 cells and nibbles in both directions.
 typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
 
@@ -408,15 +381,7 @@ __global__ __launch_bounds__(128, OCC) void dp_lane_h2_kernel(const int32_t* __r
                                                               uint32_t* __restrict__ colbuf, int32_t hq) {
     constexpr int CW = 32;
     const int lane = threadIdx.x & 63;
-#ifndef OVL_H2_LDS  // the hand-off column per tile in HBM ([tile][row quad][lane], hq quads); A/B: LDS
-    constexpr int HS = 64;
-#else
-    constexpr int HS = 128;  // hand-off dwords per row quad: [wavefront in block][lane]
-    extern __shared__ uint32_t lds_hand[];
-    uint32_t* __restrict__ hcol = lds_hand + (threadIdx.x >> 6) * 64 + lane;
-    (void)colbuf;
-    (void)hq;
-#endif
+    constexpr int HS = 64;  // the hand-off column per tile in HBM ([tile][row quad][lane], hq quads)
     const int64_t wslot = (int64_t)blockIdx.x * 2 + (threadIdx.x >> 6);
     const int64_t nslots = (int64_t)gridDim.x * 2;
     const int64_t ntiles = (n_pairs + 127) >> 7;
@@ -428,9 +393,7 @@ __global__ __launch_bounds__(128, OCC) void dp_lane_h2_kernel(const int32_t* __r
     const uint32_t tbl_diff = hi_ma ^ hi_mm;         // byte x -> match
     const half2_t h1024 = h2_splat(1024);
     for (int64_t tile = wslot; tile < ntiles; tile += nslots) {
-#ifndef OVL_H2_LDS
         uint32_t* __restrict__ hcol = colbuf + tile * (int64_t)hq * 64 + lane;
-#endif
         int64_t p[2];
         bool live[2], bad[2];
         int32_t n[2], m[2], sk[2], best[2], bend[2];
@@ -518,14 +481,9 @@ __global__ __launch_bounds__(128, OCC) void dp_lane_h2_kernel(const int32_t* __r
                     vprev -= C;
                 }
                 if constexpr (!FIRST) {
-#ifndef OVL_H2_LDS  // two quads ahead
-                    hr = hn;
+                    hr = hn;  // two quads ahead
                     hn = hn2;
                     if (it + 8 < R) hn2 = hcol[(int64_t)(it / 4 + 2) * HS];
-#else
-                    hr = hn;
-                    if (it + 4 < R) hn = hcol[(int64_t)(it / 4 + 1) * HS];
-#endif
                 }
                 half2_t d[4], l[4];
                 uint32_t t0[4], t1[4];
@@ -799,7 +757,7 @@ __global__ __launch_bounds__(256, OCC) void band_lane_kernel(const uint8_t* __re
         else fetch4(0);
         int32_t it = 0;
         for (; it < mcut; it += 4) body(it, std::true_type{});
-#ifndef OVL_BAND_UNROLL1  // eight rows per trip, as in band_lane2_kernel
+        // eight rows per trip, as in band_lane2_kernel
         if (it < R && ((R - it) & 7)) {
             body(it, std::false_type{});
             it += 4;
@@ -808,9 +766,6 @@ __global__ __launch_bounds__(256, OCC) void band_lane_kernel(const uint8_t* __re
             body(it, std::false_type{});
             body(it + 4, std::false_type{});
         }
-#else
-        for (; it < R; it += 4) body(it, std::false_type{});
-#endif
         // row n: in-band cells with 0 <= j <= m, largest value, first j (the oracle's scan)
         int32_t best = INT32_MIN, bend = -1;
 #pragma unroll
@@ -1041,7 +996,6 @@ __global__ __launch_bounds__(256, OCC) void band_lane2_kernel(const uint8_t* __r
         else fetch4(0);
         int32_t t = 0;
         for (; t < mcut + 1 && t < R; t += 4) body(t, std::true_type{});
-#ifndef OVL_BAND_UNROLL1
         // eight rows per trip: the window's one-word shift per four rows lands in place in the first body and
         // costs a register move per window word only at the trip's end (half the moves)
         if (t < R && ((R - t) & 7)) {
@@ -1052,9 +1006,6 @@ __global__ __launch_bounds__(256, OCC) void band_lane2_kernel(const uint8_t* __r
             body(t, std::false_type{});
             body(t + 4, std::false_type{});
         }
-#else
-        for (; t < R; t += 4) body(t, std::false_type{});
-#endif
         if (!h) scan();  // lane 0 has finished iteration R - 1
         // step R: lane 1's last iteration (R - 1, byte 3 of the last group); lane 0's cells are no longer read
         step(R, xs8_prev >> 24, ts_prev >> 24, std::true_type{});
@@ -1077,10 +1028,6 @@ __global__ __launch_bounds__(256, OCC) void band_lane2_kernel(const uint8_t* __r
 }  // namespace ovl
 
 using ovl::dp_lane_kernel;
-
-#ifndef OVL_H2_OCC
-#define OVL_H2_OCC 3
-#endif
 
 extern "C" int32_t ovl_dp_lane_rcap(int32_t lcap) { return ((lcap + 31) & ~31) + 4; }
 
@@ -1105,15 +1052,9 @@ extern "C" int32_t ovl_dp_lane_h2_ok(int64_t match, int64_t mismatch, int64_t in
                    std::max(match, mismatch) - 2 * indel <= 15 ? 1 : 0;
 }
 
-// hand-off bytes dp_lane_h2_kernel needs in HBM (0: it hands off through LDS)
+// hand-off bytes dp_lane_h2_kernel needs in HBM
 extern "C" int64_t ovl_dp_lane_h2_col_bytes(int64_t n_pairs, int32_t lcap) {
-#ifndef OVL_H2_LDS
     return (n_pairs + 127) / 128 * (int64_t)(((lcap + 31) & ~31) / 4) * 64 * 4;
-#else
-    (void)n_pairs;
-    (void)lcap;
-    return 0;
-#endif
 }
 
 extern "C" hipError_t ovl_launch_dp_lane(const OvlDpArgs* g, const OvlLaneArgs* k, hipStream_t stream) {
@@ -1127,30 +1068,19 @@ extern "C" hipError_t ovl_launch_dp_lane(const OvlDpArgs* g, const OvlLaneArgs* 
         // a 128-pair tile per wavefront, two per block, all launched: the dispatcher places blocks as they free up
         // (resident slots looping over the tiles: 18.5 ms against 13.0, cfg5's full DP with the LDS hand-off)
         const int64_t tiles = (g->n_pairs + 127) / 128;
-#ifdef OVL_LANE_GRID_SLOTS  // A/B: k->slots resident wavefronts looping over the tiles
-        int64_t blocks = (std::min<int64_t>(k->slots, tiles) + 1) / 2;
-#else
         int64_t blocks = (tiles + 1) / 2;
-#endif
         if (blocks < 1) blocks = 1;
-#ifndef OVL_H2_LDS
         const size_t shmem = 0;
         if (!k->colbuf) return hipErrorInvalidValue;
-#else
-        const size_t shmem = (size_t)((lcap + 31) & ~31) / 4 * 128 * 4;
-#endif
-        ovl::dp_lane_h2_kernel<OVL_H2_OCC><<<(unsigned)blocks, 128, shmem, stream>>>(
+        ovl::dp_lane_h2_kernel<3><<<(unsigned)blocks, 128, shmem, stream>>>(
             g->len, g->n_reads, k->sfx_words, k->pfx_words, k->srow, k->wsfx, g->a_idx, g->b_idx, g->n_pairs,
             lcap, (int32_t)g->match, (int32_t)g->mismatch, (int32_t)g->indel, g->out_score, g->out_end,
             g->err_flag, k->colbuf, ((lcap + 31) & ~31) / 4);
         return hipGetLastError();
     }
     const int64_t tiles = (g->n_pairs + 63) / 64;
-#ifndef OVL_LANE_GRID_SLOTS  // (the LDS hand-off only: the HBM hand-off columns are per resident slot)
+    // a tile per wavefront with the LDS hand-off; the HBM hand-off columns (HO 0 / 1) are per resident slot
     int64_t blocks = k->ho == 2 ? (tiles + 3) / 4 : (std::min<int64_t>(k->slots, tiles) + 3) / 4;
-#else
-    int64_t blocks = (std::min<int64_t>(k->slots, tiles) + 3) / 4;
-#endif
     if (blocks < 1) blocks = 1;
     const int32_t lcap = g->mcap;
     const int32_t rcap = ovl_dp_lane_rcap(lcap);
@@ -1183,16 +1113,11 @@ namespace {
 constexpr int kBandLaneMax = 64;
 
 template <int W, bool PL>
-hipError_t launch_band_lane_w(const OvlDpArgs* g, const OvlLaneArgs* k, int64_t blocks, hipStream_t stream) {
+hipError_t launch_band_lane_w(const OvlDpArgs* g, const OvlLaneArgs* k, hipStream_t stream) {
     constexpr int NB = 2 * W + 1;
     constexpr int OCC = NB <= 9 ? 8 : (NB <= 25 ? 6 : (NB <= 57 ? 4 : (NB <= 65 ? 3 : (NB <= 113 ? 2 : 1))));
-    if constexpr (OCC == 8) {  // (the grid the caller sized for 6 wavefronts per SIMD, grown to 8)
-        const int64_t tiles = (g->n_pairs + 63) / 64;
-        blocks = std::max<int64_t>(1, (std::min<int64_t>(k->slots / 6 * 8, tiles) + 3) / 4);
-    }
-#ifndef OVL_LANE_GRID_SLOTS
-    blocks = std::max<int64_t>(1, ((g->n_pairs + 63) / 64 + 3) / 4);
-#endif
+    // a tile per wavefront, the dispatcher places blocks as they free up
+    const int64_t blocks = std::max<int64_t>(1, ((g->n_pairs + 63) / 64 + 3) / 4);
     ovl::band_lane_kernel<NB, OCC, PL><<<(unsigned)blocks, 256, 0, stream>>>(
         g->codes, g->off, g->len, g->n_reads, k->sfx_words, k->pfx_words, k->srow, k->wsfx, g->a_idx, g->b_idx,
         g->n_pairs, g->mcap, (int32_t)g->match, (int32_t)g->mismatch, (int32_t)g->indel, g->out_score, g->out_end,
@@ -1207,11 +1132,7 @@ hipError_t launch_band_lane2_w(const OvlDpArgs* g, const OvlLaneArgs* k, hipStre
     constexpr int H = W + 1;
     constexpr int OCC = H <= 17 ? 6 : (H <= 33 ? 4 : 3);
     const int64_t tiles = (g->n_pairs + 31) / 32;
-#ifndef OVL_LANE_GRID_SLOTS  // a tile per wavefront, the dispatcher places blocks as they free up
-    int64_t blocks = (tiles + 3) / 4;
-#else
-    int64_t blocks = (std::min<int64_t>(k->slots / 6 * OCC, tiles) + 3) / 4;
-#endif
+    int64_t blocks = (tiles + 3) / 4;  // a tile per wavefront, the dispatcher places blocks as they free up
     if (blocks < 1) blocks = 1;
     ovl::band_lane2_kernel<NB, OCC, PL><<<(unsigned)blocks, 256, 0, stream>>>(
         g->codes, g->off, g->len, g->n_reads, k->sfx_words, k->pfx_words, k->srow, k->wsfx, g->a_idx, g->b_idx,
@@ -1224,17 +1145,16 @@ hipError_t launch_band_lane2_w(const OvlDpArgs* g, const OvlLaneArgs* k, hipStre
 constexpr int next_band_lane(int w) { return w < 32 ? w + 1 : w + 8; }
 
 template <int W>
-hipError_t dispatch_band_lane(int band, const OvlDpArgs* g, const OvlLaneArgs* k, int64_t blocks,
-                              hipStream_t stream) {
+hipError_t dispatch_band_lane(int band, const OvlDpArgs* g, const OvlLaneArgs* k, hipStream_t stream) {
     if (band == W) {
         if constexpr (W >= 1)
             if (k->split)
                 return k->sfx ? launch_band_lane2_w<W, true>(g, k, stream)
                               : launch_band_lane2_w<W, false>(g, k, stream);
-        return k->sfx ? launch_band_lane_w<W, true>(g, k, blocks, stream)
-                      : launch_band_lane_w<W, false>(g, k, blocks, stream);
+        return k->sfx ? launch_band_lane_w<W, true>(g, k, stream)
+                      : launch_band_lane_w<W, false>(g, k, stream);
     }
-    if constexpr (W < kBandLaneMax) return dispatch_band_lane<next_band_lane(W)>(band, g, k, blocks, stream);
+    if constexpr (W < kBandLaneMax) return dispatch_band_lane<next_band_lane(W)>(band, g, k, stream);
     return hipErrorInvalidValue;
 }
 }  // namespace
@@ -1247,8 +1167,5 @@ extern "C" hipError_t ovl_launch_band_lane(const OvlDpArgs* g, const OvlLaneArgs
     if (g->n_pairs <= 0) return hipSuccess;
     if (g->band < 0 || g->band > kBandLaneMax) return hipErrorInvalidValue;
     if (k->sfx && (!k->sfx_words || !k->pfx_words || k->wsfx * 32 < g->mcap)) return hipErrorInvalidValue;
-    const int64_t tiles = (g->n_pairs + 63) / 64;
-    int64_t blocks = (std::min<int64_t>(k->slots, tiles) + 3) / 4;
-    if (blocks < 1) blocks = 1;
-    return dispatch_band_lane<0>(g->band, g, k, blocks, stream);
+    return dispatch_band_lane<0>(g->band, g, k, stream);
 }

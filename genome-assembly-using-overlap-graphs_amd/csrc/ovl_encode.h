@@ -1,4 +1,4 @@
-// ovl_encode.h — host encoding of a compact pair list (ovl_api.cpp encode_chunk, decoded on the device by
+// ovl_encode.h — host encoding of a compact pair list (ovl_pipeline.cpp encode_chunk, decoded on the device by
 // ovl_pairs.hip).  Host code only (tests/c/encode_test.cpp checks every variant against the scalar form).
 //
 // Passes over a part [lo, hi) of one chunk, each reading one of the caller's int32 arrays once:

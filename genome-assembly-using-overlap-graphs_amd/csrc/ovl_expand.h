@@ -1,6 +1,6 @@
 // ovl_expand.h — host expansion of packed results (ovl_kernels.hip put_pair, sink 2) into the caller's
-// int32 (score, end) arrays.  Host code only (ovl_api.cpp; tests/c/expand_test.cpp checks every variant
-// against the scalar form).
+// int32 (score, end) arrays.  Host code only (ovl_pipeline.cpp host_expand; tests/c/expand_test.cpp checks every
+// variant against the scalar form).
 //
 // Per pair one uint16 v = j << 8 | X (end j, mismatch count X over the L = j compared bases):
 //   score = match*(j - X) + mismatch*X,  end = j

@@ -1,4 +1,4 @@
-// ovl_kernels.h — launch interface between the C ABI (ovl_api.cpp) and the kernels.
+// ovl_kernels.h — launch interface between the C ABI's host files (ovl_ctx.h) and the kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -36,7 +36,7 @@ struct OvlUngappedArgs {
     int64_t tile_base;          // the launch's first pair / 64 within the list
     const uint16_t* ix_b16;  // non-null: uniform_kernel (throughput mode, int32 keys) reads a compact pair list
     const uint8_t* ix_d8;    // instead of a_idx / b_idx: b = ix_b16[p] (0xFFFF: a bad index), a = ix_base[p / 64]
-    const int32_t* ix_base;  // + ix_d8[p]; the host pool encodes each chunk (ovl_api.cpp encode_chunk) and the
+    const int32_t* ix_base;  // + ix_d8[p]; the host pool encodes each chunk (ovl_pipeline.cpp encode_chunk) and the
                              // copy engine moves it into HBM on the second stream, where the kernel reads it
     int32_t host_out;    // result sink of uniform_kernel (put_pair): 0 int32 arrays in HBM, 1 host-mapped int32
                          // arrays (non-temporal stores), 2 host-mapped packed (end, mismatches) per pair in
@@ -125,7 +125,7 @@ extern "C" int32_t ovl_dp_lane_h2_ok(int64_t match, int64_t mismatch, int64_t in
 extern "C" int64_t ovl_dp_lane_h2_col_bytes(int64_t n_pairs, int32_t lcap);
 extern "C" hipError_t ovl_launch_dp_lane(const OvlDpArgs* args, const OvlLaneArgs* lane, hipStream_t stream);
 // band knob, a lane per pair (ovl_dp_lane.hip): ovl_band_lane_ok(band), <= 4 symbols, scores in int8;
-// uses lane->slots, and lane->sfx (row symbols and t codes from the bit planes) with sfx/pfx_words
+// uses lane->split, and lane->sfx (row symbols and t codes from the bit planes) with sfx/pfx_words
 extern "C" int32_t ovl_band_lane_ok(int32_t band);
 extern "C" hipError_t ovl_launch_band_lane(const OvlDpArgs* args, const OvlLaneArgs* lane, hipStream_t stream);
 

@@ -34,15 +34,6 @@
 #include "ovl_kernels.h"
 #include "ovl_grid.h"
 
-// uniform sweep: two shifts from one shifted row (sweep_uniform, keys_s2 / keys_t2); 0: one shifted row per shift
-#ifndef OVL_SHIFT_PAIR
-#define OVL_SHIFT_PAIR 1
-#endif
-// uniform sweep: rows of at most this many words shift s (W above: t; every W <= 8 by default)
-#ifndef OVL_SHIFT_S_MAXW
-#define OVL_SHIFT_S_MAXW 8
-#endif
-
 namespace ovl {
 
 #ifdef OVL_TRACE  // diagnostic build only (make trace): per-wavefront timestamps of the uniform kernel
@@ -394,6 +385,8 @@ __device__ __forceinline__ typename Key<KM>::T sweep_shifts(const uint32_t* Sw, 
 // block qm = m/32 is valid for r <= m % 32, so the lane snapshots best[qm] right after shift r = m % 32.
 // tmask (scalar) has bit r set iff some lane of the wavefront snapshots at shift r, so a step takes the
 // snapshot branch only on those shifts; tm = m for a t-truncated lane, -1 otherwise.
+// Rows of at most kShiftSMaxW words shift s (W above: t; every W <= 8 the layouts have).
+constexpr int kShiftSMaxW = 8;
 template <int W, int KM>
 __device__ __forceinline__ typename Key<KM>::T sweep_uniform(const uint32_t* Sw, const uint32_t* Tw, int32_t lw,
                                                              int32_t match, int32_t dms, uint32_t r_lo,
@@ -494,12 +487,12 @@ __device__ __forceinline__ typename Key<KM>::T sweep_uniform(const uint32_t* Sw,
     // two shifts per shifted row for every W (cfg3, W = 5: 191 against 194-197 us with the t shift; cfg5's
     // default scoring, W = 8: 445-449 against 448-452 us, and W = 6 no longer spills; three interleaved passes
     // each, profiles/r03_shift_s_w5_ab.json, r03_shift_s_w8_ab.json)
-    constexpr bool SHIFT_S = W <= OVL_SHIFT_S_MAXW;
+    constexpr bool SHIFT_S = W <= kShiftSMaxW;
     // Two shifts from one shifted s (keys_s2): s shifted down by 31 - r serves shift r + 1 against t as it
     // is and shift r against t moved up one bit (Tup, built once per pair), so a step of two shifts shifts
     // s once.  In Tup, bit 0 of word 0 is t position -1 (no base): that bit of a block's bottom word is
     // masked out (one v_and for blocks q >= 1; folded into the top-word mask for q = 0).
-    constexpr bool PAIR = SHIFT_S && KM == 0 && OVL_SHIFT_PAIR;
+    constexpr bool PAIR = SHIFT_S && KM == 0;
     uint32_t Tup[PAIR ? W : 1][P];
     if constexpr (PAIR) {
 #pragma unroll
@@ -508,10 +501,10 @@ __device__ __forceinline__ typename Key<KM>::T sweep_uniform(const uint32_t* Sw,
             for (int c = 0; c < P; ++c) Tup[i][c] = alignbit(Tw[i * P + c], i ? Tw[(i - 1) * P + c] : 0u, 31u);
         }
     }
-    // The same for the t shift (W > OVL_SHIFT_S_MAXW, keys_t2): t shifted up by r + 1 serves shift r + 1
+    // The same for the t shift (W > kShiftSMaxW, keys_t2): t shifted up by r + 1 serves shift r + 1
     // against s as it is and shift r against s moved down one bit (Sdn); bit 31 of Sdn's word W-1 is position
     // 32W (no base): that bit of a block's top word is masked out.
-    constexpr bool PAIR_T = !SHIFT_S && KM == 0 && OVL_SHIFT_PAIR;
+    constexpr bool PAIR_T = !SHIFT_S && KM == 0;
     uint32_t Sdn[PAIR_T ? W : 1][P];
     if constexpr (PAIR_T) {
 #pragma unroll
@@ -839,14 +832,11 @@ __device__ __forceinline__ void general_unit(bool mine, int64_t p, int32_t a, in
 //    side work overlaps the sweep instead of trailing it.
 // waves per SIMD the kernel is compiled for (VGPR budget 512 / occupancy): the
 // most that fits without spilling
-#ifndef OVL_UNI_OCC_W78
-#define OVL_UNI_OCC_W78 4  // (build macro for A/B builds: int32-key waves per SIMD at W = 7, 8)
-#endif
-#define UNI_OCC(W, KM) ((KM) == 0 ? ((W) <= 4 ? 8 : ((W) <= 5 ? 7 : ((W) <= 6 ? 6 : OVL_UNI_OCC_W78))) \
+#define UNI_OCC(W, KM) ((KM) == 0 ? ((W) <= 4 ? 8 : ((W) <= 5 ? 7 : ((W) <= 6 ? 6 : 4))) \
                                   : ((W) <= 4 ? 7 : ((W) <= 5 ? 6 : ((W) <= 6 ? 5 : 4))))
 // IX: the pair list is read in its compact encoding (b = ix_b16[p], 0xFFFF a bad index; a = ix_base[tile] +
 // ix_d8[p]), which the copy engine moved into HBM beside the previous chunk's launch (3 bytes per pair plus 4 per
-// tile over the link; ovl_api.cpp encode_chunk / issue_chunk): no decode launch before it.
+// tile over the link; ovl_pipeline.cpp encode_chunk / issue_chunk): no decode launch before it.
 template <int W, int KM, bool LAT, int OM, bool IX = false>
 __global__ __launch_bounds__(256, UNI_OCC(W, KM)) void uniform_kernel(
     const uint32_t* __restrict__ sfx, const uint32_t* __restrict__ pfx, const int32_t* __restrict__ len,
@@ -962,7 +952,6 @@ __global__ __launch_bounds__(256, UNI_OCC(W, KM)) void uniform_kernel(
                     rows[s * ROWQ + SROW / 4 + k] = make_uint4(Tw[4 * k], Tw[4 * k + 1], Tw[4 * k + 2], Tw[4 * k + 3]);
             }
             const int cnt = __popcll(pm);
-#ifndef OVL_ABLATE_DRAIN  // diagnostic build only: side pairs left unscored
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
             // issue priority over the co-resident sweeps while the side pairs drain: the drain's chain
             // (LDS restaging, a general sweep, the group max) is the launch's tail otherwise (A/B on one
@@ -995,21 +984,13 @@ __global__ __launch_bounds__(256, UNI_OCC(W, KM)) void uniform_kernel(
                 }
             }
             __builtin_amdgcn_s_setprio(0);
-#endif
             OVL_TR_CLOCK(2, cnt);
             OVL_TR_VAL(7, cnt);
             continue;
         }
         uint32_t Sw[SROW], Tw[TROW];
-#ifdef OVL_ABLATE_LOADS  // diagnostic build only: rows made up from the indices (no row loads)
-#pragma unroll
-        for (int i = 0; i < SROW; ++i) Sw[i] = (uint32_t)a * 0x9E3779B9u + (uint32_t)i * 0x85EBCA6Bu;
-#pragma unroll
-        for (int i = 0; i < TROW; ++i) Tw[i] = (uint32_t)b * 0xC2B2AE35u + (uint32_t)i * 0x27D4EB2Fu;
-#else
         load_words<SROW>(sfx + (int64_t)a * SROW, Sw);
         load_words<TROW>(pfx + (int64_t)b * TROW, Tw);
-#endif
         // read a of length lw? one bit per read (L1-resident bitmap); b's length decides uniform (m = lw).
         // TT: every other pair is scored by this sweep too -- its keys for j <= min(n, m) are the uniform
         // keys (a snapshot of the block maxima after shift min(n, m) % 32), and a shorter read a (n < m) adds
@@ -1033,12 +1014,7 @@ __global__ __launch_bounds__(256, UNI_OCC(W, KM)) void uniform_kernel(
                 ring[(tail + __popcll(pm & ((1ull << lane) - 1ull))) & (RING - 1)] = make_int4((int32_t)p, a, b, 0);
             tail += __popcll(pm);
         }
-#ifdef OVL_ABLATE_SWEEP  // diagnostic build only: keep the loads, skip the sweep
-        T best = (T)(Sw[0] ^ Tw[0] ^ Sw[SROW - 1] ^ Tw[TROW - 1]) & 0;
-        asm volatile("" ::"v"(Sw[0]), "v"(Tw[0]), "v"(Sw[SROW - 1]), "v"(Tw[TROW - 1]));
-#else
         T best = sweep_uniform<W, KM>(Sw, Tw, lw, match, mismatch - match, 0u, 32u, tmask, tm);
-#endif
         if constexpr (TT) {
             const bool win = tt && na < mb;
             uint64_t wm = __ballot(win);
@@ -1060,19 +1036,15 @@ __global__ __launch_bounds__(256, UNI_OCC(W, KM)) void uniform_kernel(
             put_pair<OM>(out_score, out_end, p, ok ? sc : -1, ok ? en : -1, na, match, pack_inv(match, mismatch));
         }
         OVL_TR_CLOCK(4, (uint32_t)best);
-#ifndef OVL_ABLATE_DRAIN
         if constexpr (!LAT) {
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
             while (tail - head >= 16) drain(16);
         }
-#endif
     }
-#ifndef OVL_ABLATE_DRAIN
     if constexpr (!LAT) {
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
         if (tail > head) drain(tail - head);
     }
-#endif
 }
 
 // General kernel: any lengths <= 32W and P bit planes (used when the read set
@@ -1241,10 +1213,7 @@ __device__ __forceinline__ void vm_drain() { asm volatile("s_waitcnt vmcnt(0)" :
 // blocks leave after twice that without a new forward, so a grid whose block 0 never ran still ends.
 // PF: tiles software-pipelined (fewer, fatter wavefronts: 2-4 per SIMD) or one tile at a time (UNI_OCC(W, 0)
 // wavefronts per SIMD, uniform_kernel's register budget)
-#ifndef OVL_RES_PF_OCC
-#define OVL_RES_PF_OCC 2  // (build macro for A/B builds: the software-pipelined form's waves per SIMD at W >= 3)
-#endif
-#define RES_OCC(W, PF) ((PF) ? ((W) >= 3 ? OVL_RES_PF_OCC : 4) : UNI_OCC(W, 0))
+#define RES_OCC(W, PF) ((PF) ? ((W) >= 3 ? 2 : 4) : UNI_OCC(W, 0))
 template <int W, bool PF>
 __global__ __launch_bounds__(256, RES_OCC(W, PF)) void resident_kernel(
     const uint32_t* __restrict__ sfx, const uint32_t* __restrict__ pfx, const int32_t* __restrict__ len,

@@ -1,0 +1,174 @@
+// ovl_local_api.cpp — single alignments (ovl_ctx.h): one pair's full DP with its traceback table (ovl_align_one)
+// and local alignment of two sequences (ovl_local_align, ovl_local.hip).
+#include "ovl_ctx.h"
+
+OVL_API int ovl_align_one(ovl_ctx* ctx, int32_t a, int32_t b, int32_t match, int32_t mismatch, int64_t indel,
+                          int32_t* out_score, int32_t* out_end, int8_t* traceback) {
+    if (!ctx) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
+    quiet(ctx);
+    Dev* c = ctx->devs[0];
+    if (!out_score || !out_end) return fail(c, OVL_E_ARG, "NULL output pointer");
+    if (c->n_reads < 0) return fail(c, OVL_E_STATE, "no resident reads: call ovl_set_reads first");
+    if (a < 0 || a >= c->n_reads || b < 0 || b >= c->n_reads)
+        return fail(c, OVL_E_INDEX, "pair (%d, %d) outside [0, %d)", a, b, c->n_reads);
+    if (c->lmax > kDpMaxLen) return fail(c, OVL_E_UNSUPPORTED, "DP supports reads up to %d bases", kDpMaxLen);
+    DeviceGuard guard;
+    HIPCHK(c, hipSetDevice(c->device));
+    // lengths from the host-visible offsets copy
+    int64_t offs[2][2];
+    HIPCHK(c, hipMemcpy(offs[0], as<int64_t>(c->off) + a, 2 * sizeof(int64_t), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(offs[1], as<int64_t>(c->off) + b, 2 * sizeof(int64_t), hipMemcpyDeviceToHost));
+    const int64_t n = offs[0][1] - offs[0][0], m = offs[1][1] - offs[1][0];
+    const size_t cells = (size_t)(n + 1) * (size_t)(m + 1);
+    int32_t idx[2] = {a, b};
+    HIPCHK(c, ensure(c->a, sizeof(int32_t) * 2));
+    HIPCHK(c, ensure(c->score, sizeof(int32_t) * 2));
+    if (traceback) {
+        HIPCHK(c, ensure(c->tb, cells));
+        HIPCHK(c, hipMemsetAsync(c->tb.p, 0, cells, c->stream));
+    }
+    HIPCHK(c, hipMemcpyAsync(c->a.p, idx, sizeof(idx), hipMemcpyHostToDevice, c->stream));
+    const int64_t amax = std::max(iabs64(match), iabs64(mismatch));
+    const int64_t M = std::max(amax, iabs64(indel));
+    const int64_t L = std::max<int32_t>(c->lmax, 1);
+    OvlDpArgs g{};
+    g.codes = as<uint8_t>(c->codes);
+    g.off = as<int64_t>(c->off);
+    g.len = as<int32_t>(c->len);
+    g.n_reads = c->n_reads;
+    g.a_idx = as<int32_t>(c->a);
+    g.b_idx = as<int32_t>(c->a) + 1;
+    g.n_pairs = 1;
+    g.mcap = (int32_t)std::max<int64_t>(m, 1);
+    g.match = match;
+    g.mismatch = mismatch;
+    g.indel = indel;
+    g.out_score = as<int32_t>(c->score);
+    g.out_end = as<int32_t>(c->score) + 1;
+    g.tb = traceback ? as<int8_t>(c->tb) : nullptr;
+    g.err_flag = as<uint32_t>(c->err_flag);
+    g.wide = !(indel > INT32_MIN && M < (int64_t(1) << 31) && (2 * L + 1) * M < (int64_t(1) << 31));
+    g.band = -1;
+    HIPCHK(c, ovl_launch_dp(&g, c->stream));
+    int32_t res[2];
+    HIPCHK(c, hipMemcpyAsync(res, c->score.p, sizeof(res), hipMemcpyDeviceToHost, c->stream));
+    if (traceback) HIPCHK(c, hipMemcpyAsync(traceback, c->tb.p, cells, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    *out_score = res[0];
+    *out_end = res[1];
+    return OVL_OK;
+}
+
+OVL_API int ovl_local_align(ovl_ctx* ctx, const uint8_t* query, int32_t n, const uint8_t* ref, int32_t m,
+                            int32_t match, int32_t mismatch, int64_t indel, int32_t* out_score, int32_t* out_end_i,
+                            int32_t* out_end_j, int32_t* out_start_i, int32_t* out_start_j, int8_t* ops,
+                            int64_t ops_cap, int64_t* out_n_ops) {
+    if (!ctx) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
+    quiet(ctx);
+    Dev* c = ctx->devs[0];
+    DeviceGuard guard;
+    if (n < 0 || m < 0) return fail(c, OVL_E_ARG, "negative length");
+    if ((n > 0 && !query) || (m > 0 && !ref)) return fail(c, OVL_E_ARG, "NULL sequence");
+    if (!out_score || !out_end_i || !out_end_j || !out_start_i || !out_start_j || !out_n_ops)
+        return fail(c, OVL_E_ARG, "NULL output pointer");
+    if (ops && ops_cap < 0) return fail(c, OVL_E_ARG, "ops_cap < 0");
+    // best-cell key: 24-bit score, 20-bit row and column
+    const int64_t mn = std::min(n, m);
+    const int64_t top = std::max<int64_t>(0, match) * mn;
+    if (n > 0xFFFFF || m > 0xFFFFF || top >= (int64_t(1) << 24))
+        return fail(c, OVL_E_UNSUPPORTED, "local alignment: lengths < 2^20 and match * min(n, m) < 2^24 required");
+    *out_score = 0; *out_end_i = 0; *out_end_j = 0; *out_start_i = 0; *out_start_j = 0; *out_n_ops = 0;
+    if (n == 0 || m == 0) return OVL_OK;
+    const int64_t M = std::max(std::max(iabs64(match), iabs64(mismatch)), iabs64(indel));
+    const int wide = (M >= (int64_t(1) << 30) || top + M >= (int64_t(1) << 31)) ? 1 : 0;
+    const int32_t n_strips = (n + 63) / 64;
+    const int64_t n_chunks = ((int64_t)m + 126) / 64;  // 64-step chunks covering tau = 0 .. m + 62
+    const int64_t steps = n_chunks * 64;                // traceback pitch per strip
+    const size_t tb_bytes = (size_t)n_strips * (size_t)steps * 64;
+    const size_t row_bytes = (size_t)n_strips * (size_t)(steps + 64) * sizeof(uint64_t);
+    if (ops && tb_bytes > (size_t(8) << 30))
+        return fail(c, OVL_E_UNSUPPORTED, "local alignment traceback table would exceed 8 GiB");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    HIPCHK(c, ensure(c->l_q, (size_t)n));
+    HIPCHK(c, ensure(c->l_r, (size_t)m));
+    if (c->l_row.bytes < row_bytes) {
+        // fresh words must not carry a live epoch: zero on (re)allocation, epochs start at 1
+        HIPCHK(c, ensure(c->l_row, row_bytes));
+        HIPCHK(c, hipMemsetAsync(c->l_row.p, 0, c->l_row.bytes, s));
+        c->l_epoch = 0;
+    }
+    if (++c->l_epoch == 0) {  // 2^32 launches: start over from zeroed words
+        HIPCHK(c, hipMemsetAsync(c->l_row.p, 0, c->l_row.bytes, s));
+        c->l_epoch = 1;
+    }
+    HIPCHK(c, ensure(c->l_best, 16));
+    if (ops) HIPCHK(c, ensure(c->l_tb, tb_bytes));
+    HIPCHK(c, hipMemcpyAsync(c->l_q.p, query, (size_t)n, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(c->l_r.p, ref, (size_t)m, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemsetAsync(c->l_best.p, 0, 16, s));
+    HIPCHK(c, hipMemsetAsync(c->err_flag.p, 0, sizeof(uint32_t), s));
+    // strips round-robin over at most 8 one-wavefront blocks per CU: far below residency, so every
+    // strip's producer is a resident wavefront (the hand-off polls would otherwise never end)
+    const int32_t blocks = std::min<int32_t>(n_strips, c->cu_count * 8);
+    HIPCHK(c, ovl_launch_local(as<uint8_t>(c->l_q), n, as<uint8_t>(c->l_r), m, match, mismatch, indel, wide,
+                               as<uint64_t>(c->l_row), ops ? as<int8_t>(c->l_tb) : nullptr,
+                               as<unsigned long long>(c->l_best), as<uint32_t>(c->err_flag), blocks, c->l_epoch, s));
+    unsigned long long key = 0;
+    uint32_t flag = 0;
+    HIPCHK(c, hipMemcpyAsync(&key, c->l_best.p, sizeof(key), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(&flag, c->err_flag.p, sizeof(flag), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (flag) {
+        HIPCHK(c, hipMemset(c->err_flag.p, 0, sizeof(uint32_t)));
+        return fail(c, OVL_E_HIP, "local alignment: a row hand-off timed out (flag %u)", flag);
+    }
+    int32_t bi = 0, bj = 0, score = 0;
+    if (key) {
+        score = (int32_t)(key >> 40);
+        bi = (int32_t)(0xFFFFFu - (uint32_t)((key >> 20) & 0xFFFFF));
+        bj = (int32_t)(0xFFFFFu - (uint32_t)(key & 0xFFFFF));
+    }
+    *out_score = score;
+    *out_end_i = bi;
+    *out_end_j = bj;
+    int32_t i = bi, j = bj;
+    int64_t k = 0;
+    if (ops && bi > 0 && bj > 0) {
+        // the walk moves up and left from (bi, bj): it reads strips 0 .. (bi-1)/64 and, in each,
+        // steps j + L - 1 <= bj + 62.  Only that corner of the table comes back, as one strided copy
+        // into a pinned buffer (the whole table is ~22 MB at contig x PhiX scale).
+        const size_t n_st = (size_t)((bi - 1) >> 6) + 1;
+        const size_t w = (size_t)(bj + 63) * 64;  // bytes of steps 0 .. bj + 62 in one strip
+        const size_t need = n_st * w;
+        if (c->l_tb_host_bytes < need) {
+            if (c->l_tb_host) (void)hipHostFree(c->l_tb_host);
+            c->l_tb_host = nullptr;
+            c->l_tb_host_bytes = 0;
+            HIPCHK(c, hipHostMalloc((void**)&c->l_tb_host, need, hipHostMallocDefault));
+            c->l_tb_host_bytes = need;
+        }
+        HIPCHK(c, hipMemcpy2DAsync(c->l_tb_host, w, c->l_tb.p, (size_t)steps * 64, w, n_st, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        const int8_t* tb = c->l_tb_host;
+        // aligners.py:133-153: walk while i > 0, j > 0 and dp[i][j] > 0
+        while (i > 0 && j > 0) {
+            const int32_t st = (i - 1) >> 6, L = (i - 1) & 63;
+            const int8_t code = tb[(size_t)st * w + (size_t)(j + L - 1) * 64 + (size_t)L];
+            if (!(code & 4)) break;
+            const int8_t op = code & 3;
+            if (op == 1) { --i; --j; }
+            else if (op == 2) { --i; }
+            else if (op == 3) { --j; }
+            else break;
+            if (k < ops_cap) ops[k] = op;
+            ++k;
+        }
+    }
+    *out_start_i = i;
+    *out_start_j = j;
+    *out_n_ops = k;
+    if (ops && k > ops_cap) return fail(c, OVL_E_RANGE, "ops_cap %lld < walk length %lld", (long long)ops_cap,
+                                        (long long)k);
+    return OVL_OK;
+}

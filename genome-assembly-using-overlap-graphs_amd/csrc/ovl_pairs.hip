@@ -3,7 +3,7 @@
 // A caller of the one-shot ABI (ovl_score_pairs / ovl_score_host) hands over int32 pair
 // arrays in host memory: 8 bytes per pair over the link before any scoring.  The candidate list of
 // overlapGraphs.py:43-52 is a-major (the outer loop walks read_copies), so `a` is runs of one value, and
-// indices below 65,535 fit 16 bits.  The host encodes each pipeline chunk (ovl_api.cpp encode_chunk) as
+// indices below 65,535 fit 16 bits.  The host encodes each pipeline chunk (ovl_pipeline.cpp encode_chunk) as
 //   b: uint16 (n_reads <= 65,535; 0xFFFF = an index outside [0, n_reads)) or int32,
 //   a: runs (value int32, chunk-relative start int32, starts[R] = chunk length) when they are few, else
 //      like b,

@@ -1,0 +1,427 @@
+// ovl_plan.cpp — kernel choice per call (ovl_plan: the ungapped popcount kernel whenever gaps provably cannot win
+// and the read store has a bit-plane layout, else a DP kernel) and the scoring launches (ovl_ctx.h).
+#include "ovl_ctx.h"
+
+namespace {
+
+// aligners.py:40: diag is taken whenever diag >= up and diag >= left.  Every dp
+// value is a sum of <= lmax diagonal terms when that always holds, so it does if
+// indel <= min(0, lmax*min(match,mismatch)) - max(0, lmax*max(match,mismatch)).
+bool gaps_cannot_win(int64_t match, int64_t mismatch, int64_t indel, int64_t lmax) {
+    const int64_t lo = std::min<int64_t>(0, lmax * std::min(match, mismatch));
+    const int64_t hi = std::max<int64_t>(0, lmax * std::max(match, mismatch));
+    return indel <= lo - hi;
+}
+
+int make_plan_full(const Dev* c, int32_t match, int32_t mismatch, int64_t indel, Plan* out);
+
+// band >= 0: the build's seed-and-extend knob (oracle_overlap_banded), exact
+// (== the reference) whenever gaps cannot win -- the seed cell (n, j*) is
+// always in the band and nothing off the ungapped diagonals can beat it -- and
+// whenever the band covers every diagonal (band >= 2 * lmax).
+int make_plan(const Dev* c, int32_t match, int32_t mismatch, int64_t indel, int32_t band, Plan* out) {
+    if (c->n_reads < 0) return fail(c, OVL_E_STATE, "no resident reads: call ovl_set_reads first");
+    const int64_t L = std::max<int32_t>(c->lmax, 1);
+    if (band < 0 || band >= 2 * L || gaps_cannot_win(match, mismatch, indel, L))
+        return make_plan_full(c, match, mismatch, indel, out);
+    // seed: the ungapped closed form (any kernel that evaluates it exactly)
+    Plan seed;
+    int rc = make_plan_full(c, match, mismatch, INT32_MIN, &seed);
+    if (rc != OVL_OK) return rc;
+    if (!gaps_cannot_win(match, mismatch, INT32_MIN, L))
+        return fail(c, OVL_E_UNSUPPORTED, "banded: the ungapped seed cannot be evaluated exactly at these scores");
+    Plan full;
+    rc = make_plan_full(c, match, mismatch, indel, &full);
+    if (rc != OVL_OK) return rc;
+    if (full.kernel != OVL_KERNEL_DP || full.wide)
+        return fail(c, OVL_E_UNSUPPORTED, "banded: scores too large for int32 cells (|score| * (2*lmax+1) >= 2^31)");
+    Plan p;
+    p.kernel = OVL_KERNEL_BANDED;
+    p.wide = false;
+    p.band = band;
+    p.seed_kernel = seed.kernel;
+    p.seed_key64 = seed.key64;
+    p.seed_wide = seed.wide;
+    *out = p;
+    return OVL_OK;
+}
+
+int make_plan_full(const Dev* c, int32_t match, int32_t mismatch, int64_t indel, Plan* out) {
+    const int64_t L = std::max<int32_t>(c->lmax, 1);
+    const int64_t amax = std::max(iabs64(match), iabs64(mismatch));
+    Plan p;
+    // ungapped closed form: exact when gaps cannot win and no int32 store can wrap
+    if (c->wmax > 0 && gaps_cannot_win(match, mismatch, indel, L) && amax * L < (int64_t(1) << 31)) {
+        p.kernel = OVL_KERNEL_UNGAPPED;
+        // 32-bit keys (score << 16) - j need |score| < 2^15 on both sides, and the
+        // folded form X * ((mismatch - match) << 16) + ... a 24-bit multiplier
+        const int64_t dms = (int64_t)mismatch - (int64_t)match;
+        // (the uniform sweep compares keys without their block constant: |score| + 32*amax
+        //  must stay below 2^15 as well)
+        p.key64 = !(amax * (2 * L + 32) < (1 << 15) && iabs64(dms) < 128 && iabs64(match) < 128);
+    } else {
+        if (c->lmax > kDpMaxLen)
+            return fail(c, OVL_E_UNSUPPORTED, "gapped DP supports reads up to %d bases (longest is %d)", kDpMaxLen,
+                        c->lmax);
+        p.kernel = OVL_KERNEL_DP;
+        const int64_t M = std::max(amax, iabs64(indel));
+        // |dp| <= 2*lmax*M; one more term for the candidates: int32 is exact below 2^31
+        p.wide = !(indel > INT32_MIN && M < (int64_t(1) << 31) && (2 * L + 1) * M < (int64_t(1) << 31));
+    }
+    *out = p;
+    return OVL_OK;
+}
+
+int launch_score_chunk(Dev* c, const Plan& pl, const int32_t* d_a, const int32_t* d_b, int64_t n_pairs,
+                       int32_t match, int32_t mismatch, int64_t indel, int32_t* d_score, int32_t* d_end,
+                       hipStream_t s);
+
+// Per-device scratch (lane_col, seed_*) is shared by every launch of the device.  A launch on stream s
+// first waits for the previous user on another stream; growing a buffer first waits for that user.
+struct ScratchNeed {
+    DevBuf* buf;
+    size_t bytes;
+};
+
+hipError_t scratch_acquire(Dev* c, hipStream_t s, std::initializer_list<ScratchNeed> needs) {
+    hipError_t e = hipSuccess;
+    for (const ScratchNeed& n : needs) {
+        if (n.buf->bytes >= n.bytes) continue;
+        if (c->scratch_used && (e = hipEventSynchronize(c->scratch_evt)) != hipSuccess) return e;
+        if ((e = ensure(*n.buf, n.bytes)) != hipSuccess) return e;
+    }
+    if (c->scratch_used && c->scratch_stream != s) e = hipStreamWaitEvent(s, c->scratch_evt, 0);
+    return e;
+}
+
+hipError_t scratch_release(Dev* c, hipStream_t s) {
+    hipError_t e = hipEventRecord(c->scratch_evt, s);
+    c->scratch_stream = s;
+    c->scratch_used = true;
+    return e;
+}
+
+// Lane-per-pair full DP (ovl_dp_lane.hip): one lane per pair, so it needs many pairs to fill the
+// chip (below that the one-wavefront-per-pair dp_fast_kernel is faster), reads short enough for
+// the per-wavefront hand-off columns, and G = dp - indel*(i+j) inside int32.
+bool use_dp_lane(const Dev* c, int64_t match, int64_t mismatch, int64_t indel, int64_t n_pairs) {
+    if (c->k.dp_lane == 0) return false;
+    const int64_t L = std::max<int32_t>(c->lmax, 1);
+    const int64_t M = std::max(std::max(iabs64(match), iabs64(mismatch)), iabs64(indel));
+    if (L > kLaneMaxLen || (4 * L + 4) * M >= (int64_t(1) << 30) || c->codes_bytes + 64 >= (int64_t(1) << 32))
+        return false;
+    return c->k.dp_lane == 1 || n_pairs >= kLaneMinPairs;
+}
+
+// rs_log2 of an ungapped launch over n pairs: bit shifts split over 1 << rs_log2 lanes (the general kernel),
+// or (uniform kernel, 2 planes) latency mode when rs_log2 > 0: up to kLatTiles tiles per CU for device lists,
+// up to kLatTilesIx for a host-encoded list (which only throughput mode reads in place)
+int32_t ungapped_rs_log2(const Dev* c, int64_t n_pairs, bool ix = false) {
+    int32_t rs_log2 = 0;
+    const int64_t want_waves = (int64_t)c->cu_count * 4 * 4;
+    while (rs_log2 < 2 && ((n_pairs << rs_log2) + 63) / 64 < want_waves) ++rs_log2;
+    if (c->planes == 2)
+        rs_log2 = ((n_pairs + 63) / 64 <= (int64_t)c->cu_count * (ix ? kLatTilesIx : kLatTiles)) ? 1 : 0;
+    return rs_log2;
+}
+
+}  // namespace
+
+// An ungapped launch over n pairs runs uniform_kernel in throughput mode, the one that can read a
+// host-encoded pair list in place (uniform_kernel IX)
+bool ix_launch(const Dev* c, int64_t n_pairs) {
+    return c->planes == 2 && c->lmax > 0 && c->wmax >= 1 && c->wmax <= 8 && ungapped_rs_log2(c, n_pairs, true) == 0;
+}
+
+// The candidate list's heavy tiles (flags per list tile on the device, ascending ids on host and device),
+// once per list; waits for the list's stream.
+int ensure_heavy(Dev* c) {
+    if (c->heavy_for == c->cand_n) return OVL_OK;
+    const int64_t n_tiles = (c->cand_n + 63) / 64;
+    HIPCHK(c, ensure(c->tile_flags, (size_t)std::max<int64_t>(n_tiles, 1)));
+    HIPCHK(c, ovl_launch_tile_flags(as<int32_t>(c->cand_a), c->cand_n, as<uint32_t>(c->full), c->n_reads,
+                                    as<uint8_t>(c->tile_flags), c->stream));
+    std::vector<uint8_t> f((size_t)n_tiles);
+    HIPCHK(c, hipMemcpyAsync(f.data(), c->tile_flags.p, (size_t)n_tiles, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->h_heavy.clear();
+    for (int64_t t = 0; t < n_tiles; ++t)
+        if (f[(size_t)t]) c->h_heavy.push_back((int32_t)t);
+    HIPCHK(c, ensure(c->heavy_ids, sizeof(int32_t) * std::max<size_t>(c->h_heavy.size(), 1)));
+    if (!c->h_heavy.empty())
+        HIPCHK(c, hipMemcpy(c->heavy_ids.p, c->h_heavy.data(), sizeof(int32_t) * c->h_heavy.size(),
+                            hipMemcpyHostToDevice));
+    c->heavy_for = c->cand_n;
+    return OVL_OK;
+}
+
+namespace {
+
+int launch_score_chunk(Dev* c, const Plan& pl, const int32_t* d_a, const int32_t* d_b, int64_t n_pairs,
+                       int32_t match, int32_t mismatch, int64_t indel, int32_t* d_score, int32_t* d_end,
+                       hipStream_t s) {
+    if (n_pairs == 0) return OVL_OK;
+    const int32_t* seed_end = nullptr;
+    if (pl.kernel == OVL_KERNEL_BANDED) {
+        // seed j* into device scratch (the outputs may be host memory), then the banded DP reads it
+        const size_t sb = sizeof(int32_t) * (size_t)n_pairs;
+        HIPCHK(c, scratch_acquire(c, s, {{&c->seed_s, sb}, {&c->seed_e, sb}}));
+        Plan seed;
+        seed.kernel = pl.seed_kernel;
+        seed.key64 = pl.seed_key64;
+        seed.wide = pl.seed_wide;
+        const int32_t out_mode = c->out_mode;
+        c->out_mode = 0;  // the seeds stay in HBM
+        int rc = launch_score_chunk(c, seed, d_a, d_b, n_pairs, match, mismatch, INT32_MIN, as<int32_t>(c->seed_s),
+                                    as<int32_t>(c->seed_e), s);
+        c->out_mode = out_mode;
+        if (rc != OVL_OK) return rc;
+        seed_end = as<int32_t>(c->seed_e);
+    }
+    if (c->ix_b16 && (pl.kernel != OVL_KERNEL_UNGAPPED || pl.key64 || !ix_launch(c, n_pairs)))
+        return fail(c, OVL_E_UNSUPPORTED, "host-encoded pair list on a launch that cannot read it");
+    if (pl.kernel == OVL_KERNEL_UNGAPPED) {
+        OvlUngappedArgs g{};
+        g.sfx = as<uint32_t>(c->sfx);
+        g.pfx = as<uint32_t>(c->pfx);
+        g.len = as<int32_t>(c->len);
+        g.n_reads = c->n_reads;
+        g.a_idx = d_a;
+        g.b_idx = d_b;
+        g.n_pairs = n_pairs;
+        // split a pair's 32 bit shifts over 1, 2 or 4 lanes until the grid has
+        // enough wavefronts to fill every SIMD a few times
+        // general kernel: split a pair's bit shifts over 1, 2 or 4 lanes until the grid
+        // has enough wavefronts.  Uniform kernel: latency mode (two wavefronts per tile,
+        // side pairs beside the sweep) when there is about one tile per wavefront slot.
+        g.rs_log2 = ungapped_rs_log2(c, n_pairs, c->ix_b16 != nullptr);
+        // uniform-length fast path (2 bit planes): pairs of two reads of length lmax;
+        // uniform_kernel scores the other pairs through its LDS side ring
+        g.lw = c->planes == 2 ? c->lmax : 0;
+        g.full = as<uint32_t>(c->full);
+        // (timing: this launch records the chunk's kernel events itself, once; issue_chunk checks they were taken)
+        g.ev_start = c->kev_start;
+        g.ev_stop = c->kev_stop;
+        g.match = match;
+        g.mismatch = mismatch;
+        g.out_score = d_score;
+        g.out_end = d_end;
+        g.err_flag = c->cur_flag;
+        g.planes = c->planes;
+        g.wmax = c->wmax;
+        g.key64 = pl.key64 ? 1 : 0;
+        g.max_blocks = (int64_t)c->cu_count * kBlocksPerCu;
+        g.host_out = c->out_mode;
+        g.ix_b16 = c->ix_b16;
+        g.ix_d8 = c->ix_d8;
+        g.ix_base = c->ix_base;
+        // a throughput-mode launch over (a 64-aligned part of) the resident candidate list: heavy tiles first
+        const int32_t* ca = as<int32_t>(c->cand_a);
+        if (!g.ix_b16 && g.lw > 0 && g.rs_log2 == 0 && c->cand_n > 0 && d_a >= ca &&
+            d_a < ca + c->cand_n && d_b == as<int32_t>(c->cand_b) + (d_a - ca) && (d_a - ca) % 64 == 0) {
+            int rc = ensure_heavy(c);
+            if (rc != OVL_OK) return rc;
+            const int64_t t0 = (d_a - ca) / 64, t1 = t0 + (n_pairs + 63) / 64;
+            const auto k0 = std::lower_bound(c->h_heavy.begin(), c->h_heavy.end(), t0);
+            const auto k1 = std::lower_bound(c->h_heavy.begin(), c->h_heavy.end(), t1);
+            if (k1 > k0) {
+                g.heavy_ids = as<int32_t>(c->heavy_ids) + (k0 - c->h_heavy.begin());
+                g.heavy_n = (int32_t)(k1 - k0);
+                g.tile_flags = as<uint8_t>(c->tile_flags);
+                g.tile_base = t0;
+            }
+        }
+        HIPCHK(c, ovl_launch_ungapped(&g, s));
+        if (g.ev_start && g.lw > 0) c->kev_start = c->kev_stop = nullptr;  // (uniform_kernel recorded them)
+    } else {
+        OvlDpArgs g{};
+        g.codes = as<uint8_t>(c->codes);
+        g.off = as<int64_t>(c->off);
+        g.len = as<int32_t>(c->len);
+        g.n_reads = c->n_reads;
+        g.a_idx = d_a;
+        g.b_idx = d_b;
+        g.n_pairs = n_pairs;
+        g.mcap = std::max<int32_t>(c->lmax, 1);
+        g.match = match;
+        g.mismatch = mismatch;
+        g.indel = indel;
+        g.out_score = d_score;
+        g.out_end = d_end;
+        g.tb = nullptr;
+        g.err_flag = c->cur_flag;
+        g.wide = pl.wide ? 1 : 0;
+        g.band = pl.kernel == OVL_KERNEL_BANDED ? pl.band : -1;
+        g.seed = seed_end;
+        g.classic = c->k.dp_classic;
+        if (g.band < 0 && !g.wide && !g.classic && use_dp_lane(c, match, mismatch, indel, n_pairs)) {
+            OvlLaneArgs k{};
+            k.cw = 32;
+            k.slots = (int64_t)c->cu_count * 4 * ovl_dp_lane_waves_per_simd(k.cw);
+            const int64_t L = std::max<int32_t>(c->lmax, 1);
+            const int64_t M = std::max(std::max(iabs64(match), iabs64(mismatch)), iabs64(indel));
+            const int64_t sma = (int64_t)match - 2 * indel, smm = (int64_t)mismatch - 2 * indel;
+            k.prof = c->k.lane_prof && c->planes == 2 && indel <= 0 && sma >= -128 && sma <= 127 && smm >= -128 &&
+                     smm <= 127;
+            k.ho = (4 * L + 4) * M < (int64_t(1) << 15) ? 1 : 0;
+            k.sfx = k.prof && c->k.lane_sfx && c->wmax > 0;
+            // column steps G[i][j] - G[i-1][j] lie in [0, max(match, mismatch) - 2*indel]: 4 bits in LDS
+            const int64_t step_max = std::max<int64_t>(match, mismatch) - 2 * indel;
+            if (k.sfx && indel <= 0 && std::max<int64_t>(match, mismatch) >= indel &&
+                step_max <= 15 && g.mcap <= 256)
+                k.ho = 2;
+            k.h2 = k.ho == 2 && c->k.lane_h2 && ovl_dp_lane_h2_ok(match, mismatch, indel);
+            // hand-off columns in HBM: one per resident slot (HO 0 / 1), per tile for the h2 form's HBM variant --
+            // which launches at most kH2Slice pairs at a time over one reused column buffer (lcap / 2 bytes per
+            // pair: 1 GiB at 256-base reads), and falls back to the int32 form (HO 2: no HBM column) when even that
+            // cannot be allocated
+            constexpr int64_t kH2Slice = int64_t(1) << 23;
+            const int64_t slice = k.h2 ? std::min(n_pairs, kH2Slice) : n_pairs;
+            size_t col_bytes =
+                k.h2 ? (size_t)ovl_dp_lane_h2_col_bytes(slice, g.mcap)
+                     : (k.ho == 2 ? 0 : (size_t)k.slots * ovl_dp_lane_rcap(g.mcap) * 64 * sizeof(uint32_t));
+            hipError_t se = scratch_acquire(c, s, {{&c->lane_col, col_bytes}});
+            if (se == hipErrorOutOfMemory && k.h2) {
+                (void)hipGetLastError();
+                k.h2 = 0;
+                col_bytes = 0;
+                se = scratch_acquire(c, s, {{&c->lane_col, col_bytes}});
+            }
+            HIPCHK(c, se);
+            k.sfx_words = as<uint32_t>(c->sfx);
+            k.pfx_words = as<uint32_t>(c->pfx);
+            k.srow = c->srow;
+            k.wsfx = c->wmax;
+            k.colbuf = as<uint32_t>(c->lane_col);
+            for (int64_t lo = 0; lo < n_pairs; lo += slice) {
+                OvlDpArgs gs = g;
+                gs.a_idx = d_a + lo;
+                gs.b_idx = d_b + lo;
+                gs.out_score = d_score + lo;
+                gs.out_end = d_end + lo;
+                gs.n_pairs = std::min(slice, n_pairs - lo);
+                HIPCHK(c, ovl_launch_dp_lane(&gs, &k, s));
+            }
+            HIPCHK(c, scratch_release(c, s));
+            return OVL_OK;
+        }
+        if (g.band >= 0) {
+            // "-inf" (kBandNeg) must stay below every value: |values| <= (2*lmax + 1) * M and the row
+            // form's scan adds up to 2*band*|indel|
+            const int64_t Mx = std::max(std::max(iabs64(match), iabs64(mismatch)), iabs64(indel));
+            const int64_t L = std::max<int32_t>(c->lmax, 1);
+            const bool neg_ok = (4 * L + 2) * Mx < (int64_t(1) << 29);
+            const int64_t lanes = 2 * (int64_t)g.band + 1;
+            const bool diag_ok = neg_ok && ovl_band_diag_slots(g.band, c->lmax, nullptr) > 0;
+            const bool rows_ok = neg_ok && lanes <= 192 && c->lmax <= 1024;
+            // lane per pair: byte scores (match/mismatch - 2*indel, -2*indel, -indel in int8), indel <= 0,
+            // <= 4 symbols, G = dp - indel*(i+j) in int32 with j down to -(2*lmax + band)
+            const int64_t sma = (int64_t)match - 2 * indel, smm = (int64_t)mismatch - 2 * indel;
+            auto i8 = [](int64_t v) { return v >= -128 && v <= 127; };
+            const bool lane_ok = c->planes == 2 && ovl_band_lane_ok(g.band) && indel <= 0 && i8(sma) &&
+                                 i8(smm) && i8(-2 * indel) && (6 * L + 2 * g.band + 8) * Mx < (int64_t(1) << 30) &&
+                                 c->lmax <= kLaneMaxLen && c->codes_bytes + 64 < (int64_t(1) << 32);
+            switch (c->k.band_form) {
+                case OVL_BAND_FORM_ROWS: g.band_form = rows_ok ? OVL_BAND_FORM_ROWS : OVL_BAND_FORM_STRIP; break;
+                case OVL_BAND_FORM_FAST: g.band_form = OVL_BAND_FORM_FAST; break;
+                case OVL_BAND_FORM_STRIP: g.band_form = OVL_BAND_FORM_STRIP; break;
+                case OVL_BAND_FORM_DIAG: g.band_form = diag_ok ? OVL_BAND_FORM_DIAG : OVL_BAND_FORM_FAST; break;
+                case OVL_BAND_FORM_LANE:
+                case OVL_BAND_FORM_LANE1:
+                case OVL_BAND_FORM_LANE2:
+                    g.band_form = lane_ok ? OVL_BAND_FORM_LANE : (diag_ok ? OVL_BAND_FORM_DIAG : OVL_BAND_FORM_FAST);
+                    break;
+                default:
+                    g.band_form = (lane_ok && n_pairs >= kLaneMinPairs)
+                                      ? OVL_BAND_FORM_LANE
+                                      : (diag_ok ? OVL_BAND_FORM_DIAG : OVL_BAND_FORM_FAST);
+                    break;
+            }
+            if (g.band_form == OVL_BAND_FORM_LANE) {
+                OvlLaneArgs k{};
+                k.sfx = c->k.lane_sfx && c->wmax > 0;
+                k.sfx_words = as<uint32_t>(c->sfx);
+                k.pfx_words = as<uint32_t>(c->pfx);
+                k.srow = c->srow;
+                k.wsfx = c->wmax;
+                k.split = c->k.band_form == OVL_BAND_FORM_LANE2 ||
+                          (c->k.band_form != OVL_BAND_FORM_LANE1 && g.band >= kBandLane2Min);
+                HIPCHK(c, ovl_launch_band_lane(&g, &k, s));
+                HIPCHK(c, scratch_release(c, s));
+                return OVL_OK;
+            }
+        }
+        HIPCHK(c, ovl_launch_dp(&g, s));
+        if (seed_end) HIPCHK(c, scratch_release(c, s));
+    }
+    return OVL_OK;
+}
+
+}  // namespace
+
+// Kernels queue pair indices as int32 (LDS side ring); split huge lists.
+int launch_score(Dev* c, const Plan& pl, const int32_t* d_a, const int32_t* d_b, int64_t n_pairs,
+                 int32_t match, int32_t mismatch, int64_t indel, int32_t* d_score, int32_t* d_end,
+                 hipStream_t s) {
+    constexpr int64_t kChunk = int64_t(1) << 30;
+    for (int64_t lo = 0; lo < n_pairs; lo += kChunk) {
+        const int64_t n = std::min(kChunk, n_pairs - lo);
+        int rc = launch_score_chunk(c, pl, d_a + lo, d_b + lo, n, match, mismatch, indel, d_score + lo, d_end + lo, s);
+        if (rc != OVL_OK) return rc;
+    }
+    return OVL_OK;
+}
+
+int check_scoring_args(ovl_ctx* c, int32_t match, int32_t mismatch, int64_t indel, int32_t band, Plan* p) {
+    // every device holds the same read set, so device 0 plans for all
+    return make_plan(c->devs[0], match, mismatch, indel, band, p);
+}
+
+OVL_API int ovl_plan(const ovl_ctx* c, int32_t match, int32_t mismatch, int64_t indel, int32_t band,
+                     int32_t* out_kernel) {
+    if (!c) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
+    if (!out_kernel) return fail(c, OVL_E_ARG, "out_kernel is NULL");
+    Plan p;
+    int rc = make_plan(c->devs[0], match, mismatch, indel, band, &p);
+    if (rc != OVL_OK) return rc;
+    *out_kernel = p.kernel;
+    return OVL_OK;
+}
+
+// ----------------------------------------------------------------------------- scoring
+
+OVL_API int ovl_score_device(ovl_ctx* c, const int32_t* d_a, const int32_t* d_b, int64_t n_pairs, int32_t match,
+                             int32_t mismatch, int64_t indel, int32_t band, int32_t* d_score, int32_t* d_end,
+                             void* stream) {
+    if (!c) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
+    quiet(c);
+    if (n_pairs < 0) return fail(c, OVL_E_ARG, "n_pairs < 0");
+    if (n_pairs > 0 && (!d_a || !d_b || !d_score || !d_end)) return fail(c, OVL_E_ARG, "NULL device pointer");
+    Dev* d = c->devs[0];
+    Plan p;
+    int rc = make_plan(d, match, mismatch, indel, band, &p);
+    if (rc != OVL_OK) return rc;
+    if (n_pairs > 0 && d->n_reads == 0) return fail(c, OVL_E_INDEX, "pairs given but the read set is empty");
+    DeviceGuard guard;
+    HIPCHK(c, hipSetDevice(d->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);  // NULL = the default (null) stream
+    return launch_score(d, p, d_a, d_b, n_pairs, match, mismatch, indel, d_score, d_end, s);
+}
+
+OVL_API int ovl_check_device_errors(ovl_ctx* c) {
+    if (!c) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
+    quiet(c);
+    DeviceGuard guard;
+    int rc = OVL_OK;
+    for (Dev* d : c->devs) {
+        HIPCHK(c, hipSetDevice(d->device));
+        HIPCHK(c, hipDeviceSynchronize());
+        uint32_t flag = 0;
+        HIPCHK(c, hipMemcpy(&flag, d->err_flag.p, sizeof(flag), hipMemcpyDeviceToHost));
+        if (flag) {
+            HIPCHK(c, hipMemset(d->err_flag.p, 0, sizeof(uint32_t)));
+            rc = fail(c, OVL_E_INDEX, "a device scoring call saw a pair index outside [0, n_reads)");
+        }
+    }
+    return rc;
+}

@@ -1,6 +1,8 @@
 // ovl_pool.h — the host side's CPU share detection (CpuShare) and worker pool (CopyPool): host copies,
-// expansion of packed results, pair-list encoding and read preparation split over threads (ovl_api.cpp).
-// Host code only; tools/pool_probe.cpp times the pool's per-batch cost on its own.
+// expansion of packed results, pair-list encoding and read preparation split over threads (ovl_pipeline.cpp,
+// ovl_reads.cpp).  Host code only; tools/pool_probe.cpp times the pool's per-batch cost on its own.  The classes
+// live in a named namespace, not an anonymous one: every file of libovl that includes this header must share the
+// one CpuShare slot and the one CopyPool of the process (their statics are then one per shared object).
 #pragma once
 
 #include <immintrin.h>
@@ -26,7 +28,7 @@
 #include <thread>
 #include <vector>
 
-namespace {
+namespace ovl_host {
 
 // Processes that share this process's CPUs and drive libovl (the reference's joblib workers, experiments.py:537
 // n_jobs=-1, or torch.distributed ranks).  Each such process holds one abstract unix socket bound to
@@ -137,12 +139,12 @@ class CpuShare {
 // profiles/r02_pool_threads_*.json.  Round 5, one process, per-rank steps at N = 1 / 2 / 4 / 8 of the target list:
 // 12 threads 0.138 / 0.089 / 0.060 / 0.045 ms against 15 threads 0.150 / 0.095 / 0.065 / 0.050, same box; streamed
 // records (OVL_PACK=2) preferred 15 by 1-7 %, profiles/r05_pool_threads_ab.json.)
-int pool_rule(int cpus, int sharers, int env_threads) {
+inline int pool_rule(int cpus, int sharers, int env_threads) {
     if (env_threads > 0) return std::min(64, env_threads);
     return std::max(1, std::min(12, cpus / std::max(1, sharers) - 1));
 }
 
-int env_pool_threads() {
+inline int env_pool_threads() {
     for (const char* k : {"OVL_POOL_THREADS", "OVL_HOST_THREADS"})
         if (const char* e = getenv(k)) return std::max(0, atoi(e));
     return 0;
@@ -334,4 +336,8 @@ class CopyPool {
     std::condition_variable cv_, done_;
 };
 
-}  // namespace
+}  // namespace ovl_host
+
+using ovl_host::CopyPool;
+using ovl_host::CpuShare;
+using ovl_host::pool_rule;

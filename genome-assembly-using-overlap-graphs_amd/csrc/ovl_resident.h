@@ -1,7 +1,7 @@
 // ovl_resident.h — host side of the resident scoring grid (ovl_kernels.hip resident_kernel): one per device of a
 // context, launched on the first eligible call and left running, so a call posts a request into pinned memory and
 // expands the ring records as they land -- no launch, no completion event.  Host code only,
-// included by ovl_api.cpp.
+// included through ovl_ctx.h.
 //
 // Protocol (ovl_kernels.h OvlResidentCtl / OvlResidentBody):
 //  * the host writes body[seq & 1], then ctl = seq (release); the grid's block 0 polls ctl and forwards the request;
@@ -35,7 +35,7 @@
 #include "ovl_grid.h"
 #include "ovl_pool.h"
 
-namespace {
+namespace ovl_host {  // (named: the grid registry, ResidentGrid::reg, is one per process)
 
 // What a grid is launched over: the resident read set and the candidate list's heavy-tile flags, fixed for its life
 // (a call over anything else stops it and launches a new one).
@@ -579,4 +579,8 @@ class ResidentGrid {
     }
 };
 
-}  // namespace
+}  // namespace ovl_host
+
+using ovl_host::ResidentCall;
+using ovl_host::ResidentGrid;
+using ovl_host::ResidentReads;

@@ -1,4 +1,4 @@
-// ovl_scan.h — host pass over a read set's bytes (ovl_api.cpp stage_reads): the alphabet, and the 2-bit
+// ovl_scan.h — host pass over a read set's bytes (ovl_reads.cpp stage_reads): the alphabet, and the 2-bit
 // packing of ACGT-only bytes that ovl_set_reads uploads instead of the bytes (unpack2_kernel expands it on the
 // device).  Host code only (tests/c/scan_test.cpp checks the vector form against the scalar one).
 #pragma once

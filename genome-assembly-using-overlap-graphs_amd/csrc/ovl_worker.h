@@ -1,4 +1,4 @@
-// ovl_worker.h -- a host thread per device of a multi-device context (ovl_api.cpp run_pipeline), bound to the CPUs
+// ovl_worker.h -- a host thread per device of a multi-device context (ovl_pipeline.cpp run_pipeline), bound to the CPUs
 // of its GPU's NUMA node.  Host code only.
 #pragma once
 

@@ -112,8 +112,8 @@ def _share_torch_hip_runtime() -> None:
 def load():
     """Load and type libovl.so; raises OvlError if it is absent.
 
-    OVL_LIB_PATH may point at another build of the same library (diagnostic
-    ablation builds under build/ablate_*); it is never a CPU implementation.
+    OVL_LIB_PATH may point at another build of the same library (the diagnostic
+    trace build, build/trace/libovl.so); it is never a CPU implementation.
     """
     global _lib
     with _lock:

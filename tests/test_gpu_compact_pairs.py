@@ -1,4 +1,4 @@
-"""GPU: host pair lists in compact form (ovl_pairs.hip, ovl_api.cpp encode_chunk).
+"""GPU: host pair lists in compact form (ovl_pairs.hip, ovl_pipeline.cpp encode_chunk).
 
 ovl_score_host / ovl_score_pairs encode the caller's int32 pairs per pipeline chunk -- b as uint16 when
 n_reads <= 65,535; a, when the list is a-major (overlapGraphs.py:43-52), as tile deltas that uniform_kernel

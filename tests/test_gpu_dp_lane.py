@@ -187,7 +187,7 @@ def test_lane_flags_bad_index(mixed_set):
 
 def test_h2_full_dp_across_launch_slices(oracle_mod):
     """The packed-f16 full DP (dp_lane_h2_kernel) launches at most 2^23 pairs at a time over one reused hand-off
-    column buffer (ovl_api.cpp launch_score_chunk, kH2Slice): a device list of 2^24 + 4,099 pairs (cfg2's list
+    column buffer (ovl_plan.cpp launch_score_chunk, kH2Slice): a device list of 2^24 + 4,099 pairs (cfg2's list
     repeated) scores in three slices with each slice's results where they belong -- checked against the oracle on a
     strided sample and on every pair around the slice boundaries -- and the device memory the call leaves allocated
     stays near one slice's column buffer (64 B per pair at 100-base reads: 0.54 GB), not the list's (1.07 GB)."""

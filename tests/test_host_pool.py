@@ -2,6 +2,7 @@
 drive libovl on one CPU set -- the reference's joblib workers (experiments.py:481-539, n_jobs=-1)."""
 import multiprocessing as mp
 import os
+import subprocess
 
 from ovlgraph import _lib
 from ovlgraph.engine import host_pool
@@ -17,6 +18,18 @@ def test_rule():
     assert rule(8, 1, 0) == 7
     assert rule(16, 4, 5) == 5            # OVL_POOL_THREADS wins
     assert rule(1, 1, 0) == 1
+
+
+def test_process_wide_singletons_are_single():
+    """Several host files of libovl include ovl_pool.h and ovl_resident.h: the pool, the CPU-share slot and the
+    resident grids' registry must still be one per process -- one symbol each in the library, not one per file
+    (which is what an anonymous namespace in those headers would give)."""
+    _lib.load()
+    out = subprocess.run(["nm", "-C", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    names = [f[2] for f in (line.split(None, 2) for line in out.splitlines()) if len(f) == 3]
+    for tail in ("CopyPool::pool_", "CpuShare::get()::one", "ResidentGrid::reg()::v"):
+        hits = [n for n in names if n.endswith(tail) and not n.startswith("guard variable")]
+        assert len(hits) == 1, (tail, hits)
 
 
 def _worker(barrier, q):
