@@ -129,6 +129,8 @@ struct Knobs {
     int32_t resident_pf = 1;      // its tiles software-pipelined (fewer, fatter wavefronts) or one at a time
     int32_t resident_sleep = 4;   // its non-lead blocks' pause between polls (~0.1 us units)
     int32_t resident_ring = 0;    // its ring's memory (ResidentGrid::ring_kind)
+    int32_t local_batch_waves = 0; // OVL_LOCAL_BATCH_WAVES: cap on the wavefronts of ovl_local_align_batch's
+                                  // kernel (0: none; tests reach slab reuse with a handful of queries)
     int32_t pack_direct_pct = 18; // OVL_PACK_DIRECT_PCT: packed calls into pinned arrays store this share of the
                                   // pairs (the last chunk) as int32 straight into them, over the link while the
                                   // host expands the packed chunks (tools/pack_ab.py, target point, six
@@ -158,6 +160,14 @@ constexpr int64_t kCompactMin = int64_t(1) << 16;
 // 250 K-pair shard 22.7 -> 9.4 us, the N = 4 step 0.085 -> 0.075 ms; tools/pool_probe.cpp,
 // profiles/r04_pool_ab_*.json)
 constexpr size_t kExpandPart = size_t(1) << 14;
+// ovl_local_align_batch: a query stays on the batch kernel (one wavefront per query) up to this many 64-row
+// strips and this large a traceback table of its own; all slabs of a launch together stay inside the budget,
+// which caps the wavefront count; the carried row lives in LDS up to this many int32
+constexpr int32_t kBatchMaxStrips = 16;
+constexpr size_t kBatchSlabMax = size_t(64) << 20;
+constexpr size_t kBatchSlabBudget = size_t(4) << 30;
+constexpr int64_t kBatchLdsRow = 8192;
+constexpr int32_t kBatchWavesPerCu = 8;
 
 struct ovl_ctx;
 
@@ -207,6 +217,10 @@ struct Dev {
     // pinned host copy of the part of the traceback table the walk can reach (grown on demand)
     int8_t* l_tb_host = nullptr;
     size_t l_tb_host_bytes = 0;
+    // batched local alignment (ovl_local_align_batch): the upload block (items, query bytes, reference), the two
+    // counters, per-wavefront rows / traceback slabs / op scratch, and the results (8 int32 per query, packed ops)
+    DevBuf lb_in, lb_ctr, lb_rows, lb_slabs, lb_wops, lb_out, lb_ops;
+    hipEvent_t lb_ev[2] = {};  // timing on: around the batch kernel
     // host-array pipeline: events per slot and pinned staging (slots x cap pairs x {a, b} / {score, end})
     hipEvent_t ev_k[kSlots] = {};
     int32_t* st_in = nullptr;
@@ -285,6 +299,7 @@ struct ovl_ctx {
     int64_t x_link_bytes = 0, x_packed_pairs = 0;  // ovl_last_transfer
     int64_t x_res_bytes = 0, x_rec_pairs = 0, x_esc = 0;  // ovl_last_results
     int64_t x_ix_pairs = 0, x_dec_pairs = 0;       // ovl_last_pair_list
+    int32_t x_lb_batched = 0, x_lb_single = 0, x_lb_waves = 0;  // ovl_last_local_batch
 };
 
 int fail(const ovl_ctx* c, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));

@@ -153,6 +153,37 @@ extern "C" hipError_t ovl_launch_local(const uint8_t* q, int32_t n, const uint8_
                                        unsigned long long* best, uint32_t* err_flag, int32_t blocks, uint32_t epoch,
                                        hipStream_t stream);
 
+// batched local alignment (ovl_local_batch.hip): `waves` one-wavefront blocks take items[0 .. n_items) from
+// *counter (zeroed by the caller).  Item k aligns q[q_off .. q_off + n) to ref[win_lo .. win_lo + m), n, m >= 1,
+// in int32 cells.  Per wavefront w: rows + w * row_pitch (int32; row_pitch 0: the row lives in the launch's
+// lds_row_bytes of dynamic LDS), and with a traceback slabs + w * slab_pitch (bytes, >= the largest item's
+// n_strips x 64 * n_chunks x 64) and wave_ops + w * wave_ops_pitch (>= the largest n + m).  out: 8 int32 per
+// item at out[8 * item.out]: score, end_i, end_j, start_i, start_j, n_ops, and the 64-bit position of its ops
+// in `ops` (reserved from *ops_total, zeroed by the caller).  slabs == NULL: score only (starts = ends, no ops).
+struct OvlLocalBatchItem {
+    int64_t q_off;
+    int32_t n, win_lo, m, out;
+};
+struct OvlLocalBatchArgs {
+    const uint8_t* q;
+    const uint8_t* ref;
+    const OvlLocalBatchItem* items;
+    int32_t n_items;
+    int32_t match, mismatch, indel;
+    uint32_t* counter;
+    unsigned long long* ops_total;
+    int32_t* rows;
+    int64_t row_pitch;
+    int8_t* slabs;
+    int64_t slab_pitch;
+    int8_t* wave_ops;
+    int64_t wave_ops_pitch;
+    int32_t* out;
+    int8_t* ops;
+};
+extern "C" hipError_t ovl_launch_local_batch(const OvlLocalBatchArgs* a, int32_t waves, uint32_t lds_row_bytes,
+                                             hipStream_t stream);
+
 // shard bounds of a pair list balanced by len[a]*len[b] + 1 (ovl_candidates.hip): ovl_shard_scan writes
 // the inclusive prefix sum of the costs (n_pairs int64), ovl_shard_cut the shards + 1 cuts of [lo, hi)
 extern "C" hipError_t ovl_shard_temp_bytes(int64_t n_pairs, size_t* bytes);

@@ -172,3 +172,194 @@ OVL_API int ovl_local_align(ovl_ctx* ctx, const uint8_t* query, int32_t n, const
                                         (long long)k);
     return OVL_OK;
 }
+
+// Many queries against windows of one reference in one call (ovl_local_batch.hip): every query that fits one
+// wavefront goes through one launch of the batch kernel; the rest (long, wide-scoring or with a traceback table
+// beyond kBatchSlabMax) go through ovl_local_align afterwards.
+OVL_API int ovl_local_align_batch(ovl_ctx* ctx, const uint8_t* queries, const int64_t* q_off, int32_t n_queries,
+                                  const uint8_t* reference, int32_t ref_len, const int32_t* win_lo,
+                                  const int32_t* win_len, int32_t match, int32_t mismatch, int64_t indel,
+                                  int32_t* out_score, int32_t* out_end_i, int32_t* out_end_j, int32_t* out_start_i,
+                                  int32_t* out_start_j, int8_t* ops, const int64_t* ops_off, int64_t* out_n_ops) {
+    if (!ctx) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
+    quiet(ctx);
+    Dev* c = ctx->devs[0];
+    DeviceGuard guard;
+    const auto t_call = std::chrono::steady_clock::now();
+    if (n_queries < 0 || ref_len < 0) return fail(c, OVL_E_ARG, "negative count or length");
+    if (n_queries > 0 && !q_off) return fail(c, OVL_E_ARG, "q_off is NULL");
+    if ((win_lo == nullptr) != (win_len == nullptr))
+        return fail(c, OVL_E_ARG, "win_lo and win_len must both be given or both be NULL");
+    if (n_queries > 0 && (!out_score || !out_end_i || !out_end_j || !out_start_i || !out_start_j || !out_n_ops))
+        return fail(c, OVL_E_ARG, "NULL output pointer");
+    if (ops && !ops_off) return fail(c, OVL_E_ARG, "ops without ops_off");
+    // every argument check comes before anything is written or run
+    const int64_t pos_match = std::max<int64_t>(0, match);
+    for (int32_t k = 0; k < n_queries; ++k) {
+        const int64_t n = q_off[k + 1] - q_off[k];
+        if (q_off[k] < 0 || n < 0) return fail(c, OVL_E_ARG, "query %d: bad offsets", k);
+        const int64_t lo = win_lo ? win_lo[k] : 0, m = win_lo ? win_len[k] : ref_len;
+        if (lo < 0 || m < 0 || lo + m > ref_len)
+            return fail(c, OVL_E_ARG, "query %d: window [%lld, %lld) outside the reference of %d", k, (long long)lo,
+                        (long long)(lo + m), ref_len);
+        if ((n > 0 && !queries) || (m > 0 && !reference)) return fail(c, OVL_E_ARG, "NULL sequence");
+        if (ops && ops_off[k + 1] - ops_off[k] < n + m)
+            return fail(c, OVL_E_ARG, "query %d: ops slot of %lld < n + m = %lld", k,
+                        (long long)(ops_off[k + 1] - ops_off[k]), (long long)(n + m));
+    }
+    for (int32_t k = 0; k < n_queries; ++k) {
+        const int64_t n = q_off[k + 1] - q_off[k], m = win_lo ? win_len[k] : ref_len;
+        if (n > 0xFFFFF || m > 0xFFFFF || pos_match * std::min(n, m) >= (int64_t(1) << 24))
+            return fail(c, OVL_E_UNSUPPORTED,
+                        "local alignment, query %d: lengths < 2^20 and match * min(n, m) < 2^24 required", k);
+    }
+    ctx->x_lb_batched = ctx->x_lb_single = ctx->x_lb_waves = 0;
+    ctx->t_kernel_ms = ctx->t_call_ms = 0.0;
+    // route the queries
+    const int64_t M = std::max(std::max(iabs64(match), iabs64(mismatch)), iabs64(indel));
+    struct Q {
+        int32_t k, n, lo, m;
+        int64_t cost;
+    };
+    std::vector<Q> batch;
+    std::vector<int32_t> single;
+    size_t slab_max = 0;
+    int64_t row_max = 0, nm_max = 0, nm_sum = 0, q_bytes = 0;
+    for (int32_t k = 0; k < n_queries; ++k) {
+        out_score[k] = 0; out_end_i[k] = 0; out_end_j[k] = 0; out_start_i[k] = 0; out_start_j[k] = 0;
+        out_n_ops[k] = 0;
+        const int64_t n = q_off[k + 1] - q_off[k], m = win_lo ? win_len[k] : ref_len;
+        if (n == 0 || m == 0) continue;
+        const int64_t top = pos_match * std::min(n, m);
+        const bool wide = M >= (int64_t(1) << 30) || top + M >= (int64_t(1) << 31);
+        const int64_t n_strips = (n + 63) / 64, steps = ((m + 126) / 64) * 64;
+        const size_t table = (size_t)n_strips * (size_t)steps * 64;
+        if (wide || n_strips > kBatchMaxStrips || (ops && table > kBatchSlabMax)) {
+            single.push_back(k);
+            continue;
+        }
+        batch.push_back({k, (int32_t)n, win_lo ? win_lo[k] : 0, (int32_t)m, n * m});
+        slab_max = std::max(slab_max, table);
+        row_max = std::max(row_max, steps);
+        nm_max = std::max(nm_max, n + m);
+        nm_sum += n + m;
+        q_bytes += n;
+    }
+    if (!batch.empty()) {
+        // long queries first: the wavefronts that take the short ones last even the launch's tail out
+        std::stable_sort(batch.begin(), batch.end(), [](const Q& x, const Q& y) { return x.cost > y.cost; });
+        const int32_t nb = (int32_t)batch.size();
+        const size_t slab_pitch = (slab_max + 255) & ~size_t(255);
+        int64_t waves = std::min<int64_t>(nb, (int64_t)c->cu_count * kBatchWavesPerCu);
+        if (ops) waves = std::min<int64_t>(waves, std::max<int64_t>(1, (int64_t)(kBatchSlabBudget / slab_pitch)));
+        if (c->k.local_batch_waves > 0) waves = std::min<int64_t>(waves, c->k.local_batch_waves);
+        const bool row_lds = row_max <= kBatchLdsRow;
+        const int64_t wops_pitch = (nm_max + 63) & ~int64_t(63);
+        // one upload block: the items, the batched queries' bytes, the reference
+        const size_t o_q = sizeof(OvlLocalBatchItem) * (size_t)nb, o_r = o_q + (size_t)q_bytes;
+        std::vector<char> blob(o_r + (size_t)ref_len);
+        OvlLocalBatchItem* items = reinterpret_cast<OvlLocalBatchItem*>(blob.data());
+        int64_t qo = 0;
+        for (int32_t b = 0; b < nb; ++b) {
+            const Q& x = batch[b];
+            items[b] = {qo, x.n, x.lo, x.m, b};
+            memcpy(blob.data() + o_q + qo, queries + q_off[x.k], (size_t)x.n);
+            qo += x.n;
+        }
+        memcpy(blob.data() + o_r, reference, (size_t)ref_len);
+        HIPCHK(c, hipSetDevice(c->device));
+        hipStream_t s = c->stream;
+        HIPCHK(c, ensure(c->lb_in, blob.size()));
+        HIPCHK(c, ensure(c->lb_ctr, 16));
+        HIPCHK(c, ensure(c->lb_out, sizeof(int32_t) * 8 * (size_t)nb));
+        if (!row_lds) HIPCHK(c, ensure(c->lb_rows, sizeof(int32_t) * (size_t)row_max * (size_t)waves));
+        if (ops) {
+            HIPCHK(c, ensure(c->lb_slabs, slab_pitch * (size_t)waves));
+            HIPCHK(c, ensure(c->lb_wops, (size_t)wops_pitch * (size_t)waves));
+            HIPCHK(c, ensure(c->lb_ops, (size_t)nm_sum));
+        }
+        HIPCHK(c, hipMemcpyAsync(c->lb_in.p, blob.data(), blob.size(), hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipMemsetAsync(c->lb_ctr.p, 0, 16, s));
+        OvlLocalBatchArgs a{};
+        a.items = as<OvlLocalBatchItem>(c->lb_in);
+        a.q = as<uint8_t>(c->lb_in) + o_q;
+        a.ref = as<uint8_t>(c->lb_in) + o_r;
+        a.n_items = nb;
+        a.match = match;
+        a.mismatch = mismatch;
+        a.indel = (int32_t)indel;  // |indel| < 2^30 here: wider scorings went to `single`
+        a.counter = as<uint32_t>(c->lb_ctr);
+        a.ops_total = reinterpret_cast<unsigned long long*>(as<char>(c->lb_ctr) + 8);
+        a.rows = row_lds ? nullptr : as<int32_t>(c->lb_rows);
+        a.row_pitch = row_lds ? 0 : row_max;
+        a.slabs = ops ? as<int8_t>(c->lb_slabs) : nullptr;
+        a.slab_pitch = (int64_t)slab_pitch;
+        a.wave_ops = ops ? as<int8_t>(c->lb_wops) : nullptr;
+        a.wave_ops_pitch = wops_pitch;
+        a.out = as<int32_t>(c->lb_out);
+        a.ops = ops ? as<int8_t>(c->lb_ops) : nullptr;
+        if (ctx->timing) {
+            for (hipEvent_t& e : c->lb_ev)
+                if (!e) HIPCHK(c, hipEventCreate(&e));
+            HIPCHK(c, hipEventRecord(c->lb_ev[0], s));
+        }
+        HIPCHK(c, ovl_launch_local_batch(&a, (int32_t)waves, row_lds ? (uint32_t)(row_max * 4) : 0u, s));
+        if (ctx->timing) HIPCHK(c, hipEventRecord(c->lb_ev[1], s));
+        std::vector<int32_t> res((size_t)nb * 8);
+        unsigned long long ctr[2] = {0, 0};
+        HIPCHK(c, hipMemcpyAsync(res.data(), c->lb_out.p, res.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(ctr, c->lb_ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        if (ctx->timing) {
+            float ms = 0.f;
+            HIPCHK(c, hipEventElapsedTime(&ms, c->lb_ev[0], c->lb_ev[1]));
+            ctx->t_kernel_ms = ms;
+        }
+        const unsigned long long total = ctr[1];
+        if (total > (unsigned long long)nm_sum)
+            return fail(c, OVL_E_INTERNAL, "batched local alignment: %llu ops for a capacity of %lld", total,
+                        (long long)nm_sum);
+        std::vector<int8_t> packed((size_t)total);
+        if (total) {
+            HIPCHK(c, hipMemcpyAsync(packed.data(), c->lb_ops.p, (size_t)total, hipMemcpyDeviceToHost, s));
+            HIPCHK(c, hipStreamSynchronize(s));
+        }
+        for (int32_t b = 0; b < nb; ++b) {
+            const int32_t k = batch[b].k;
+            const int32_t* o = res.data() + (size_t)b * 8;
+            out_score[k] = o[0]; out_end_i[k] = o[1]; out_end_j[k] = o[2];
+            out_start_i[k] = ops ? o[3] : o[1];
+            out_start_j[k] = ops ? o[4] : o[2];
+            if (ops && o[5] > 0) {
+                const unsigned long long base = (unsigned long long)(uint32_t)o[6] |
+                                                ((unsigned long long)(uint32_t)o[7] << 32);
+                if (base + (unsigned long long)o[5] > total || o[5] > batch[b].n + batch[b].m)
+                    return fail(c, OVL_E_INTERNAL, "batched local alignment: query %d's ops lie outside the buffer", k);
+                memcpy(ops + ops_off[k], packed.data() + base, (size_t)o[5]);
+                out_n_ops[k] = o[5];
+            }
+        }
+        ctx->x_lb_batched = nb;
+        ctx->x_lb_waves = (int32_t)waves;
+    }
+    for (int32_t k : single) {
+        const int32_t n = (int32_t)(q_off[k + 1] - q_off[k]);
+        const int32_t lo = win_lo ? win_lo[k] : 0, m = win_lo ? win_len[k] : ref_len;
+        const int rc = ovl_local_align(ctx, queries + q_off[k], n, reference + lo, m, match, mismatch, indel,
+                                       out_score + k, out_end_i + k, out_end_j + k, out_start_i + k, out_start_j + k,
+                                       ops ? ops + ops_off[k] : nullptr, ops ? ops_off[k + 1] - ops_off[k] : 0,
+                                       out_n_ops + k);
+        if (rc != OVL_OK) return rc;
+    }
+    ctx->x_lb_single = (int32_t)single.size();
+    ctx->t_call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+    return OVL_OK;
+}
+
+OVL_API int ovl_last_local_batch(const ovl_ctx* ctx, int32_t* batched, int32_t* single, int32_t* waves) {
+    if (!ctx) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
+    if (batched) *batched = ctx->x_lb_batched;
+    if (single) *single = ctx->x_lb_single;
+    if (waves) *waves = ctx->x_lb_waves;
+    return OVL_OK;
+}

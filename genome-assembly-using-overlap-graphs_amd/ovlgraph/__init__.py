@@ -3,9 +3,11 @@ roiteichman/Genome-Assembly-Using-Overlap-Graphs (aligners.py / overlapGraphs.py
 
     from ovlgraph.overlapGraphs import construct_overlap_graph_nx_k
     from ovlgraph.aligners import overlap_alignment
+    from ovlgraph.performanceMeasures import calculate_measures
 
 Candidate pairs are enumerated on the host (Python), every pair is scored by
-hand-written gfx950 HIP kernels behind the C ABI of include/ovl.h.
+hand-written gfx950 HIP kernels behind the C ABI of include/ovl.h; the evaluation
+stage aligns all contigs of an assembly to the genome in one batched launch.
 """
 from ._lib import OvlError  # noqa: F401
 from .engine import INDEL_DEFAULT, OverlapEngine, default_engine, encode_reads, score_reads  # noqa: F401

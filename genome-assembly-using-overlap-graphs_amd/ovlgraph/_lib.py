@@ -16,7 +16,7 @@ PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(PKG_ROOT, "build", "libovl.so")
 CSRC = os.path.join(PKG_ROOT, "csrc")
 
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 OVL_OK = 0
 ERRORS = {
@@ -71,6 +71,9 @@ SIGNATURES = {
     "ovl_resident_stats": (ctypes.c_int, [_P, _pi32, _pi64, _pi64, _pi32]),
     "ovl_local_align": (ctypes.c_int, [_P, _P, _i32, _P, _i32, _i32, _i32, _i64, _pi32, _pi32, _pi32, _pi32,
                                        _pi32, _P, _i64, _pi64]),
+    "ovl_local_align_batch": (ctypes.c_int, [_P, _P, _P, _i32, _P, _i32, _P, _P, _i32, _i32, _i64, _P, _P, _P, _P,
+                                             _P, _P, _P, _P]),
+    "ovl_last_local_batch": (ctypes.c_int, [_P, _pi32, _pi32, _pi32]),
     "ovl_remove_cycles": (ctypes.c_int, [_P, _P, _P, _i32, _P, _pi64]),
     "ovl_remove_cycles_stream": (ctypes.c_int, [_P, _P, _P, _i32, _P, _pi64, _P, _P, _P]),
 }

@@ -102,3 +102,35 @@ def align_read_or_contig_to_reference(read_or_contig, reference_genome, read_len
         tp, a_r, a_q, sc, st, en = local_alignment(read_or_contig, tail, match_score, mismatch, indel, engine)
         return tp, a_r, a_q, sc, len(reference_genome) - L + st, len(reference_genome) - L + en
     return local_alignment(read_or_contig, reference_genome, match_score, mismatch, indel, engine)
+
+
+def align_to_reference_batch(items, reference_genome, read_length, match_score=10, mismatch=-1, indel=-1,
+                             engine: OverlapEngine = None):
+    """``align_read_or_contig_to_reference`` for every item in one GPU call: a list whose element ``i``
+    equals ``align_read_or_contig_to_reference(items[i], reference_genome, read_length, ...)``.
+
+    An item with ``0 < len < read_length`` is aligned to the window ``(G - len, len)`` of the reference,
+    every other item to the whole reference (an empty one too: ``reference_genome[-0:]``, aligners.py:189);
+    items shorter than ``read_length`` have their positions shifted back by ``G - len``.
+    """
+    items = list(items)
+    G = len(reference_genome)
+    windows, shifts = [], []
+    for it in items:
+        L = len(it)
+        short = L < read_length
+        tail = short and 0 < L <= G  # reference_genome[-L:] with L > G is the whole reference as well
+        windows.append((G - L, L) if tail else (0, G))
+        shifts.append(G - L if short else 0)
+    eng = engine or default_engine()
+    with _lock:
+        sc, bi, bj, si, sj, ops = eng.local_align_batch(items, reference_genome, windows, int(match_score),
+                                                        int(mismatch), int(indel))
+    out = []
+    for k, it in enumerate(items):
+        lo, ln = windows[k]
+        ref = reference_genome[lo:lo + ln] if (lo, ln) != (0, G) else reference_genome
+        a_r, a_q = _local_strings(it, ref, int(bi[k]), int(bj[k]), ops[k].tolist())
+        to_print = f"\nTarget:   {a_r}\n          {'|' * len(a_r)}\nQuery:    {a_q}"
+        out.append((to_print, a_r, a_q, int(sc[k]), shifts[k] + int(sj[k]), shifts[k] + int(bj[k])))
+    return out

@@ -338,6 +338,56 @@ class OverlapEngine:
         sc, ei, ej, si, sj = (o.value for o in outs)
         return sc, ei, ej, si, sj, (ops[: k.value] if traceback else None)
 
+    def local_align_batch(self, queries: Sequence[str], reference: str, windows=None, match: int = 10,
+                          mismatch: int = -1, indel: int = -1, traceback: bool = True):
+        """``local_align`` of every query against ``reference`` in one call (ovl_local_align_batch).
+
+        ``windows`` (optional): one ``(lo, length)`` per query, the slice of the reference it is aligned
+        to; positions are relative to that slice.  Returns ``(score, end_i, end_j, start_i, start_j, ops)``:
+        five int32 arrays and a list of per-query op arrays (walk order; ``None`` without traceback).
+        """
+        queries = list(queries)
+        nq = len(queries)
+        buf, offs = encode_reads(queries + [reference])
+        G = len(reference)
+        q_off = np.ascontiguousarray(offs[: nq + 1])
+        ref = np.ascontiguousarray(buf[int(offs[nq]): int(offs[nq]) + G]) if G else np.zeros(1, np.uint8)
+        if windows is None:
+            lo = ln = None
+            m = np.full(nq, G, dtype=np.int64)
+        else:
+            w = np.asarray(list(windows), dtype=np.int64).reshape(-1, 2)
+            if w.shape[0] != nq:
+                raise OvlError(-1, "windows must hold one (lo, length) per query")
+            if w.size and (w.min() < -2 ** 31 or w.max() >= 2 ** 31):
+                raise OvlError(-1, "window outside the int32 range")
+            lo = np.ascontiguousarray(w[:, 0], dtype=np.int32)
+            ln = np.ascontiguousarray(w[:, 1], dtype=np.int32)
+            m = w[:, 1]
+        outs = [np.zeros(max(nq, 1), dtype=np.int32) for _ in range(5)]
+        n_ops = np.zeros(max(nq, 1), dtype=np.int64)
+        ops = ops_off = None
+        if traceback:
+            ops_off = np.zeros(nq + 1, dtype=np.int64)
+            np.cumsum(np.diff(q_off) + np.maximum(m, 0), out=ops_off[1:])
+            ops = np.zeros(max(int(ops_off[-1]), 1), dtype=np.int8)
+        check(self._L.ovl_local_align_batch(
+            self._ctx, _ptr(buf), _ptr(q_off), nq, _ptr(ref), G, _ptr(lo) if lo is not None else None,
+            _ptr(ln) if ln is not None else None, int(match), int(mismatch), int(indel),
+            *[_ptr(o) for o in outs], _ptr(ops) if traceback else None, _ptr(ops_off) if traceback else None,
+            _ptr(n_ops)), self._ctx)
+        walks = None
+        if traceback:
+            walks = [ops[int(ops_off[k]): int(ops_off[k]) + int(n_ops[k])] for k in range(nq)]
+        return tuple(o[:nq] for o in outs) + (walks,)
+
+    def last_local_batch(self) -> Dict[str, int]:
+        """{batched, single, waves} of the last ``local_align_batch`` (ovl_last_local_batch): the queries that took
+        the batch kernel, those that took the single-pair path, and the batch kernel's wavefronts."""
+        v = [ctypes.c_int32() for _ in range(3)]
+        check(self._L.ovl_last_local_batch(self._ctx, *[ctypes.byref(x) for x in v]), self._ctx)
+        return dict(zip(("batched", "single", "waves"), (x.value for x in v)))
+
     # ---------------------------------------------------------------- scoring
     def score_pairs(self, reads: Sequence[str], a_idx, b_idx, match: int = 10, mismatch: int = -1,
                     indel: int = INDEL_DEFAULT, band: int = -1, out=None,

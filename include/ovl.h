@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define OVL_ABI_VERSION 3
+#define OVL_ABI_VERSION 4
 
 enum {
     OVL_OK = 0,
@@ -251,6 +251,29 @@ int ovl_local_align(ovl_ctx* ctx, const uint8_t* query, int32_t n, const uint8_t
                     int32_t match, int32_t mismatch, int64_t indel, int32_t* out_score, int32_t* out_end_i,
                     int32_t* out_end_j, int32_t* out_start_i, int32_t* out_start_j, int8_t* ops,
                     int64_t ops_cap, int64_t* out_n_ops);
+/*
+ * ovl_local_align for many queries against one reference in one call (the evaluation stage's shape:
+ * every contig of an assembly against the genome).  Query k is queries[q_off[k] .. q_off[k+1]) and is
+ * aligned to reference[win_lo[k] .. win_lo[k] + win_len[k]) (win_lo and win_len both NULL: the whole
+ * reference for every query); its results, at index k of the output arrays, are what ovl_local_align
+ * returns for that query and that slice, positions relative to the window.  ops == NULL: scores only
+ * (starts equal ends, out_n_ops[k] = 0); otherwise query k's walk goes to ops[ops_off[k] ..), and
+ * ops_off[k+1] - ops_off[k] must be at least n_k + m_k (OVL_E_ARG otherwise).  Every argument is checked
+ * before anything runs or is written: OVL_E_ARG for null or negative arguments and windows outside the
+ * reference, OVL_E_UNSUPPORTED (naming the query) for ovl_local_align's per-query limits.  Empty queries
+ * and empty windows give zeros.  Queries that fit one wavefront (up to 16 strips of 64 rows, int32 cells,
+ * a traceback table up to 64 MiB) run in one launch of a kernel that gives each query to one wavefront;
+ * the others run one by one as ovl_local_align does.  Runs on the context's first device.
+ * ovl_last_local_batch: how many of the last call's queries took the batch kernel, how many the
+ * single-pair path, and the wavefronts the batch kernel was launched with (at most
+ * OVL_LOCAL_BATCH_WAVES when that is set at context creation).
+ */
+int ovl_local_align_batch(ovl_ctx* ctx, const uint8_t* queries, const int64_t* q_off, int32_t n_queries,
+                          const uint8_t* reference, int32_t ref_len, const int32_t* win_lo,
+                          const int32_t* win_len, int32_t match, int32_t mismatch, int64_t indel,
+                          int32_t* out_score, int32_t* out_end_i, int32_t* out_end_j, int32_t* out_start_i,
+                          int32_t* out_start_j, int8_t* ops, const int64_t* ops_off, int64_t* out_n_ops);
+int ovl_last_local_batch(const ovl_ctx* ctx, int32_t* batched, int32_t* single, int32_t* waves);
 
 /* Cycle removal of overlapGraphs.py:106-130 (remove_cycles_from_graph), host-side, no context.
  * Replaces:  while True: cycle = nx.find_cycle(G, orientation='original') ... G.remove_edge(u, v)
