@@ -112,6 +112,7 @@ Knobs read_knobs() {
         else if (!strcmp(e, "decode")) k.pairs_ix = 0;
     }
     if (const char* e = getenv("OVL_LOCAL_BATCH_WAVES")) k.local_batch_waves = std::max(0, atoi(e));
+    if (const char* e = getenv("OVL_TR_WINDOW")) k.tr_window = std::max(0, atoi(e));
     if (const char* e = getenv("OVL_PIPE_CHUNK")) {
         const long long v = atoll(e);
         if (v >= 64) k.pipe_chunk = v;
@@ -131,10 +132,13 @@ void destroy_dev(Dev* d) {
                       &d->k_order, &d->k_lo, &d->k_hi, &d->k_cnt, &d->k_offs, &d->k_temp, &d->cand_a, &d->cand_b,
                       &d->sh_cum, &d->sh_temp, &d->sh_cuts, &d->l_q, &d->l_r, &d->l_row, &d->l_tb, &d->l_best,
                       &d->lane_col, &d->seed_s, &d->seed_e, &d->tile_flags, &d->heavy_ids, &d->cp_hbm, &d->lb_in,
-                      &d->lb_ctr, &d->lb_rows, &d->lb_slabs, &d->lb_wops, &d->lb_out, &d->lb_ops})
+                      &d->lb_ctr, &d->lb_rows, &d->lb_slabs, &d->lb_wops, &d->lb_out, &d->lb_ops, &d->tr_off,
+                      &d->tr_edge, &d->tr_order, &d->tr_ctr, &d->tr_out})
         release(*b);
     if (d->l_tb_host) (void)hipHostFree(d->l_tb_host);
     for (hipEvent_t e : d->lb_ev)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : d->tr_ev)
         if (e) (void)hipEventDestroy(e);
     free_staging(d->st_in);
     free_staging(d->st_out);

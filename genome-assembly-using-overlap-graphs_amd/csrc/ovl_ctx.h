@@ -131,6 +131,8 @@ struct Knobs {
     int32_t resident_ring = 0;    // its ring's memory (ResidentGrid::ring_kind)
     int32_t local_batch_waves = 0; // OVL_LOCAL_BATCH_WAVES: cap on the wavefronts of ovl_local_align_batch's
                                   // kernel (0: none; tests reach slab reuse with a handful of queries)
+    int32_t tr_window = 0;        // OVL_TR_WINDOW: entries of a node's out-row held in LDS per pass of
+                                  // ovl_transitive_reduce (0: kReduceWindow; tests force several passes)
     int32_t pack_direct_pct = 18; // OVL_PACK_DIRECT_PCT: packed calls into pinned arrays store this share of the
                                   // pairs (the last chunk) as int32 straight into them, over the link while the
                                   // host expands the packed chunks (tools/pack_ab.py, target point, six
@@ -221,6 +223,9 @@ struct Dev {
     // counters, per-wavefront rows / traceback slabs / op scratch, and the results (8 int32 per query, packed ops)
     DevBuf lb_in, lb_ctr, lb_rows, lb_slabs, lb_wops, lb_out, lb_ops;
     hipEvent_t lb_ev[2] = {};  // timing on: around the batch kernel
+    // transitive reduction (ovl_reduce_api.cpp): the CSR, the node order, the counter and the mask
+    DevBuf tr_off, tr_edge, tr_order, tr_ctr, tr_out;
+    hipEvent_t tr_ev[2] = {};  // timing on: around the reduction kernel
     // host-array pipeline: events per slot and pinned staging (slots x cap pairs x {a, b} / {score, end})
     hipEvent_t ev_k[kSlots] = {};
     int32_t* st_in = nullptr;
@@ -300,6 +305,8 @@ struct ovl_ctx {
     int64_t x_res_bytes = 0, x_rec_pairs = 0, x_esc = 0;  // ovl_last_results
     int64_t x_ix_pairs = 0, x_dec_pairs = 0;       // ovl_last_pair_list
     int32_t x_lb_batched = 0, x_lb_single = 0, x_lb_waves = 0;  // ovl_last_local_batch
+    int32_t x_tr_window = 0, x_tr_passes = 0;                   // ovl_last_transitive
+    int64_t x_tr_steps = 0;
 };
 
 int fail(const ovl_ctx* c, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));

@@ -184,6 +184,25 @@ struct OvlLocalBatchArgs {
 extern "C" hipError_t ovl_launch_local_batch(const OvlLocalBatchArgs* a, int32_t waves, uint32_t lds_row_bytes,
                                              hipStream_t stream);
 
+// transitive reduction of an overlap graph (ovl_reduce.hip): `blocks` persistent workgroups of kReduceThreads take
+// order[0 .. n_order) -- the nodes with out-edges, heaviest first by two-hop work -- from *counter (zeroed by the
+// caller).  edge[e] = {head, weight} of CSR edge e (heads validated in [0, n_nodes), |weight| < 2^30); a window of
+// `window` entries of the current node's out-row lives in the launch's 4 * window bytes of dynamic LDS; `group`
+// (a power of two, 8 .. 64) lanes share one successor's list, kReduceLoads entries per lane and trip.
+// reduced[e] is written for every edge.
+constexpr int kReduceThreads = 512;
+constexpr int kReduceLoads = 4;  // entries of a successor list a lane loads per trip, all in flight before the first is used
+struct OvlReduceArgs {
+    const int64_t* off;
+    const int2* edge;
+    const int32_t* order;
+    int32_t n_nodes, n_order;
+    int32_t window, group;
+    uint32_t* counter;
+    uint8_t* reduced;
+};
+extern "C" hipError_t ovl_launch_reduce(const OvlReduceArgs* a, int32_t blocks, hipStream_t stream);
+
 // shard bounds of a pair list balanced by len[a]*len[b] + 1 (ovl_candidates.hip): ovl_shard_scan writes
 // the inclusive prefix sum of the costs (n_pairs int64), ovl_shard_cut the shards + 1 cuts of [lo, hi)
 extern "C" hipError_t ovl_shard_temp_bytes(int64_t n_pairs, size_t* bytes);

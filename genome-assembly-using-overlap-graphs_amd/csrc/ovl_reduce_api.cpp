@@ -1,0 +1,165 @@
+// ovl_reduce_api.cpp — transitive reduction of an overlap graph (overlapGraphs.py:235-303): the argument checks,
+// the host form (ovl_transitive_reduce_host) and the device call (ovl_transitive_reduce, ovl_reduce.hip).
+#include "ovl_ctx.h"
+
+namespace {
+
+constexpr int32_t kReduceWindow = 20224;   // out-row entries in LDS per pass (79 KiB: two workgroups per CU)
+constexpr int32_t kReduceBlocksPerCu = 2;
+constexpr int64_t kReduceWeightLimit = int64_t(1) << 30;  // the device forms int32 sums of two weights
+
+// Every check of both entry points, before anything is launched or written.  `work` and `steps`, when given (both
+// or neither), receive each node's two-hop work sum over w in succ(v) of deg(w) and their total.
+template <typename C>
+int check_graph(const C* c, const int64_t* off, const int32_t* head, const int64_t* weight, int32_t n_nodes,
+                const uint8_t* reduced, const int64_t* n_reduced, std::vector<int64_t>* work, int64_t* steps) {
+    if (n_nodes < 0) return fail(c, OVL_E_ARG, "negative node count");
+    if (!off || !n_reduced) return fail(c, OVL_E_ARG, "NULL off or n_reduced");
+    if (off[0] != 0) return fail(c, OVL_E_ARG, "off[0] = %lld, not 0", (long long)off[0]);
+    for (int32_t v = 0; v < n_nodes; ++v)
+        if (off[v + 1] < off[v]) return fail(c, OVL_E_ARG, "off decreases at node %d", v);
+    const int64_t n_edges = off[n_nodes];
+    if (n_edges > 0 && (!head || !weight || !reduced)) return fail(c, OVL_E_ARG, "NULL head, weight or reduced");
+    for (int64_t e = 0; e < n_edges; ++e)
+        if (head[e] < 0 || head[e] >= n_nodes)
+            return fail(c, OVL_E_INDEX, "edge %lld: head %d outside [0, %d)", (long long)e, head[e], n_nodes);
+    for (int64_t e = 0; e < n_edges; ++e)
+        if (weight[e] >= kReduceWeightLimit || weight[e] <= -kReduceWeightLimit)
+            return fail(c, OVL_E_RANGE, "edge %lld: |weight| = |%lld| >= 2^30", (long long)e, (long long)weight[e]);
+    if (!work) return OVL_OK;  // the host form needs no step counts
+    int64_t total = 0;
+    work->assign((size_t)n_nodes, 0);
+    for (int32_t v = 0; v < n_nodes; ++v) {
+        int64_t w = 0;
+        for (int64_t e = off[v]; e < off[v + 1]; ++e) w += off[head[e] + 1] - off[head[e]];
+        (*work)[(size_t)v] = w;
+        total += w;
+    }
+    *steps = total;
+    return OVL_OK;
+}
+
+// A mark array per source node, reset by re-walking the node's successors.
+void reduce_host(const int64_t* off, const int32_t* head, const int64_t* weight, int32_t n_nodes, uint8_t* reduced,
+                 int64_t* n_reduced) {
+    std::vector<int64_t> row((size_t)n_nodes, 0);
+    std::vector<uint8_t> mark((size_t)n_nodes, 0);  // 0 no edge (v, x), 1 edge, 2 eliminated
+    int64_t count = 0;
+    for (int32_t v = 0; v < n_nodes; ++v) {
+        const int64_t e0 = off[v], e1 = off[v + 1];
+        for (int64_t e = e0; e < e1; ++e) {
+            row[(size_t)head[e]] = weight[e];
+            mark[(size_t)head[e]] = 1;
+        }
+        for (int64_t e = e0; e < e1; ++e) {
+            const int32_t w = head[e];
+            const int64_t vw = weight[e];
+            for (int64_t f = off[w]; f < off[w + 1]; ++f) {
+                const size_t x = (size_t)head[f];
+                if (mark[x] == 1 && vw + weight[f] >= row[x]) mark[x] = 2;
+            }
+        }
+        for (int64_t e = e0; e < e1; ++e) {
+            const size_t x = (size_t)head[e];
+            reduced[e] = mark[x] == 2;
+            count += mark[x] == 2;
+            mark[x] = 0;
+        }
+    }
+    *n_reduced = count;
+}
+
+}  // namespace
+
+OVL_API int ovl_transitive_reduce_host(const int64_t* off, const int32_t* head, const int64_t* weight,
+                                       int32_t n_nodes, uint8_t* reduced, int64_t* n_reduced) {
+    const int rc = check_graph((const ovl_ctx*)nullptr, off, head, weight, n_nodes, reduced, n_reduced, nullptr,
+                               nullptr);
+    if (rc != OVL_OK) return rc;
+    reduce_host(off, head, weight, n_nodes, reduced, n_reduced);
+    return OVL_OK;
+}
+
+OVL_API int ovl_transitive_reduce(ovl_ctx* ctx, const int64_t* off, const int32_t* head, const int64_t* weight,
+                                  int32_t n_nodes, uint8_t* reduced, int64_t* n_reduced) {
+    if (!ctx) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
+    quiet(ctx);
+    Dev* c = ctx->devs[0];
+    DeviceGuard guard;
+    const auto t_call = std::chrono::steady_clock::now();
+    std::vector<int64_t> work;
+    int64_t steps = 0;
+    const int rc = check_graph(c, off, head, weight, n_nodes, reduced, n_reduced, &work, &steps);
+    if (rc != OVL_OK) return rc;
+    const int64_t n_edges = n_nodes > 0 ? off[n_nodes] : 0;
+    const int32_t window = std::min(kReduceWindow, c->k.tr_window > 0 ? c->k.tr_window : kReduceWindow);
+    ctx->x_tr_window = window;
+    ctx->x_tr_passes = (int32_t)(((int64_t)n_nodes + window - 1) / window);
+    ctx->x_tr_steps = steps;
+    ctx->t_kernel_ms = ctx->t_call_ms = 0.0;
+    *n_reduced = 0;
+    if (n_edges == 0) return OVL_OK;
+    // nodes with out-edges, heaviest first (ties in node order)
+    std::vector<int32_t> order;
+    order.reserve((size_t)n_nodes);
+    for (int32_t v = 0; v < n_nodes; ++v)
+        if (off[v + 1] > off[v]) order.push_back(v);
+    std::stable_sort(order.begin(), order.end(),
+                     [&](int32_t x, int32_t y) { return work[(size_t)x] > work[(size_t)y]; });
+    std::vector<int2> edge((size_t)n_edges);
+    for (int64_t e = 0; e < n_edges; ++e) edge[(size_t)e] = make_int2(head[e], (int32_t)weight[e]);
+    // lanes per successor list: the power of two in [8, 64] that covers the mean list walked in one trip
+    const int64_t mean = steps / n_edges;
+    int32_t group = 8;
+    while (group < 64 && group * kReduceLoads < mean) group *= 2;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    HIPCHK(c, ensure(c->tr_off, sizeof(int64_t) * ((size_t)n_nodes + 1)));
+    HIPCHK(c, ensure(c->tr_edge, sizeof(int2) * (size_t)n_edges));
+    HIPCHK(c, ensure(c->tr_order, sizeof(int32_t) * order.size()));
+    HIPCHK(c, ensure(c->tr_ctr, 16));
+    HIPCHK(c, ensure(c->tr_out, (size_t)n_edges));
+    HIPCHK(c, hipMemcpyAsync(c->tr_off.p, off, sizeof(int64_t) * ((size_t)n_nodes + 1), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(c->tr_edge.p, edge.data(), sizeof(int2) * (size_t)n_edges, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(c->tr_order.p, order.data(), sizeof(int32_t) * order.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemsetAsync(c->tr_ctr.p, 0, 16, s));
+    HIPCHK(c, hipMemsetAsync(c->tr_out.p, 0, (size_t)n_edges, s));
+    OvlReduceArgs a{};
+    a.off = as<int64_t>(c->tr_off);
+    a.edge = as<int2>(c->tr_edge);
+    a.order = as<int32_t>(c->tr_order);
+    a.n_nodes = n_nodes;
+    a.n_order = (int32_t)order.size();
+    a.window = window;
+    a.group = group;
+    a.counter = as<uint32_t>(c->tr_ctr);
+    a.reduced = as<uint8_t>(c->tr_out);
+    const int32_t blocks = (int32_t)std::min<int64_t>((int64_t)order.size(), (int64_t)c->cu_count * kReduceBlocksPerCu);
+    if (ctx->timing) {
+        for (hipEvent_t& e : c->tr_ev)
+            if (!e) HIPCHK(c, hipEventCreate(&e));
+        HIPCHK(c, hipEventRecord(c->tr_ev[0], s));
+    }
+    HIPCHK(c, ovl_launch_reduce(&a, blocks, s));
+    if (ctx->timing) HIPCHK(c, hipEventRecord(c->tr_ev[1], s));
+    HIPCHK(c, hipMemcpyAsync(reduced, c->tr_out.p, (size_t)n_edges, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (ctx->timing) {
+        float ms = 0.f;
+        HIPCHK(c, hipEventElapsedTime(&ms, c->tr_ev[0], c->tr_ev[1]));
+        ctx->t_kernel_ms = ms;
+    }
+    int64_t count = 0;
+    for (int64_t e = 0; e < n_edges; ++e) count += reduced[e];
+    *n_reduced = count;
+    ctx->t_call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+    return OVL_OK;
+}
+
+OVL_API int ovl_last_transitive(const ovl_ctx* ctx, int32_t* window_nodes, int32_t* passes, int64_t* two_hop_steps) {
+    if (!ctx) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
+    if (window_nodes) *window_nodes = ctx->x_tr_window;
+    if (passes) *passes = ctx->x_tr_passes;
+    if (two_hop_steps) *two_hop_steps = ctx->x_tr_steps;
+    return OVL_OK;
+}

@@ -80,6 +80,29 @@ def _outputs(n: int, out) -> Tuple[np.ndarray, np.ndarray]:
     return sc[:n], en[:n]
 
 
+def _csr_arrays(off, heads, weights) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """A CSR graph as the contiguous (int64 off, int32 heads, int64 weights) the C ABI takes."""
+    off = np.ascontiguousarray(off, dtype=np.int64)
+    heads = np.ascontiguousarray(heads, dtype=np.int32)
+    weights = np.ascontiguousarray(weights, dtype=np.int64)
+    if off.ndim != 1 or off.shape[0] < 1 or heads.ndim != 1 or heads.shape != weights.shape:
+        raise OvlError(-1, "CSR graph: off needs n_nodes + 1 entries, heads and weights one entry per edge")
+    if int(off[-1]) > heads.shape[0]:
+        raise OvlError(-1, f"CSR graph: off[-1] = {int(off[-1])} exceeds the {heads.shape[0]} edges given")
+    return off, heads, weights
+
+
+def transitive_reduce_host(off, heads, weights) -> np.ndarray:
+    """``OverlapEngine.transitive_reduce`` by the library's host loop (ovl_transitive_reduce_host): no context,
+    no GPU."""
+    off, heads, weights = _csr_arrays(off, heads, weights)
+    reduced = np.zeros(max(heads.shape[0], 1), dtype=np.uint8)
+    n_reduced = ctypes.c_int64(0)
+    check(_lib.load().ovl_transitive_reduce_host(_ptr(off), _ptr(heads), _ptr(weights), off.shape[0] - 1,
+                                                 _ptr(reduced), ctypes.byref(n_reduced)))
+    return reduced[:heads.shape[0]]
+
+
 def host_pool() -> Dict[str, int]:
     """The host thread pool's plan, recounted now (ovl_host_pool): {threads, sharers, cpus, packed}."""
     v = [ctypes.c_int32() for _ in range(4)]
@@ -387,6 +410,24 @@ class OverlapEngine:
         v = [ctypes.c_int32() for _ in range(3)]
         check(self._L.ovl_last_local_batch(self._ctx, *[ctypes.byref(x) for x in v]), self._ctx)
         return dict(zip(("batched", "single", "waves"), (x.value for x in v)))
+
+    # ---------------------------------------------------------------- graph stages
+    def transitive_reduce(self, off, heads, weights) -> np.ndarray:
+        """The reference's transitive reduction (overlapGraphs.py:235-303) of a CSR graph on the GPU
+        (ovl_transitive_reduce): a uint8 mask over the CSR edges, 1 where the reference removes the edge."""
+        off, heads, weights = _csr_arrays(off, heads, weights)
+        reduced = np.zeros(max(heads.shape[0], 1), dtype=np.uint8)
+        n_reduced = ctypes.c_int64(0)
+        check(self._L.ovl_transitive_reduce(self._ctx, _ptr(off), _ptr(heads), _ptr(weights), off.shape[0] - 1,
+                                            _ptr(reduced), ctypes.byref(n_reduced)), self._ctx)
+        return reduced[:heads.shape[0]]
+
+    def last_transitive(self) -> Dict[str, int]:
+        """{window, passes, two_hop_steps} of the last ``transitive_reduce`` (ovl_last_transitive): the out-row
+        entries held in LDS per pass, the passes per node, and the two-hop paths walked."""
+        w, p, s = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int64()
+        check(self._L.ovl_last_transitive(self._ctx, ctypes.byref(w), ctypes.byref(p), ctypes.byref(s)), self._ctx)
+        return {"window": w.value, "passes": p.value, "two_hop_steps": s.value}
 
     # ---------------------------------------------------------------- scoring
     def score_pairs(self, reads: Sequence[str], a_idx, b_idx, match: int = 10, mismatch: int = -1,

@@ -21,6 +21,11 @@ reference's find_cycle / remove-weakest-edge loop, through an exact replay of
 that loop in native code (``ovl_remove_cycles``) that does not restart its DFS
 after each removal.  Topological sorting and contig walking (:64-103, :133-193)
 stay networkx/Python.
+
+``transitive_reduction`` (:235-303) and ``assemble_contigs_string`` (:306-329) are
+the string pipeline: the reduction's marking over every two-hop path runs on the
+GPU (``ovl_transitive_reduce``) or, for small graphs and without a GPU, in the
+library's host loop.
 """
 from __future__ import annotations
 
@@ -535,6 +540,21 @@ def _csr_python(nodes, adj):
     return off, heads, weights
 
 
+def _graph_csr(G, nodes, mod):
+    """(off, heads, weights, mod) of a materialised graph: the CSR by the C pass when ``mod`` (the C extension)
+    is given and ``G`` is networkx's own DiGraph over plain dicts, else by the Python passes (``mod`` is then
+    returned as None: the C passes over the graph's dicts do not apply to it)."""
+    adj = G._adj
+    got = mod.csr(nodes, adj, np.integer) if mod is not None and type(G) is nx.DiGraph and type(adj) is dict else None
+    if got is None:
+        return _csr_python(nodes, adj) + (None,)
+    boff, bheads, bw = got
+    off = np.frombuffer(boff, dtype=np.int64)
+    n_edges = int(off[-1])
+    return (off, np.frombuffer(bheads, dtype=np.int32, count=n_edges),
+            np.frombuffer(bw, dtype=np.int64, count=n_edges), mod)
+
+
 # the lazy path's replay and dict build overlapped (build_overlap_stream); OVL_CYCLES_STREAM=0 runs them one after
 # the other (tests compare both)
 _STREAM_OFF = os.environ.get("OVL_CYCLES_STREAM", "1") == "0"
@@ -598,21 +618,10 @@ def remove_cycles_from_graph(overlap_graph, native_edges: Optional[bool] = None,
                           overlapped=False)
         return G
     nodes = list(G)
-    adj = G._adj
     if native_edges and mod is None:
         raise RuntimeError("ovlgraph._digraph is not built (make -C genome-assembly-using-overlap-graphs_amd/csrc)")
     # the C passes need networkx's own DiGraph (plain dicts; remove_edge not overridden)
-    got = mod.csr(nodes, adj, np.integer) if mod is not None and type(G) is nx.DiGraph and type(adj) is dict else None
-    if got is not None:
-        boff, bheads, bw = got
-        off = np.frombuffer(boff, dtype=np.int64)
-        n_edges = int(off[-1])
-        heads = np.frombuffer(bheads, dtype=np.int32, count=n_edges)
-        weights = np.frombuffer(bw, dtype=np.int64, count=n_edges)
-    else:
-        mod = None
-        off, heads, weights = _csr_python(nodes, adj)
-        n_edges = int(off[-1])
+    off, heads, weights, mod = _graph_csr(G, nodes, mod)
     t1 = time.perf_counter()
     removed, n_rem = _replay(off, heads, weights)
     t2 = time.perf_counter()
@@ -706,3 +715,87 @@ def assemble_contigs_using_overlap_graphs(reads, k=5, params=None, engine: Optio
                 contigs.append(create_contig(f"{read}_{copy_index}", dag, visited, topo_order))
     return contigs
 
+
+# transitive_reduction(device=None) takes the GPU from this many two-hop steps (sum over v, over w in succ(v), of
+# deg(w)).  The crossover with the host loop, upload included, lies between two points of tools/transitive_probe.py's
+# sweep and moves with the box's CPU: at 254,016 steps (64 reads) the device call took 72 us against the host loop's
+# 87 us (profiles/transitive.json), 80 against 86 and 75 against 56 in two other runs; at 866,400 steps (96 reads)
+# 81 us against 278 us.  The constant is the first point from which the device call won in every run.
+TRANSITIVE_DEVICE_MIN_STEPS = 866_400
+
+
+def _reduced_mask(off, heads, weights, engine: Optional[OverlapEngine], device: Optional[bool]) -> np.ndarray:
+    """uint8 mask over the CSR edges, 1 where the reference's transitive_reduction removes the edge."""
+    from .engine import device_count, transitive_reduce_host
+    if device is None:
+        steps = int(np.diff(off)[heads].sum()) if heads.shape[0] else 0
+        device = steps >= TRANSITIVE_DEVICE_MIN_STEPS and (engine is not None or device_count() > 0)
+    if not device:
+        return transitive_reduce_host(off, heads, weights)
+    return (engine or default_engine()).transitive_reduce(off, heads, weights)
+
+
+def transitive_reduction(overlap_graph, fuzz=10, engine: Optional[OverlapEngine] = None,
+                         device: Optional[bool] = None):
+    """overlapGraphs.py:235-303: a copy of the graph without the edges (v, x) for which some successor w of v has
+    an edge (w, x) with ``weight(v, w) + weight(w, x) >= weight(v, x)`` -- what the reference's marking loops
+    compute (``fuzz`` is accepted and, as there, never read).  The input is untouched; the result has the input's
+    node and successor order and the predecessor order of ``DiGraph.copy()`` (edges re-added tail-major in node
+    order).  ``weight`` must be an integer on every edge.  The reference's per-step prints are not reproduced.
+
+    The marking runs over a CSR of the graph in native code: on the GPU (``ovl_transitive_reduce``) or by the
+    library's host loop.  ``device=None`` takes the host loop when no GPU is visible or the graph has fewer than
+    ``TRANSITIVE_DEVICE_MIN_STEPS`` two-hop paths; True / False force the choice.  A ``LazyOverlapDiGraph`` that
+    is still columns stays so: the CSR comes from its columns and only the surviving edges' dicts are built."""
+    G = overlap_graph
+    mod = _digraph()
+    if mod is not None and type(G) is LazyOverlapDiGraph and not G.is_materialised:
+        edges = G.__dict__["_ovl_edges"]
+        off, heads, weights = edges.csr()
+        alive = 1 - _reduced_mask(off, heads, weights, engine, device)
+        out = LazyOverlapDiGraph._over(edges)
+        out.graph.update(G.graph)
+        # (insertion order is tail-major here -- pairs a-major, then copies of a -- so the predecessor order of the
+        # surviving edges is the copy's)
+        out._materialise(alive)
+        return out
+    nodes = list(G)
+    try:
+        off, heads, weights, mod = _graph_csr(G, nodes, mod)
+    except TypeError:
+        raise TypeError("transitive_reduction needs an integer 'weight' on every edge") from None
+    reduced = _reduced_mask(off, heads, weights, engine, device)
+    H = G.copy()
+    idx = np.flatnonzero(reduced)
+    if idx.shape[0]:
+        tails = np.searchsorted(off, idx, side="right") - 1
+        if mod is not None and type(H) is nx.DiGraph:
+            try:
+                mod.remove_edges(H._succ, H._pred, nodes, np.ascontiguousarray(tails, np.int64),
+                                 heads[idx].astype(np.int64))
+            finally:
+                nx._clear_cache(H)
+        else:
+            H.remove_edges_from([(nodes[t], nodes[h]) for t, h in zip(tails.tolist(), heads[idx].tolist())])
+    return H
+
+
+def assemble_contigs_string(reads, fuzz=5, engine: Optional[OverlapEngine] = None, scorer=None,
+                            device: Optional[bool] = None, verbose: bool = False):
+    """overlapGraphs.py:306-329: the string pipeline -- all-pairs overlap graph (GPU scoring), transitive
+    reduction, then a greedy walk (``create_contig`` with no topological order: the first unvisited neighbour in
+    adjacency order) from every node whose read is unvisited, in node order.  The same contigs in the same order.
+    ``verbose`` prints the reference's two lines (``overlap_graph: ...`` / ``reduced_graph: ...``), which format
+    every edge; ``scorer`` and ``device`` are ``construct_overlap_graph_string``'s and ``transitive_reduction``'s."""
+    overlap_graph, _read_copies = construct_overlap_graph_string(reads, engine=engine, scorer=scorer)
+    if verbose:
+        print(f"overlap_graph: {overlap_graph.edges}")
+    reduced_graph = transitive_reduction(overlap_graph, engine=engine, device=device)
+    if verbose:
+        print(f"reduced_graph: {reduced_graph.edges}")
+    visited: set = set()
+    contigs = []
+    for node in reduced_graph.nodes():
+        if node.split("_")[0] not in visited:
+            contigs.append(create_contig(node, reduced_graph, visited, {}))
+    return contigs

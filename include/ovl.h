@@ -26,6 +26,8 @@
  *  - Semantics are the reference's: DP fill of aligners.py:27-48 with int64
  *    arithmetic and int32 stores, last-row strict-'>' first argmax of
  *    aligners.py:50-57.  score >= 0 and 0 <= end <= len(t) always.
+ *  - Graph stages on a CSR of the DiGraph: cycle removal (ovl_remove_cycles, host) and the string pipeline's
+ *    transitive reduction (ovl_transitive_reduce, device; overlapGraphs.py:235-303).
  */
 #ifndef OVL_H
 #define OVL_H
@@ -293,6 +295,32 @@ int ovl_remove_cycles(const int64_t* off, const int32_t* head, const int64_t* we
 int ovl_remove_cycles_stream(const int64_t* off, const int32_t* head, const int64_t* weight, int32_t n_nodes,
                              int64_t* removed, int64_t* n_removed, uint8_t* alive, int32_t* final_nodes,
                              int64_t* n_final);
+
+/*
+ * Transitive reduction of overlapGraphs.py:235-303 (transitive_reduction) on the context's first device.
+ * Replaces the marking loops over every two-hop path v -> w -> x (networkx dict lookups and a print per step).
+ * The graph is the CSR of ovl_remove_cycles: node order, adjacency order, int64 weights.  Heads within one node's
+ * list must be distinct (it is a DiGraph); self-loops are allowed.  reduced[e] (capacity off[n_nodes]) = 1 iff
+ * the reference removes CSR edge e, else 0, and *n_reduced their count.  What the reference's loops compute:
+ *   edge (v, x) is removed iff some w in succ(v) -- v and x themselves included when they are successors of v
+ *   -- has an edge (w, x) with weight(v, w) + weight(w, x) >= weight(v, x).
+ * Its fuzz argument is never read, eliminated successors are still expanded, so the result does not depend on the
+ * visiting order.  Every argument is checked on the host before anything is launched or written: OVL_E_ARG for
+ * null pointers, a negative n_nodes, off[0] != 0 or an off that decreases; OVL_E_INDEX for a head outside
+ * [0, n_nodes); OVL_E_RANGE for |weight| >= 2^30 (the device holds int32 weights and forms sums of two).
+ * A window of a node's out-row lives in LDS; a graph with more nodes than the window takes several passes per
+ * node (OVL_TR_WINDOW at context creation lowers the window's entries, for tests).  No device memory grows
+ * faster than the edge count.  With ovl_set_timing on, ovl_last_timing reports the kernel and the call.
+ * ovl_transitive_reduce_host: the same checks and result from a plain host loop (a mark array per source node),
+ * with no context and no GPU -- the small-graph path and the baseline the device call is measured against.
+ * ovl_last_transitive: the window's entries, the passes per node and the two-hop steps
+ * (sum over v, over w in succ(v), of deg(w)) of the last ovl_transitive_reduce.
+ */
+int ovl_transitive_reduce(ovl_ctx* ctx, const int64_t* off, const int32_t* head, const int64_t* weight,
+                          int32_t n_nodes, uint8_t* reduced, int64_t* n_reduced);
+int ovl_transitive_reduce_host(const int64_t* off, const int32_t* head, const int64_t* weight, int32_t n_nodes,
+                               uint8_t* reduced, int64_t* n_reduced);
+int ovl_last_transitive(const ovl_ctx* ctx, int32_t* window_nodes, int32_t* passes, int64_t* two_hop_steps);
 
 #ifdef __cplusplus
 }
