@@ -1,4 +1,4 @@
-// ovl_expand.h — host expansion of packed results (ovl_kernels.hip put_pair, sink 2) into the caller's
+// ovl_expand.h — host expansion of packed results (ovl_sweep.h put_pair, sink 2) into the caller's
 // int32 (score, end) arrays.  Host code only (ovl_pipeline.cpp host_expand; tests/c/expand_test.cpp checks every
 // variant against the scalar form).
 //
@@ -180,7 +180,7 @@ __attribute__((target("avx512f,avx512bw"))) inline void expand_avx512(int32_t* s
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Tile records (ovl_kernels.hip put_ring_rec, the resident grid's ring): tile t's record is 32 dwords at r = rec + 32 t,
+// Tile records (ovl_resident.hip put_ring_rec, the resident grid's ring): tile t's record is 32 dwords at r = rec + 32 t,
 //   r[w] = phase << 31 | c[w + 32] << 15 | c[w]    (c[l]: the 15-bit code of the tile's pair l)
 // c = j(j + 1)/2 + X (end j, X mismatches over L = j compared bases): score = match*j + (mismatch - match)*X.
 // c = 0x7FFF: the pair's special word sp[l] holds it --

@@ -1,10 +1,10 @@
-// ovl_grid.h — the resident scoring grid's interface between its kernel (ovl_kernels.hip resident_kernel) and its
+// ovl_grid.h — the resident scoring grid's interface between its kernel (ovl_resident.hip resident_kernel) and its
 // host side (ovl_resident.h).  Kept apart from ovl_kernels.h so that the other kernel files do not depend on it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-// The resident scoring grid (ovl_kernels.hip resident_kernel; host side ovl_resident.h).  One request: score
+// The resident scoring grid (ovl_resident.hip resident_kernel; host side ovl_resident.h).  One request: score
 // pairs [0, n_pairs) of a_idx / b_idx (device pointers into the resident candidate list) like uniform_kernel's
 // streamed tile records, into a ring of records in pinned host memory: the request's tile t goes to ring tile
 // ri = (pos + t) mod 2^ring_log2 with phase bit ((pos + t) >> ring_log2) + 1 (mod 2), so a ring tile's dwords

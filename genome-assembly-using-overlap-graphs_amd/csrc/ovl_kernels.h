@@ -95,6 +95,12 @@ extern "C" hipError_t ovl_launch_tile_flags(const int32_t* a_idx, int64_t n_pair
                                             int32_t n_reads, uint8_t* flags, hipStream_t stream);
 
 extern "C" hipError_t ovl_launch_dp(const OvlDpArgs* args, hipStream_t stream);
+// the band knob's row and anti-diagonal forms (ovl_band.hip): internal, reached only through ovl_launch_dp's
+// form switch (ovl_dp.hip)
+namespace ovl {
+hipError_t launch_band_rows(const OvlDpArgs* args, hipStream_t stream);
+hipError_t launch_band_diag(const OvlDpArgs* args, hipStream_t stream);
+}  // namespace ovl
 // compact host pair lists (ovl_pairs.hip): dst[i] = src[i] from 2- or 4-byte elements (uint16 0xFFFF -> -1; src and
 // dst 16-byte aligned), and runs: dst[starts[r] .. starts[r + 1]) = vals[r]
 extern "C" hipError_t ovl_launch_widen(const void* src, int32_t width, int64_t n, int32_t* dst, hipStream_t stream);

@@ -27,43 +27,17 @@
 #include <type_traits>
 
 #include "ovl_kernels.h"
+#include "ovl_wave.h"
 
 namespace ovl_local {
 
-__device__ __forceinline__ int32_t shr1(int32_t v) {
-    // lane L receives lane L-1's value (lane 0 gets 0): DPP wave_shr:1
-    return __builtin_amdgcn_update_dpp(0, v, 0x138, 0xF, 0xF, false);
-}
-
-// vec[L] = s: v_writelane_b32 with an inline-constant lane (one SGPR read: the constant-bus limit)
-template <int L>
-__device__ __forceinline__ int32_t writelane(int32_t vec, int32_t s) {
-    asm volatile("v_writelane_b32 %0, %1, %2" : "+v"(vec) : "s"(s), "n"(L));
-    return vec;
-}
-
-// f(integral_constant<int, U>) for U = B .. E-1: a compile-time step index inside the unrolled loop
-template <int B, int E, typename F>
-__device__ __forceinline__ void unroll(F&& f) {
-    if constexpr (B < E) {
-        f(std::integral_constant<int, B>{});
-        unroll<B + 1, E>(f);
-    }
-}
+using namespace ovl_wave;
 
 __device__ __forceinline__ uint64_t ld8(const uint64_t* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 __device__ __forceinline__ void st8(uint64_t* p, uint64_t v) {
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-template <bool TB>
-__device__ __forceinline__ void flush_codes(const uint8_t* tbs, int8_t* dst_chunk, int lane) {
-    const uint4* src = reinterpret_cast<const uint4*>(tbs);
-    uint4* dst = reinterpret_cast<uint4*>(dst_chunk);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) dst[k * 64 + lane] = src[k * 64 + lane];
 }
 
 template <typename Acc, bool TB>
@@ -120,7 +94,7 @@ __global__ __launch_bounds__(64) void sw_kernel(const uint8_t* __restrict__ q, i
                 const int32_t lds_t = __builtin_amdgcn_readlane(v_t, u);
                 if (TB && u == 0 && pend >= 0) {  // (u is a compile-time step index)
                     // the previous chunk's codes leave LDS once this chunk's inputs are in registers
-                    flush_codes<TB>(tbs, tbrow + (int64_t)pend * 64 * 64, lane);
+                    flush_codes(tbs, tbrow + (int64_t)pend * 64 * 64, lane);
                     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
                 }
                 int32_t upin = shr1(cur);
@@ -169,7 +143,7 @@ __global__ __launch_bounds__(64) void sw_kernel(const uint8_t* __restrict__ q, i
         }
         if (TB && pend >= 0) {
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            flush_codes<TB>(tbs, tbrow + (int64_t)pend * 64 * 64, lane);
+            flush_codes(tbs, tbrow + (int64_t)pend * 64 * 64, lane);
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
         }
         // strip's best: max value, then smallest row i, then smallest column j (fill order)

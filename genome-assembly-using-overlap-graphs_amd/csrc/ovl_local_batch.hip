@@ -36,31 +36,15 @@
 #include <type_traits>
 
 #include "ovl_kernels.h"
+#include "ovl_wave.h"
 
 namespace ovl_local_batch {
 
-__device__ __forceinline__ int32_t shr1(int32_t v) {
-    // lane L receives lane L-1's value (lane 0 gets 0): DPP wave_shr:1
-    return __builtin_amdgcn_update_dpp(0, v, 0x138, 0xF, 0xF, false);
-}
-
-template <int L>
-__device__ __forceinline__ int32_t writelane(int32_t vec, int32_t s) {
-    asm volatile("v_writelane_b32 %0, %1, %2" : "+v"(vec) : "s"(s), "n"(L));
-    return vec;
-}
-
-template <int B, int E, typename F>
-__device__ __forceinline__ void unroll(F&& f) {
-    if constexpr (B < E) {
-        f(std::integral_constant<int, B>{});
-        unroll<B + 1, E>(f);
-    }
-}
+using namespace ovl_wave;
 
 // this wavefront's stores become visible to its own other lanes (see the file comment)
 __device__ __forceinline__ void drain() {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    vm_drain();
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
 }
 
@@ -68,13 +52,6 @@ __device__ __forceinline__ void drain() {
 __device__ __forceinline__ uint32_t take(uint32_t* counter, int lane) {
     const uint32_t old = atomicAdd(counter, lane == 0 ? 1u : 0u);
     return (uint32_t)__builtin_amdgcn_readlane((int32_t)old, 0);
-}
-
-__device__ __forceinline__ void flush_codes(const uint8_t* tbs, int8_t* dst_chunk, int lane) {
-    const uint4* src = reinterpret_cast<const uint4*>(tbs);
-    uint4* dst = reinterpret_cast<uint4*>(dst_chunk);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) dst[k * 64 + lane] = src[k * 64 + lane];
 }
 
 template <bool TB>

@@ -6,7 +6,7 @@ void host_copy(void* dst, const void* src, size_t bytes) { CopyPool::get().copy(
 
 namespace {
 
-// Packed results (ovl_kernels.hip put_pair, sink 2) into the caller's int32 arrays (ovl_expand.h), split
+// Packed results (ovl_sweep.h put_pair, sink 2) into the caller's int32 arrays (ovl_expand.h), split
 // over the host pool, at the widest vector width this CPU runs.
 void host_expand(int32_t* s, int32_t* e, const uint16_t* pk, const int32_t* esc, int32_t match, int32_t mismatch,
                  bool nt, size_t n, size_t min_part) {
@@ -610,7 +610,7 @@ int device_cuts(Dev* d, int64_t lo, int64_t hi, int32_t shards, std::vector<int6
     return OVL_OK;
 }
 
-// Direct host-array calls move results packed (ovl_kernels.hip put_pair, sink 2: end and mismatch count
+// Direct host-array calls move results packed (ovl_sweep.h put_pair, sink 2: end and mismatch count
 // in a uint16) when the uniform kernel scores them with int32 keys and reads are at most 254 bases (ends
 // and mismatch counts below the 0xFF marker).  One-device contexts only: the calling thread's host pool
 // expands every packed chunk, so N devices would funnel N links' results through one pool, where int32

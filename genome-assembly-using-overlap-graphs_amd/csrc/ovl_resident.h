@@ -1,4 +1,4 @@
-// ovl_resident.h — host side of the resident scoring grid (ovl_kernels.hip resident_kernel): one per device of a
+// ovl_resident.h — host side of the resident scoring grid (ovl_resident.hip resident_kernel): one per device of a
 // context, launched on the first eligible call and left running, so a call posts a request into pinned memory and
 // expands the ring records as they land -- no launch, no completion event.  Host code only,
 // included through ovl_ctx.h.

@@ -1,4 +1,4 @@
-// Tile records (genome-assembly-using-overlap-graphs_amd/csrc/ovl_expand.h; ovl_kernels.hip put_ring_rec, the
+// Tile records (genome-assembly-using-overlap-graphs_amd/csrc/ovl_expand.h; ovl_resident.hip put_ring_rec, the
 // resident grid's ring, whose decoders rec_tile_*_t these side-array forms share): (1) every code j(j + 1)/2 + X, X <= j <= 254, decodes to (j, X); (2) random tiles -- window pairs
 // and bad pairs among them (special words), ends of 0, partial last tiles -- encoded by the host restatement of
 // the record encoder (encode_rec_tile) in either phase decode through the scalar form and, where this CPU runs it, the

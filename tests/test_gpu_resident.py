@@ -1,4 +1,4 @@
-"""GPU: the resident scoring grid (ovl_kernels.hip resident_kernel, ovl_resident.h) against the oracle.
+"""GPU: the resident scoring grid (ovl_resident.hip resident_kernel, ovl_resident.h) against the oracle.
 
 With OVL_RESIDENT=1 (opt-in), ovl_score_candidates(_range) calls of the uniform kernel's form go to a kernel that
 stays on the device between calls and takes requests through pinned memory.  Every result is compared bit for bit with the
