@@ -113,6 +113,7 @@ Knobs read_knobs() {
     }
     if (const char* e = getenv("OVL_LOCAL_BATCH_WAVES")) k.local_batch_waves = std::max(0, atoi(e));
     if (const char* e = getenv("OVL_TR_WINDOW")) k.tr_window = std::max(0, atoi(e));
+    if (const char* e = getenv("OVL_REACH_WINDOW")) k.reach_window = std::max(0, atoi(e));
     if (const char* e = getenv("OVL_PIPE_CHUNK")) {
         const long long v = atoll(e);
         if (v >= 64) k.pipe_chunk = v;
@@ -133,12 +134,15 @@ void destroy_dev(Dev* d) {
                       &d->sh_cum, &d->sh_temp, &d->sh_cuts, &d->l_q, &d->l_r, &d->l_row, &d->l_tb, &d->l_best,
                       &d->lane_col, &d->seed_s, &d->seed_e, &d->tile_flags, &d->heavy_ids, &d->cp_hbm, &d->lb_in,
                       &d->lb_ctr, &d->lb_rows, &d->lb_slabs, &d->lb_wops, &d->lb_out, &d->lb_ops, &d->tr_off,
-                      &d->tr_edge, &d->tr_order, &d->tr_ctr, &d->tr_out})
+                      &d->tr_edge, &d->tr_order, &d->tr_ctr, &d->tr_out, &d->rc_off, &d->rc_head, &d->rc_order,
+                      &d->rc_matrix, &d->rc_pivot, &d->rc_out})
         release(*b);
     if (d->l_tb_host) (void)hipHostFree(d->l_tb_host);
     for (hipEvent_t e : d->lb_ev)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : d->tr_ev)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : d->rc_ev)
         if (e) (void)hipEventDestroy(e);
     free_staging(d->st_in);
     free_staging(d->st_out);

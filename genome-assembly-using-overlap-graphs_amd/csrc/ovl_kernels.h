@@ -209,6 +209,34 @@ struct OvlReduceArgs {
 };
 extern "C" hipError_t ovl_launch_reduce(const OvlReduceArgs* a, int32_t blocks, hipStream_t stream);
 
+// reachability reduction of a string graph (ovl_reach.hip): matrix is n_nodes rows of `words` = ceil(n_nodes / 64)
+// uint64 (bit x of row u: a path of at least one edge from u to x), pivot 64 rows of the same width.  In stream
+// order: fill (the rows from the CSR; heads validated in [0, n_nodes)), then for K = 0 .. words - 1 pivot and
+// update (`group` lanes per row: a power of two, 1 .. 64), then mark over order[0 .. n_order) -- the nodes with at
+// least two out-edges, heaviest first -- with `group` lanes per node holding kReachAccWords words each of a column
+// window of window_words <= min(words, group * kReachAccWords) words (window_words <= group: one word per lane and
+// kReachAhead * kReachAccWords rows in flight).  mark stores reduced[e] for every edge of those nodes.
+constexpr int kReachLoads = 16;    // pivot rows a lane of update loads per trip over a dense pivot word, all in
+                                   // flight before the first OR (four per trip over a sparse one)
+constexpr int kReachAhead = 4;     // successors whose rows a lane of mark loads before the first is used
+                                   // (kReachAhead * kReachAccWords where a lane holds one word of acc)
+constexpr int kReachAccWords = 4;  // words of acc per lane of mark
+struct OvlReachArgs {
+    const int64_t* off;
+    const int32_t* head;
+    const int32_t* order;
+    int32_t n_nodes, n_order;
+    int32_t words;
+    uint64_t* matrix;
+    uint64_t* pivot;
+    uint8_t* reduced;
+};
+extern "C" hipError_t ovl_launch_reach_fill(const OvlReachArgs* a, hipStream_t stream);
+extern "C" hipError_t ovl_launch_reach_pivot(const OvlReachArgs* a, int32_t K, hipStream_t stream);
+extern "C" hipError_t ovl_launch_reach_update(const OvlReachArgs* a, int32_t K, int32_t group, hipStream_t stream);
+extern "C" hipError_t ovl_launch_reach_mark(const OvlReachArgs* a, int32_t group, int32_t window_words,
+                                            hipStream_t stream);
+
 // shard bounds of a pair list balanced by len[a]*len[b] + 1 (ovl_candidates.hip): ovl_shard_scan writes
 // the inclusive prefix sum of the costs (n_pairs int64), ovl_shard_cut the shards + 1 cuts of [lo, hi)
 extern "C" hipError_t ovl_shard_temp_bytes(int64_t n_pairs, size_t* bytes);

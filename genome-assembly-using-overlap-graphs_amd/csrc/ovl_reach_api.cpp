@@ -1,0 +1,182 @@
+// ovl_reach_api.cpp — reachability reduction of a string graph (overlapGraphs.py:354-367, transitive_reduction2):
+// the host form (ovl_reach_reduce_host) and the device call (ovl_reach_reduce, ovl_reach.hip).  The argument checks
+// are ovl_graph_check.h's, shared with ovl_reduce_api.cpp.
+#include "ovl_ctx.h"
+#include "ovl_graph_check.h"
+
+namespace {
+
+constexpr int32_t kReachWindowWords = 64 * kReachAccWords;  // a wavefront's acc: 16,384 columns per window
+
+// rows * words uint64, or false when the size does not fit or cannot be allocated
+bool alloc_matrix(std::vector<uint64_t>& m, int64_t rows, int64_t words) {
+    if (words > 0 && rows > (int64_t)(SIZE_MAX / sizeof(uint64_t)) / words) return false;
+    try {
+        m.assign((size_t)(rows * words), 0);
+    } catch (const std::bad_alloc&) {
+        return false;
+    }
+    return true;
+}
+
+// R[u] = the nodes reachable from u by at least one edge: the adjacency rows, then row-OR Warshall
+void closure_host(const int64_t* off, const int32_t* head, int32_t n, int64_t words, uint64_t* R) {
+    for (int32_t v = 0; v < n; ++v)
+        for (int64_t e = off[v]; e < off[v + 1]; ++e) R[v * words + (head[e] >> 6)] |= uint64_t(1) << (head[e] & 63);
+    for (int32_t k = 0; k < n; ++k) {
+        const uint64_t* rk = R + k * words;
+        const int64_t kw = k >> 6;
+        const uint64_t kb = uint64_t(1) << (k & 63);
+        for (int32_t i = 0; i < n; ++i) {
+            uint64_t* ri = R + i * words;
+            if (!(ri[kw] & kb) || i == k) continue;
+            for (int64_t j = 0; j < words; ++j) ri[j] |= rk[j];
+        }
+    }
+}
+
+// the positional rule over the closure: acc = OR of R[u] over the successors seen so far
+int64_t mark_host(const int64_t* off, const int32_t* head, int32_t n, int64_t words, const uint64_t* R,
+                  uint8_t* reduced) {
+    std::vector<uint64_t> acc((size_t)words);
+    int64_t count = 0;
+    for (int32_t v = 0; v < n; ++v) {
+        const int64_t e0 = off[v], e1 = off[v + 1];
+        if (e1 - e0 < 2) {
+            if (e1 > e0) reduced[e0] = 0;  // a first successor is never removed
+            continue;
+        }
+        std::fill(acc.begin(), acc.end(), 0);
+        for (int64_t e = e0; e < e1; ++e) {
+            const int32_t w = head[e];
+            reduced[e] = (uint8_t)((acc[(size_t)(w >> 6)] >> (w & 63)) & 1u);
+            count += reduced[e];
+            const uint64_t* rw = R + w * words;
+            for (int64_t j = 0; j < words; ++j) acc[(size_t)j] |= rw[j];
+        }
+    }
+    return count;
+}
+
+int32_t pow2_at_least(int32_t x, int32_t cap) {
+    int32_t g = 1;
+    while (g < x && g < cap) g *= 2;
+    return g;
+}
+
+}  // namespace
+
+OVL_API int ovl_reach_reduce_host(const int64_t* off, const int32_t* head, int32_t n_nodes, uint8_t* reduced,
+                                  int64_t* n_reduced, uint64_t* closure) {
+    const ovl_ctx* none = nullptr;
+    const int rc = check_graph(none, off, head, nullptr, false, n_nodes, reduced, n_reduced, nullptr, nullptr);
+    if (rc != OVL_OK) return rc;
+    const int64_t words = ((int64_t)n_nodes + 63) / 64;
+    std::vector<uint64_t> own;
+    uint64_t* R = closure;
+    if (!R) {
+        if (!alloc_matrix(own, n_nodes, words))
+            return fail(none, OVL_E_OOM, "no memory for the %d x %d-bit reachability matrix", n_nodes, n_nodes);
+        R = own.data();
+    } else {
+        std::fill(R, R + (int64_t)n_nodes * words, uint64_t(0));
+    }
+    closure_host(off, head, n_nodes, words, R);
+    *n_reduced = mark_host(off, head, n_nodes, words, R, reduced);
+    return OVL_OK;
+}
+
+OVL_API int ovl_reach_reduce(ovl_ctx* ctx, const int64_t* off, const int32_t* head, int32_t n_nodes, uint8_t* reduced,
+                             int64_t* n_reduced, uint64_t* closure) {
+    if (!ctx) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
+    quiet(ctx);
+    Dev* c = ctx->devs[0];
+    DeviceGuard guard;
+    const auto t_call = std::chrono::steady_clock::now();
+    const int rc = check_graph(c, off, head, nullptr, false, n_nodes, reduced, n_reduced, nullptr, nullptr);
+    if (rc != OVL_OK) return rc;
+    const int64_t n_edges = n_nodes > 0 ? off[n_nodes] : 0;
+    const int32_t words = (int32_t)(((int64_t)n_nodes + 63) / 64);
+    int32_t window_words = kReachWindowWords;
+    if (c->k.reach_window > 0) window_words = std::min(kReachWindowWords, (c->k.reach_window + 63) / 64);
+    ctx->x_rc_words = words;
+    ctx->x_rc_blocks = words;  // ceil(n_nodes / 64) pivot blocks: one per word column
+    ctx->x_rc_window = window_words * 64;
+    ctx->t_kernel_ms = ctx->t_call_ms = 0.0;
+    const size_t matrix_bytes = sizeof(uint64_t) * (size_t)n_nodes * (size_t)words;
+    if (n_edges == 0) {  // nothing reaches anything
+        if (closure && matrix_bytes) memset(closure, 0, matrix_bytes);
+        *n_reduced = 0;
+        return OVL_OK;
+    }
+    // nodes with at least two out-edges, heaviest (degree x words) first, ties in node order
+    std::vector<int32_t> order;
+    for (int32_t v = 0; v < n_nodes; ++v)
+        if (off[v + 1] - off[v] >= 2) order.push_back(v);
+    std::stable_sort(order.begin(), order.end(),
+                     [&](int32_t x, int32_t y) { return off[x + 1] - off[x] > off[y + 1] - off[y]; });
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    HIPCHK(c, ensure(c->rc_matrix, matrix_bytes));
+    HIPCHK(c, ensure(c->rc_pivot, sizeof(uint64_t) * 64 * (size_t)words));
+    HIPCHK(c, ensure(c->rc_off, sizeof(int64_t) * ((size_t)n_nodes + 1)));
+    HIPCHK(c, ensure(c->rc_head, sizeof(int32_t) * (size_t)n_edges));
+    HIPCHK(c, ensure(c->rc_order, sizeof(int32_t) * order.size()));
+    HIPCHK(c, ensure(c->rc_out, (size_t)n_edges));
+    HIPCHK(c, hipMemcpyAsync(c->rc_off.p, off, sizeof(int64_t) * ((size_t)n_nodes + 1), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(c->rc_head.p, head, sizeof(int32_t) * (size_t)n_edges, hipMemcpyHostToDevice, s));
+    if (!order.empty())
+        HIPCHK(c, hipMemcpyAsync(c->rc_order.p, order.data(), sizeof(int32_t) * order.size(), hipMemcpyHostToDevice,
+                                 s));
+    HIPCHK(c, hipMemsetAsync(c->rc_out.p, 0, (size_t)n_edges, s));  // (nodes with one out-edge keep it)
+    OvlReachArgs a{};
+    a.off = as<int64_t>(c->rc_off);
+    a.head = as<int32_t>(c->rc_head);
+    a.order = as<int32_t>(c->rc_order);
+    a.n_nodes = n_nodes;
+    a.n_order = (int32_t)order.size();
+    a.words = words;
+    a.matrix = as<uint64_t>(c->rc_matrix);
+    a.pivot = as<uint64_t>(c->rc_pivot);
+    a.reduced = as<uint8_t>(c->rc_out);
+    const int32_t row_group = pow2_at_least(words, 64);
+    // the window the marking walks with: never wider than a row, so that rows of up to 64 words take the
+    // one-word-per-lane form (ovl_launch_reach_mark) at the default window too
+    const int32_t mark_window = std::min(words, window_words);
+    const int32_t mark_group = pow2_at_least(mark_window, 64);
+    if (ctx->timing) {
+        for (hipEvent_t& e : c->rc_ev)
+            if (!e) HIPCHK(c, hipEventCreate(&e));
+        HIPCHK(c, hipEventRecord(c->rc_ev[0], s));
+    }
+    HIPCHK(c, ovl_launch_reach_fill(&a, s));
+    if (closure || !order.empty()) {
+        for (int32_t K = 0; K < words; ++K) {
+            HIPCHK(c, ovl_launch_reach_pivot(&a, K, s));
+            HIPCHK(c, ovl_launch_reach_update(&a, K, row_group, s));
+        }
+    }
+    HIPCHK(c, ovl_launch_reach_mark(&a, mark_group, mark_window, s));
+    if (ctx->timing) HIPCHK(c, hipEventRecord(c->rc_ev[1], s));
+    HIPCHK(c, hipMemcpyAsync(reduced, c->rc_out.p, (size_t)n_edges, hipMemcpyDeviceToHost, s));
+    if (closure) HIPCHK(c, hipMemcpyAsync(closure, c->rc_matrix.p, matrix_bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (ctx->timing) {
+        float ms = 0.f;
+        HIPCHK(c, hipEventElapsedTime(&ms, c->rc_ev[0], c->rc_ev[1]));
+        ctx->t_kernel_ms = ms;
+    }
+    int64_t count = 0;
+    for (int64_t e = 0; e < n_edges; ++e) count += reduced[e];
+    *n_reduced = count;
+    ctx->t_call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+    return OVL_OK;
+}
+
+OVL_API int ovl_last_reach(const ovl_ctx* ctx, int32_t* words_per_row, int32_t* pivot_blocks, int32_t* window_bits) {
+    if (!ctx) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
+    if (words_per_row) *words_per_row = ctx->x_rc_words;
+    if (pivot_blocks) *pivot_blocks = ctx->x_rc_blocks;
+    if (window_bits) *window_bits = ctx->x_rc_window;
+    return OVL_OK;
+}

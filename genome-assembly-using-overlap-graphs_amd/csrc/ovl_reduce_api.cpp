@@ -1,43 +1,12 @@
 // ovl_reduce_api.cpp — transitive reduction of an overlap graph (overlapGraphs.py:235-303): the argument checks,
 // the host form (ovl_transitive_reduce_host) and the device call (ovl_transitive_reduce, ovl_reduce.hip).
 #include "ovl_ctx.h"
+#include "ovl_graph_check.h"
 
 namespace {
 
 constexpr int32_t kReduceWindow = 20224;   // out-row entries in LDS per pass (79 KiB: two workgroups per CU)
 constexpr int32_t kReduceBlocksPerCu = 2;
-constexpr int64_t kReduceWeightLimit = int64_t(1) << 30;  // the device forms int32 sums of two weights
-
-// Every check of both entry points, before anything is launched or written.  `work` and `steps`, when given (both
-// or neither), receive each node's two-hop work sum over w in succ(v) of deg(w) and their total.
-template <typename C>
-int check_graph(const C* c, const int64_t* off, const int32_t* head, const int64_t* weight, int32_t n_nodes,
-                const uint8_t* reduced, const int64_t* n_reduced, std::vector<int64_t>* work, int64_t* steps) {
-    if (n_nodes < 0) return fail(c, OVL_E_ARG, "negative node count");
-    if (!off || !n_reduced) return fail(c, OVL_E_ARG, "NULL off or n_reduced");
-    if (off[0] != 0) return fail(c, OVL_E_ARG, "off[0] = %lld, not 0", (long long)off[0]);
-    for (int32_t v = 0; v < n_nodes; ++v)
-        if (off[v + 1] < off[v]) return fail(c, OVL_E_ARG, "off decreases at node %d", v);
-    const int64_t n_edges = off[n_nodes];
-    if (n_edges > 0 && (!head || !weight || !reduced)) return fail(c, OVL_E_ARG, "NULL head, weight or reduced");
-    for (int64_t e = 0; e < n_edges; ++e)
-        if (head[e] < 0 || head[e] >= n_nodes)
-            return fail(c, OVL_E_INDEX, "edge %lld: head %d outside [0, %d)", (long long)e, head[e], n_nodes);
-    for (int64_t e = 0; e < n_edges; ++e)
-        if (weight[e] >= kReduceWeightLimit || weight[e] <= -kReduceWeightLimit)
-            return fail(c, OVL_E_RANGE, "edge %lld: |weight| = |%lld| >= 2^30", (long long)e, (long long)weight[e]);
-    if (!work) return OVL_OK;  // the host form needs no step counts
-    int64_t total = 0;
-    work->assign((size_t)n_nodes, 0);
-    for (int32_t v = 0; v < n_nodes; ++v) {
-        int64_t w = 0;
-        for (int64_t e = off[v]; e < off[v + 1]; ++e) w += off[head[e] + 1] - off[head[e]];
-        (*work)[(size_t)v] = w;
-        total += w;
-    }
-    *steps = total;
-    return OVL_OK;
-}
 
 // A mark array per source node, reset by re-walking the node's successors.
 void reduce_host(const int64_t* off, const int32_t* head, const int64_t* weight, int32_t n_nodes, uint8_t* reduced,
@@ -73,8 +42,8 @@ void reduce_host(const int64_t* off, const int32_t* head, const int64_t* weight,
 
 OVL_API int ovl_transitive_reduce_host(const int64_t* off, const int32_t* head, const int64_t* weight,
                                        int32_t n_nodes, uint8_t* reduced, int64_t* n_reduced) {
-    const int rc = check_graph((const ovl_ctx*)nullptr, off, head, weight, n_nodes, reduced, n_reduced, nullptr,
-                               nullptr);
+    const int rc = check_graph((const ovl_ctx*)nullptr, off, head, weight, true, n_nodes, reduced, n_reduced,
+                               nullptr, nullptr);
     if (rc != OVL_OK) return rc;
     reduce_host(off, head, weight, n_nodes, reduced, n_reduced);
     return OVL_OK;
@@ -89,7 +58,7 @@ OVL_API int ovl_transitive_reduce(ovl_ctx* ctx, const int64_t* off, const int32_
     const auto t_call = std::chrono::steady_clock::now();
     std::vector<int64_t> work;
     int64_t steps = 0;
-    const int rc = check_graph(c, off, head, weight, n_nodes, reduced, n_reduced, &work, &steps);
+    const int rc = check_graph(c, off, head, weight, true, n_nodes, reduced, n_reduced, &work, &steps);
     if (rc != OVL_OK) return rc;
     const int64_t n_edges = n_nodes > 0 ? off[n_nodes] : 0;
     const int32_t window = std::min(kReduceWindow, c->k.tr_window > 0 ? c->k.tr_window : kReduceWindow);

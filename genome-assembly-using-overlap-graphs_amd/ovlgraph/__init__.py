@@ -13,13 +13,15 @@ from ._lib import OvlError  # noqa: F401
 from .engine import INDEL_DEFAULT, OverlapEngine, default_engine, encode_reads, score_reads  # noqa: F401
 
 __all__ = ["OvlError", "OverlapEngine", "default_engine", "encode_reads", "score_reads", "INDEL_DEFAULT",
-           "transitive_reduction", "assemble_contigs_string"]
+           "transitive_reduction", "assemble_contigs_string", "transitive_reduction2", "find_unitigs",
+           "assemble_contigs"]
 
 
 def __getattr__(name):
-    # the string pipeline's entry points live in overlapGraphs, which imports networkx: loaded on first use, so
+    # the string and unitig pipelines' entry points live in overlapGraphs, which imports networkx: loaded on first use, so
     # scoring-only processes (the sharded workers) do not pay for it
-    if name in ("transitive_reduction", "assemble_contigs_string"):
+    if name in ("transitive_reduction", "assemble_contigs_string", "transitive_reduction2", "find_unitigs",
+                "assemble_contigs"):
         from . import overlapGraphs
         return getattr(overlapGraphs, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -103,6 +103,31 @@ def transitive_reduce_host(off, heads, weights) -> np.ndarray:
     return reduced[:heads.shape[0]]
 
 
+def _reach_arrays(off, heads, closure: bool):
+    """A weightless CSR graph as the C ABI takes it, with the mask and (``closure``) the n x ceil(n / 64) uint64
+    matrix to receive the results."""
+    off = np.ascontiguousarray(off, dtype=np.int64)
+    heads = np.ascontiguousarray(heads, dtype=np.int32)
+    if off.ndim != 1 or off.shape[0] < 1 or heads.ndim != 1:
+        raise OvlError(-1, "CSR graph: off needs n_nodes + 1 entries, heads one entry per edge")
+    if int(off[-1]) > heads.shape[0]:
+        raise OvlError(-1, f"CSR graph: off[-1] = {int(off[-1])} exceeds the {heads.shape[0]} edges given")
+    n = off.shape[0] - 1
+    reduced = np.zeros(max(heads.shape[0], 1), dtype=np.uint8)
+    matrix = np.zeros((n, (n + 63) // 64), dtype=np.uint64) if closure else None
+    return off, heads, reduced, matrix
+
+
+def reach_reduce_host(off, heads, closure: bool = False):
+    """``OverlapEngine.reach_reduce`` on one host thread (ovl_reach_reduce_host): no context, no GPU."""
+    off, heads, reduced, matrix = _reach_arrays(off, heads, closure)
+    n_reduced = ctypes.c_int64(0)
+    check(_lib.load().ovl_reach_reduce_host(_ptr(off), _ptr(heads), off.shape[0] - 1, _ptr(reduced),
+                                            ctypes.byref(n_reduced), _ptr(matrix) if closure else None))
+    mask = reduced[:heads.shape[0]]
+    return (mask, matrix) if closure else mask
+
+
 def host_pool() -> Dict[str, int]:
     """The host thread pool's plan, recounted now (ovl_host_pool): {threads, sharers, cpus, packed}."""
     v = [ctypes.c_int32() for _ in range(4)]
@@ -428,6 +453,26 @@ class OverlapEngine:
         w, p, s = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int64()
         check(self._L.ovl_last_transitive(self._ctx, ctypes.byref(w), ctypes.byref(p), ctypes.byref(s)), self._ctx)
         return {"window": w.value, "passes": p.value, "two_hop_steps": s.value}
+
+    def reach_reduce(self, off, heads, closure: bool = False):
+        """The reference's ``transitive_reduction2`` (overlapGraphs.py:354-367) of a weightless CSR graph on the GPU
+        (ovl_reach_reduce): a uint8 mask over the CSR edges, 1 where the reference removes the edge -- edge (v, w)
+        goes iff a successor of v that stands before w reaches w.  ``closure=True`` returns ``(mask, matrix)``, the
+        matrix n x ceil(n / 64) uint64: bit x & 63 of word x >> 6 of row u is set iff a path of at least one edge
+        leads from u to x."""
+        off, heads, reduced, matrix = _reach_arrays(off, heads, closure)
+        n_reduced = ctypes.c_int64(0)
+        check(self._L.ovl_reach_reduce(self._ctx, _ptr(off), _ptr(heads), off.shape[0] - 1, _ptr(reduced),
+                                       ctypes.byref(n_reduced), _ptr(matrix) if closure else None), self._ctx)
+        mask = reduced[:heads.shape[0]]
+        return (mask, matrix) if closure else mask
+
+    def last_reach(self) -> Dict[str, int]:
+        """{words_per_row, pivot_blocks, window_bits} of the last ``reach_reduce`` (ovl_last_reach): the bit matrix's
+        row width, the closure's pivot blocks of 64 nodes, and the columns the marking holds in registers per pass."""
+        v = [ctypes.c_int32() for _ in range(3)]
+        check(self._L.ovl_last_reach(self._ctx, *[ctypes.byref(x) for x in v]), self._ctx)
+        return dict(zip(("words_per_row", "pivot_blocks", "window_bits"), (x.value for x in v)))
 
     # ---------------------------------------------------------------- scoring
     def score_pairs(self, reads: Sequence[str], a_idx, b_idx, match: int = 10, mismatch: int = -1,

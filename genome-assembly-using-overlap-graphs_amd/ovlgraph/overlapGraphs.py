@@ -26,6 +26,11 @@ stay networkx/Python.
 the string pipeline: the reduction's marking over every two-hop path runs on the
 GPU (``ovl_transitive_reduce``) or, for small graphs and without a GPU, in the
 library's host loop.
+
+``transitive_reduction2`` (:354-367), ``find_unitigs`` (:370-402) and ``assemble_contigs``
+(:405-412) are the unitig pipeline: the reduction's one ``nx.has_path`` search per pair of
+successors becomes a reachability bit matrix, closed and swept on the GPU
+(``ovl_reach_reduce``) or, for small graphs and without a GPU, on one host thread.
 """
 from __future__ import annotations
 
@@ -506,6 +511,13 @@ def construct_overlap_graph_string(reads, engine: Optional[OverlapEngine] = None
 
 def construct_string_graph(reads, engine: Optional[OverlapEngine] = None, scorer=None):
     """Raw reads as nodes, ``combinations(reads, 2)`` scored, edges where score > 0 (:332-351)."""
+    G = _string_graph(reads, engine, scorer)
+    print(f"graph: {G.edges}")
+    return G
+
+
+def _string_graph(reads, engine: Optional[OverlapEngine], scorer) -> nx.DiGraph:
+    """``construct_string_graph`` without its ``graph:`` line (which formats every edge)."""
     reads = list(reads)
     G = nx.DiGraph()
     G.add_nodes_from(reads)
@@ -521,7 +533,6 @@ def construct_string_graph(reads, engine: Optional[OverlapEngine] = None, scorer
     sc, en = _score(distinct, np.ascontiguousarray(a), np.ascontiguousarray(b), engine, scorer)
     G.add_edges_from((distinct[x], distinct[y], {"weight": s, "end_position": e})
                      for x, y, s, e in zip(a.tolist(), b.tolist(), sc.tolist(), en.tolist()) if s > 0)
-    print(f"graph: {G.edges}")
     return G
 
 
@@ -799,3 +810,109 @@ def assemble_contigs_string(reads, fuzz=5, engine: Optional[OverlapEngine] = Non
         if node.split("_")[0] not in visited:
             contigs.append(create_contig(node, reduced_graph, visited, {}))
     return contigs
+
+
+# transitive_reduction2(device=None) takes the GPU from this many nodes.  The unit is the node count because both
+# costs follow it, not the edge count: the closure is n rows of ceil(n / 64) words OR-ed along up to n pivots, and a
+# device call pays 2 * ceil(n / 64) + 2 launches whatever the graph holds (a 16,384-node digraph of 49,152 edges:
+# 19.9 ms against the host form's 6.76 s).  From tools/reach_probe.py's two sweeps over string graphs
+# (profiles/reach.json; medians of 5, upload included): 256 nodes 258 us against the host form's 166 us; 400 nodes
+# 375 against 410, a 9 % margin with the repetitions' ranges 20 and 44 us wide, so that point turns with the box's
+# CPU; 495 nodes 471 against 664, and from there the device call won at every point (1,663 nodes: 1.96 ms against
+# 17.2 ms).  The constant is the first point from which it won clear of the repetitions' spread.
+REACH_DEVICE_MIN_WORK = 495
+
+
+def _csr_heads(nodes, adj) -> Tuple[np.ndarray, np.ndarray]:
+    """The successor lists as a weightless CSR (node order, adjacency order within a node); no edge attribute is
+    read."""
+    index = {v: i for i, v in enumerate(nodes)}
+    deg = np.fromiter((len(adj[u]) for u in nodes), dtype=np.int64, count=len(nodes))
+    off = np.zeros(len(nodes) + 1, dtype=np.int64)
+    np.cumsum(deg, out=off[1:])
+    heads = np.fromiter((index[v] for u in nodes for v in adj[u]), dtype=np.int32, count=int(off[-1]))
+    return off, heads
+
+
+def transitive_reduction2(graph, engine: Optional[OverlapEngine] = None, device: Optional[bool] = None):
+    """overlapGraphs.py:354-367: a copy of the graph without the edges (v, w) for which a successor u of v that
+    stands before w in v's successor order reaches w by a path of at least one edge -- what the reference's
+    ``nx.has_path`` call per ``combinations(successors(v), 2)`` pair computes.  The searches run on the input
+    graph, so the visiting order does not matter; the first successor of a node always stays; a self-loop (v, v)
+    removes every later successor of v.  The input is untouched; the result has the input's node and successor
+    order and the predecessor order of ``DiGraph.copy()`` (edges re-added tail-major in node order).  Any DiGraph
+    with any hashable nodes; no edge attribute is read.  The reference's ``Removing edge`` prints are not
+    reproduced.
+
+    The rule runs over a CSR of the graph in native code, on a reachability bit matrix of n^2 / 8 bytes: on the GPU
+    (``ovl_reach_reduce``: blocked Warshall, then one sweep per node) or on one host thread.  ``device=None`` takes
+    the host form when no GPU is visible or the graph has fewer than ``REACH_DEVICE_MIN_WORK`` nodes; True / False
+    force the choice."""
+    from .engine import device_count, reach_reduce_host
+    G = graph
+    nodes = list(G)
+    off, heads = _csr_heads(nodes, G._adj)
+    if device is None:
+        device = len(nodes) >= REACH_DEVICE_MIN_WORK and (engine is not None or device_count() > 0)
+    reduced = (engine or default_engine()).reach_reduce(off, heads) if device else reach_reduce_host(off, heads)
+    H = G.copy()
+    idx = np.flatnonzero(reduced)
+    if idx.shape[0]:
+        tails = np.searchsorted(off, idx, side="right") - 1
+        mod = _digraph()
+        if mod is not None and type(H) is nx.DiGraph:
+            try:
+                mod.remove_edges(H._succ, H._pred, nodes, np.ascontiguousarray(tails, np.int64),
+                                 heads[idx].astype(np.int64))
+            finally:
+                nx._clear_cache(H)
+        else:
+            H.remove_edges_from([(nodes[t], nodes[h]) for t, h in zip(tails.tolist(), heads[idx].tolist())])
+    return H
+
+
+def find_unitigs(graph):
+    """overlapGraphs.py:370-402: from every node not yet on a path, in node order, extend a path while its last node
+    has exactly one successor and one predecessor and that successor is unvisited; the unitig is the first node's
+    string plus each further node past the edge's ``end_position``.  Only the path's last node is tested, so a node
+    with several predecessors is still appended (and ends the path).  The same unitigs in the same order; the
+    reference's ``next_node:`` prints are not reproduced.
+
+    One deliberate difference: when the next node is already on the current path -- a lone self-loop, a two-node
+    cycle, any cycle of nodes with in- and out-degree 1 entered at one of them -- the reference appends it again
+    and never returns.  Here that raises ``ValueError`` naming the node."""
+    unitigs = []
+    visited: set = set()
+    succ, pred = graph._succ, graph._pred
+    for node in graph.nodes():
+        if node in visited:
+            continue
+        path = [node]
+        on_path = {node}
+        while len(succ[path[-1]]) == 1 and len(pred[path[-1]]) == 1:
+            next_node = next(iter(succ[path[-1]]))
+            if next_node in visited:
+                break
+            if next_node in on_path:
+                raise ValueError(f"find_unitigs: the path from {node!r} comes back to {next_node!r}, a cycle of "
+                                 "non-branching nodes on which the reference's walk never ends")
+            path.append(next_node)
+            on_path.add(next_node)
+        visited.update(path)
+        seq = path[0]
+        for i in range(1, len(path)):
+            seq += path[i][succ[path[i - 1]][path[i]]["end_position"]:]
+        unitigs.append(seq)
+    return unitigs
+
+
+def assemble_contigs(reads, engine: Optional[OverlapEngine] = None, scorer=None, device: Optional[bool] = None,
+                     verbose: bool = False):
+    """overlapGraphs.py:405-412: the unitig pipeline -- ``construct_string_graph`` (GPU scoring),
+    ``transitive_reduction2``, ``find_unitigs``.  The same contigs in the same order.  ``verbose`` prints
+    ``construct_string_graph``'s ``graph: ...`` line, which formats every edge; ``scorer`` and ``device`` are
+    ``construct_string_graph``'s and ``transitive_reduction2``'s."""
+    graph = _string_graph(reads, engine, scorer)
+    if verbose:
+        print(f"graph: {graph.edges}")
+    return find_unitigs(transitive_reduction2(graph, engine=engine, device=device))

@@ -27,7 +27,8 @@
  *    arithmetic and int32 stores, last-row strict-'>' first argmax of
  *    aligners.py:50-57.  score >= 0 and 0 <= end <= len(t) always.
  *  - Graph stages on a CSR of the DiGraph: cycle removal (ovl_remove_cycles, host) and the string pipeline's
- *    transitive reduction (ovl_transitive_reduce, device; overlapGraphs.py:235-303).
+ *    transitive reduction (ovl_transitive_reduce, device; overlapGraphs.py:235-303), and the unitig pipeline's
+ *    reachability reduction (ovl_reach_reduce, device; overlapGraphs.py:354-367).
  */
 #ifndef OVL_H
 #define OVL_H
@@ -321,6 +322,35 @@ int ovl_transitive_reduce(ovl_ctx* ctx, const int64_t* off, const int32_t* head,
 int ovl_transitive_reduce_host(const int64_t* off, const int32_t* head, const int64_t* weight, int32_t n_nodes,
                                uint8_t* reduced, int64_t* n_reduced);
 int ovl_last_transitive(const ovl_ctx* ctx, int32_t* window_nodes, int32_t* passes, int64_t* two_hop_steps);
+
+/*
+ * Reachability reduction of overlapGraphs.py:354-367 (transitive_reduction2) on the context's first device.
+ * Replaces one nx.has_path search per ordered pair of successors of every node.  The graph is a CSR without
+ * weights: node order, adjacency order; self-loops and cycles are allowed.  With R[u][x] true iff the graph has a
+ * path of at least one edge from u to x, reduced[e] (capacity off[n_nodes]) = 1 iff the reference removes edge
+ * e = (v, w):
+ *   some u that stands before w in v's successor order has R[u][w].
+ * The searches run on the unmodified graph, so the result does not depend on the visiting order; a node's first
+ * successor is never removed.  A row that lists a head twice (no DiGraph has one) gets the positional rule
+ * literally: an earlier equal entry removes the later one only when R[w][w].
+ * closure, when not NULL, receives R as n_nodes rows of ceil(n_nodes / 64) uint64 words: bit x of row u is bit
+ * x & 63 of word x >> 6, bits at and above n_nodes are zero.
+ * Every argument is checked on the host before anything is launched or written: OVL_E_ARG for null pointers, a
+ * negative n_nodes, off[0] != 0 or an off that decreases; OVL_E_INDEX for a head outside [0, n_nodes); OVL_E_OOM
+ * when the n_nodes^2 / 8-byte matrix cannot be allocated.  The matrix is closed by blocked Warshall over pivot
+ * blocks of 64 nodes, 2 * ceil(n_nodes / 64) + 2 launches on one stream whatever the graph's diameter; the marking
+ * holds a window of the rows' columns in registers and takes several passes over wider rows (OVL_REACH_WINDOW at
+ * context creation lowers the window's bits, for tests).  With ovl_set_timing on, ovl_last_timing reports the
+ * launches and the call.
+ * ovl_reach_reduce_host: the same checks and results on one host thread (row-OR Warshall over the same bit
+ * matrix), with no context and no GPU -- the small-graph path and the baseline the device call is measured against.
+ * ovl_last_reach: the words per row, the pivot blocks and the marking window's bits of the last ovl_reach_reduce.
+ */
+int ovl_reach_reduce(ovl_ctx* ctx, const int64_t* off, const int32_t* head, int32_t n_nodes, uint8_t* reduced,
+                     int64_t* n_reduced, uint64_t* closure);
+int ovl_reach_reduce_host(const int64_t* off, const int32_t* head, int32_t n_nodes, uint8_t* reduced,
+                          int64_t* n_reduced, uint64_t* closure);
+int ovl_last_reach(const ovl_ctx* ctx, int32_t* words_per_row, int32_t* pivot_blocks, int32_t* window_bits);
 
 #ifdef __cplusplus
 }
