@@ -1,8 +1,8 @@
 // ovl_ctx.h — internal header of the C ABI of include/ovl.h on top of the gfx950 kernels: the context and
 // per-device state, and the functions that cross the host files ovl_ctx.cpp (contexts, devices, pinned memory),
 // ovl_plan.cpp (planner, kernel launch), ovl_pipeline.cpp (host-array pipeline), ovl_reads.cpp (read upload),
-// ovl_cand.cpp (candidate lists, resident grid), ovl_local_api.cpp (single alignments) and the graph stages
-// ovl_reduce_api.cpp / ovl_reach_api.cpp.
+// ovl_cand.cpp (candidate lists, resident grid), ovl_local_api.cpp (single alignments), ovl_depth_api.cpp (read
+// depth) and the graph stages ovl_reduce_api.cpp / ovl_reach_api.cpp.
 //
 // A context (ovl_ctx) drives one or more HIP devices from one host thread.  Each
 // device (Dev) owns: a compute stream and two copy streams (H2D, D2H), its copy
@@ -134,6 +134,8 @@ struct Knobs {
                                   // kernel (0: none; tests reach slab reuse with a handful of queries)
     int32_t tr_window = 0;        // OVL_TR_WINDOW: entries of a node's out-row held in LDS per pass of
                                   // ovl_transitive_reduce (0: kReduceWindow; tests force several passes)
+    int32_t read_best_chunk = 0;  // OVL_READ_BEST_CHUNK: contigs per launch of ovl_read_best's score pass (0: what
+                                  // the tile budget allows; tests force several chunks)
     int32_t reach_window = 0;     // OVL_REACH_WINDOW: columns (bits) of the reachability rows that ovl_reach_reduce's
                                   // marking holds in registers per pass (0: 16,384; tests force several passes)
     int32_t pack_direct_pct = 18; // OVL_PACK_DIRECT_PCT: packed calls into pinned arrays store this share of the
@@ -232,6 +234,10 @@ struct Dev {
     // reachability reduction (ovl_reach_api.cpp): the CSR, the node order, the bit matrix, the pivot rows, the mask
     DevBuf rc_off, rc_head, rc_order, rc_matrix, rc_pivot, rc_out;
     hipEvent_t rc_ev[2] = {};  // timing on: around all of a call's launches
+    // read depth (ovl_depth_api.cpp): the upload block (padded reads, lengths, contigs, their offsets and lengths),
+    // a chunk's score / cell tile, the per-read results and the tie bits
+    DevBuf rb_in, rb_tile, rb_res, rb_bits;
+    hipEvent_t rb_ev[2] = {};  // timing on: around the score pass and its folds
     // host-array pipeline: events per slot and pinned staging (slots x cap pairs x {a, b} / {score, end})
     hipEvent_t ev_k[kSlots] = {};
     int32_t* st_in = nullptr;
@@ -314,6 +320,8 @@ struct ovl_ctx {
     int32_t x_tr_window = 0, x_tr_passes = 0;                   // ovl_last_transitive
     int64_t x_tr_steps = 0;
     int32_t x_rc_words = 0, x_rc_blocks = 0, x_rc_window = 0;   // ovl_last_reach
+    int64_t x_rb_lane = 0, x_rb_fallback = 0;                   // ovl_last_read_best
+    int32_t x_rb_launches = 0;
 };
 
 int fail(const ovl_ctx* c, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));

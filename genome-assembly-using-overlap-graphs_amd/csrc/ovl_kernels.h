@@ -190,6 +190,34 @@ struct OvlLocalBatchArgs {
 extern "C" hipError_t ovl_launch_local_batch(const OvlLocalBatchArgs* a, int32_t waves, uint32_t lds_row_bytes,
                                              hipStream_t stream);
 
+// lane-per-read local alignment scores (ovl_local_lane.hip): reads is pitch rows of `rows` symbols (0 .. 254, 255
+// beyond the read's r_len; pitch a multiple of 64, 16-byte aligned), contigs the renumbered contig symbols with every
+// c_off a multiple of four and readable up to the next multiple of four past its end.  A launch of `groups` =
+// pitch / 64 by `split` one-wavefront blocks scores contigs [c_lo, c_hi) and stores tile_score / tile_end
+// [(c - c_lo) * pitch + read]: the score and, when it is positive, end_i << 20 | end_j (end_j counted from the
+// contig's first column).  Needs mismatch <= 0, indel <= 0, match * rows < 2^23, contigs shorter than 2^20.
+// ovl_launch_read_best_fold then folds that tile into the per-read results (first < 0: no contig seen yet) and,
+// when tie_bits is not NULL, the rows of `words` = ceil(n_contigs / 32) bit words; c_lo must be a multiple of 32.
+struct OvlLocalLaneArgs {
+    const uint8_t* reads;
+    const int32_t* r_len;
+    const uint8_t* contigs;
+    const int64_t* c_off;
+    const int32_t* c_len;
+    int64_t pitch;
+    int32_t c_lo, c_hi;
+    int32_t read_length;
+    int32_t match, mismatch, indel;
+    int32_t* tile_score;
+    uint32_t* tile_end;
+};
+constexpr int32_t kLocalLaneMaxRows = 128;
+extern "C" hipError_t ovl_launch_local_lane(const OvlLocalLaneArgs* a, int32_t rows, int32_t groups, int32_t split,
+                                            hipStream_t stream);
+extern "C" hipError_t ovl_launch_read_best_fold(const OvlLocalLaneArgs* a, int32_t n_reads, int32_t words,
+                                                int32_t* best, int32_t* first, int32_t* n_best, uint32_t* cell,
+                                                uint32_t* tie_bits, hipStream_t stream);
+
 // transitive reduction of an overlap graph (ovl_reduce.hip): `blocks` persistent workgroups of kReduceThreads take
 // order[0 .. n_order) -- the nodes with out-edges, heaviest first by two-hop work -- from *counter (zeroed by the
 // caller).  edge[e] = {head, weight} of CSR edge e (heads validated in [0, n_nodes), |weight| < 2^30); a window of

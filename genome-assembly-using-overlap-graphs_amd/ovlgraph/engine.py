@@ -128,6 +128,38 @@ def reach_reduce_host(off, heads, closure: bool = False):
     return (mask, matrix) if closure else mask
 
 
+def _read_best_arrays(reads, contigs, scores: bool):
+    """Reads and contigs as the C ABI of ovl_read_best takes them (one symbol map for both), with the arrays to
+    receive the results: five int32 arrays over the reads, the tie bits and (``scores``) the score matrix."""
+    reads, contigs = list(reads), list(contigs)
+    R, C = len(reads), len(contigs)
+    buf, offs = encode_reads(reads + contigs)
+    r_off = np.ascontiguousarray(offs[: R + 1])
+    c_off = np.ascontiguousarray(offs[R:])
+    outs = [np.zeros(max(R, 1), dtype=np.int32) for _ in range(5)]
+    bits = np.zeros((max(R, 1), max((C + 31) // 32, 1)), dtype=np.uint32)
+    sc = np.zeros((max(R, 1), max(C, 1)), dtype=np.int32) if scores else None
+    return R, C, buf, r_off, c_off, outs, bits, sc
+
+
+def _read_best_result(R: int, C: int, outs, bits, sc) -> Dict[str, np.ndarray]:
+    res = dict(zip(("best_score", "first_best", "n_best", "start", "end"), (o[:R] for o in outs)))
+    res["tie_bits"] = bits[:R, : (C + 31) // 32]
+    if sc is not None:
+        res["scores"] = sc[:R, :C]
+    return res
+
+
+def read_best_host(reads, contigs, read_length: int, match: int = 10, mismatch: int = -1, indel: int = -1,
+                   scores: bool = False) -> Dict[str, np.ndarray]:
+    """``OverlapEngine.read_best`` on one host thread (ovl_read_best_host): no context, no GPU."""
+    R, C, buf, r_off, c_off, outs, bits, sc = _read_best_arrays(reads, contigs, scores)
+    check(_lib.load().ovl_read_best_host(_ptr(buf), _ptr(r_off), R, _ptr(buf), _ptr(c_off), C, int(read_length),
+                                         int(match), int(mismatch), int(indel), *[_ptr(o) for o in outs], _ptr(bits),
+                                         _ptr(sc) if scores else None))
+    return _read_best_result(R, C, outs, bits, sc)
+
+
 def host_pool() -> Dict[str, int]:
     """The host thread pool's plan, recounted now (ovl_host_pool): {threads, sharers, cpus, packed}."""
     v = [ctypes.c_int32() for _ in range(4)]
@@ -435,6 +467,27 @@ class OverlapEngine:
         v = [ctypes.c_int32() for _ in range(3)]
         check(self._L.ovl_last_local_batch(self._ctx, *[ctypes.byref(x) for x in v]), self._ctx)
         return dict(zip(("batched", "single", "waves"), (x.value for x in v)))
+
+    def read_best(self, reads, contigs, read_length: int, match: int = 10, mismatch: int = -1, indel: int = -1,
+                  scores: bool = False) -> Dict[str, np.ndarray]:
+        """Every read against every contig by ``align_read_or_contig_to_reference`` (ovl_read_best), reduced per
+        read: ``best_score``, ``first_best`` (the first contig position that attains it, -1 without contigs),
+        ``n_best``, ``start`` and ``end`` (the aligned stretch on that contig) as int32 arrays, ``tie_bits``
+        (reads x ceil(contigs / 32) uint32: bit c of row r set iff contig c attains the best score) and, with
+        ``scores=True``, the reads x contigs score matrix."""
+        R, C, buf, r_off, c_off, outs, bits, sc = _read_best_arrays(reads, contigs, scores)
+        check(self._L.ovl_read_best(self._ctx, _ptr(buf), _ptr(r_off), R, _ptr(buf), _ptr(c_off), C,
+                                    int(read_length), int(match), int(mismatch), int(indel),
+                                    *[_ptr(o) for o in outs], _ptr(bits), _ptr(sc) if scores else None), self._ctx)
+        return _read_best_result(R, C, outs, bits, sc)
+
+    def last_read_best(self) -> Dict[str, int]:
+        """{lane_pairs, fallback_pairs, launches} of the last ``read_best`` (ovl_last_read_best): the (read, contig)
+        pairs the lane-per-read kernel scored, those that went through the existing local-alignment kernels, and
+        the lane kernel's launches."""
+        a, b, n = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32()
+        check(self._L.ovl_last_read_best(self._ctx, ctypes.byref(a), ctypes.byref(b), ctypes.byref(n)), self._ctx)
+        return {"lane_pairs": a.value, "fallback_pairs": b.value, "launches": n.value}
 
     # ---------------------------------------------------------------- graph stages
     def transitive_reduce(self, off, heads, weights) -> np.ndarray:

@@ -352,6 +352,46 @@ int ovl_reach_reduce_host(const int64_t* off, const int32_t* head, int32_t n_nod
                           int64_t* n_reduced, uint64_t* closure);
 int ovl_last_reach(const ovl_ctx* ctx, int32_t* words_per_row, int32_t* pivot_blocks, int32_t* window_bits);
 
+/*
+ * The selection step of the reference's read-depth coverage (plots.py:115-135, plot_reconstructed_coverage) on the
+ * context's first device: every read against every contig.  Read r is reads[r_off[r] .. r_off[r+1]), contig c is
+ * contigs[c_off[c] .. c_off[c+1]); repeated contigs are separate positions.  For each pair the rule is
+ * align_read_or_contig_to_reference (aligners.py:170-202): a read with 0 < len < read_length is aligned to the
+ * contig's last len bases (the whole contig when it is shorter), every other read to the whole contig, and a read
+ * shorter than read_length has (contig length - len) added to its positions.  Per read, over the contigs in order:
+ *   best_score[r]  the maximum score,
+ *   first_best[r]  the smallest c that attains it (-1 when n_contigs == 0, with zeros elsewhere),
+ *   n_best[r]      how many contigs attain it,
+ *   best_start[r], best_end[r]  the start and end positions of the alignment to contig first_best[r], in that
+ *                  contig's coordinates with the shift applied (local_alignment's start_pos and end_pos),
+ *   tie_bits       (may be NULL) n_reads rows of ceil(n_contigs / 32) words: bit c & 31 of word c >> 5 of row r is
+ *                  set iff contig c attains best_score[r],
+ *   scores         (may be NULL; tests and small inputs) n_reads x n_contigs scores, row-major.
+ * Every argument is checked before anything runs or is written: OVL_E_ARG for null pointers, negative counts or
+ * read_length and offsets that decrease; OVL_E_UNSUPPORTED beyond ovl_local_align's limits (lengths < 2^20,
+ * match * min(n, m) < 2^24) or when the contigs together reach 2^31 bases.
+ * The scores come from a kernel in which one lane owns one read and a wavefront's 64 reads sweep a contig column by
+ * column with the DP column in registers; it takes reads of up to 128 bases under scorings with mismatch <= 0,
+ * indel <= 0, match < 65536 and at most 255 distinct symbols.  Every other (read, contig) pair goes through
+ * ovl_local_align_batch inside the same call.  The scores' tile in device memory is bounded by a chunk of contigs
+ * (OVL_READ_BEST_CHUNK at context creation sets the contigs per chunk, for tests) and folded into the per-read
+ * results on the device.  The start positions come from a second pass of n_reads items through
+ * ovl_local_align_batch, each read against its first best contig.  With ovl_set_timing on, ovl_last_timing reports
+ * the score pass (the lane kernel's launches and their folds) and the call.
+ * ovl_read_best_host: the same checks and results on one host thread, with no context and no GPU.
+ * ovl_last_read_best: the pairs of the last ovl_read_best that took the lane kernel, those that took the existing
+ * kernels, and the lane kernel's launches.
+ */
+int ovl_read_best(ovl_ctx* ctx, const uint8_t* reads, const int64_t* r_off, int32_t n_reads, const uint8_t* contigs,
+                  const int64_t* c_off, int32_t n_contigs, int32_t read_length, int32_t match, int32_t mismatch,
+                  int64_t indel, int32_t* best_score, int32_t* first_best, int32_t* n_best, int32_t* best_start,
+                  int32_t* best_end, uint32_t* tie_bits, int32_t* scores);
+int ovl_read_best_host(const uint8_t* reads, const int64_t* r_off, int32_t n_reads, const uint8_t* contigs,
+                       const int64_t* c_off, int32_t n_contigs, int32_t read_length, int32_t match, int32_t mismatch,
+                       int64_t indel, int32_t* best_score, int32_t* first_best, int32_t* n_best, int32_t* best_start,
+                       int32_t* best_end, uint32_t* tie_bits, int32_t* scores);
+int ovl_last_read_best(const ovl_ctx* ctx, int64_t* lane_pairs, int64_t* fallback_pairs, int32_t* launches);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,260 @@
+// read_best_host_check.cpp — the host code of csrc/ovl_depth_api.cpp (the argument checks and ovl_read_best_host)
+// as a stand-alone program, for a sanitizer build on a machine without a GPU:
+//
+//     make -C genome-assembly-using-overlap-graphs_amd/csrc read-best-host-check
+//
+// compiles this file and ovl_depth_api.cpp with -fsanitize=address,undefined (host side) and runs the result.  It
+// runs hand cases with known answers, random reads and contigs against a plain full-table restatement of
+// aligners.py:85-202, and every error case (outputs untouched).  The device call is linked but never made: its
+// launches, the batched alignment and the context helpers are stubs here.
+#include <cstdarg>
+
+#include "ovl_ctx.h"
+
+thread_local std::string g_err;
+
+int fail(const ovl_ctx*, int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    g_err = buf;
+    return code;
+}
+int fail(const Dev*, int code, const char* fmt, ...) {
+    g_err = fmt;
+    return code;
+}
+void quiet(ovl_ctx*) {}
+extern "C" hipError_t ovl_launch_local_lane(const OvlLocalLaneArgs*, int32_t, int32_t, int32_t, hipStream_t) {
+    return hipErrorNotSupported;
+}
+extern "C" hipError_t ovl_launch_read_best_fold(const OvlLocalLaneArgs*, int32_t, int32_t, int32_t*, int32_t*,
+                                                int32_t*, uint32_t*, uint32_t*, hipStream_t) {
+    return hipErrorNotSupported;
+}
+extern "C" int ovl_local_align_batch(ovl_ctx*, const uint8_t*, const int64_t*, int32_t, const uint8_t*, int32_t,
+                                     const int32_t*, const int32_t*, int32_t, int32_t, int64_t, int32_t*, int32_t*,
+                                     int32_t*, int32_t*, int32_t*, int8_t*, const int64_t*, int64_t*) {
+    return OVL_E_UNSUPPORTED;
+}
+
+static int g_failed = 0;
+#define EXPECT(cond)                                                        \
+    do {                                                                    \
+        if (!(cond)) {                                                      \
+            fprintf(stderr, "%s:%d: %s failed\n", __FILE__, __LINE__, #cond); \
+            ++g_failed;                                                     \
+        }                                                                   \
+    } while (0)
+
+struct Seqs {
+    std::vector<uint8_t> bytes;
+    std::vector<int64_t> off{0};
+    void add(const std::string& s) {
+        bytes.insert(bytes.end(), s.begin(), s.end());
+        off.push_back((int64_t)bytes.size());
+    }
+    int32_t n() const { return (int32_t)off.size() - 1; }
+    std::string at(int32_t k) const { return std::string(bytes.begin() + off[k], bytes.begin() + off[k + 1]); }
+    const uint8_t* data() const { return bytes.empty() ? nullptr : bytes.data(); }
+};
+
+struct Triple {
+    int64_t score, start, end;
+};
+
+// aligners.py:85-167 on full tables
+static Triple local_plain(const std::string& q, const std::string& t, int64_t match, int64_t mismatch, int64_t indel) {
+    const size_t n = q.size(), m = t.size();
+    std::vector<std::vector<int64_t>> dp(n + 1, std::vector<int64_t>(m + 1, 0));
+    std::vector<std::vector<int>> tb(n + 1, std::vector<int>(m + 1, 0));
+    int64_t best = 0;
+    size_t bi = 0, bj = 0;
+    for (size_t i = 1; i <= n; ++i)
+        for (size_t j = 1; j <= m; ++j) {
+            const int64_t d = dp[i - 1][j - 1] + (q[i - 1] == t[j - 1] ? match : mismatch);
+            const int64_t u = dp[i - 1][j] + indel, l = dp[i][j - 1] + indel;
+            if (d >= u && d >= l && d >= 0) { dp[i][j] = d; tb[i][j] = 1; }
+            else if (u >= l && u >= 0) { dp[i][j] = u; tb[i][j] = 2; }
+            else if (l >= 0) { dp[i][j] = l; tb[i][j] = 3; }
+            if (dp[i][j] > best) { best = dp[i][j]; bi = i; bj = j; }
+        }
+    size_t i = bi, j = bj;
+    while (i > 0 && j > 0 && dp[i][j] > 0) {
+        if (tb[i][j] == 1) { --i; --j; }
+        else if (tb[i][j] == 2) --i;
+        else if (tb[i][j] == 3) --j;
+        else break;
+    }
+    return {best, (int64_t)j, (int64_t)bj};
+}
+
+// aligners.py:170-202
+static Triple align_plain(const std::string& q, const std::string& t, int32_t read_length, int64_t match,
+                          int64_t mismatch, int64_t indel) {
+    const int64_t L = (int64_t)q.size(), m = (int64_t)t.size();
+    if (L < read_length) {
+        const std::string tail = (L > 0 && L < m) ? t.substr((size_t)(m - L)) : t;  // Python's t[-L:]
+        Triple r = local_plain(q, tail, match, mismatch, indel);
+        r.start += m - L;
+        r.end += m - L;
+        return r;
+    }
+    return local_plain(q, t, match, mismatch, indel);
+}
+
+struct Out {
+    std::vector<int32_t> best, first, nb, start, end, scores;
+    std::vector<uint32_t> bits;
+    Out(int32_t R, int32_t C)
+        : best(R + 1, 77), first(R + 1, 77), nb(R + 1, 77), start(R + 1, 77), end(R + 1, 77),
+          scores((size_t)R * C + 1, 77), bits((size_t)R * ((C + 31) / 32) + 1, 77u) {}
+};
+
+static int run_host(const Seqs& rd, const Seqs& ct, int32_t read_length, int32_t match, int32_t mismatch,
+                    int64_t indel, Out& o) {
+    return ovl_read_best_host(rd.data(), rd.off.data(), rd.n(), ct.data(), ct.off.data(), ct.n(), read_length, match,
+                              mismatch, indel, o.best.data(), o.first.data(), o.nb.data(), o.start.data(),
+                              o.end.data(), o.bits.data(), o.scores.data());
+}
+
+static void expect_matches_plain(const Seqs& rd, const Seqs& ct, int32_t read_length, int32_t match, int32_t mismatch,
+                                 int64_t indel) {
+    const int32_t R = rd.n(), C = ct.n(), words = (C + 31) / 32;
+    Out o(R, C);
+    EXPECT(run_host(rd, ct, read_length, match, mismatch, indel, o) == OVL_OK);
+    for (int32_t r = 0; r < R; ++r) {
+        int64_t best = 0;
+        int32_t first = -1, nb = 0;
+        Triple ft{0, 0, 0};
+        std::vector<uint32_t> bits((size_t)words, 0);
+        for (int32_t c = 0; c < C; ++c) {
+            const Triple t = align_plain(rd.at(r), ct.at(c), read_length, match, mismatch, indel);
+            EXPECT(o.scores[(size_t)r * C + c] == t.score);
+            if (first < 0 || t.score > best) {
+                best = t.score; first = c; nb = 1; ft = t;
+                std::fill(bits.begin(), bits.end(), 0u);
+            } else if (t.score == best) {
+                ++nb;
+            } else {
+                continue;
+            }
+            bits[(size_t)(c >> 5)] |= 1u << (c & 31);
+        }
+        EXPECT(o.best[r] == best && o.first[r] == first && o.nb[r] == nb);
+        EXPECT(o.start[r] == ft.start && o.end[r] == ft.end);
+        for (int32_t w = 0; w < words; ++w) EXPECT(o.bits[(size_t)r * words + w] == bits[(size_t)w]);
+    }
+    // the guard elements past the arrays' ends are untouched
+    EXPECT(o.best[R] == 77 && o.first[R] == 77 && o.nb[R] == 77 && o.start[R] == 77 && o.end[R] == 77);
+    EXPECT(o.scores[(size_t)R * C] == 77 && o.bits[(size_t)R * words] == 77u);
+}
+
+static std::string rand_seq(uint32_t& state, int n, int alphabet) {
+    std::string s;
+    for (int i = 0; i < n; ++i) {
+        state = state * 1664525u + 1013904223u;
+        s.push_back("ACGT"[(state >> 24) % (uint32_t)alphabet]);
+    }
+    return s;
+}
+
+int main() {
+    // hand cases: a gap of three, a tail window, ties over a repeated contig, an empty read and an empty contig
+    {
+        Seqs rd, ct;
+        rd.add("ACGTACGT");
+        rd.add("GGA");
+        rd.add("");
+        ct.add("TTACGTTTTACGTTT");
+        ct.add("CCCCGGA");
+        ct.add("");
+        ct.add("CCCCGGA");
+        Out o(3, 4);
+        EXPECT(run_host(rd, ct, 8, 10, -1, -1, o) == OVL_OK);
+        // ACGT---ACGT: 8 matches and 3 gaps on contig 0, columns 3 .. 13
+        EXPECT(o.best[0] == 77 && o.first[0] == 0 && o.nb[0] == 1 && o.start[0] == 2 && o.end[0] == 13);
+        // GGA is shorter than read_length: the last 3 bases of each contig, found whole on contigs 1 and 3
+        EXPECT(o.best[1] == 30 && o.first[1] == 1 && o.nb[1] == 2 && o.start[1] == 4 && o.end[1] == 7);
+        EXPECT(o.bits[1] == 0xAu);
+        // the empty read scores 0 everywhere and sits at the first contig's end
+        EXPECT(o.best[2] == 0 && o.first[2] == 0 && o.nb[2] == 4 && o.start[2] == 15 && o.end[2] == 15);
+        EXPECT(o.bits[2] == 0xFu);
+        expect_matches_plain(rd, ct, 8, 10, -1, -1);
+    }
+    // random inputs over small alphabets (many ties), contig counts across the 32-bit word boundary, four scorings
+    const int32_t scorings[4][3] = {{10, -1, -1}, {2, -3, -2}, {1, 0, -1}, {5, -4, -100000}};
+    uint32_t state = 12345;
+    for (int round = 0; round < 8; ++round) {
+        Seqs rd, ct;
+        const int32_t C = round < 4 ? 5 : (round == 4 ? 32 : (round == 5 ? 33 : 65));
+        const int alphabet = 2 + round % 3;
+        for (int32_t c = 0; c < C; ++c) {
+            state = state * 1664525u + 1013904223u;
+            ct.add(rand_seq(state, (int)((state >> 20) % 40), alphabet));
+        }
+        for (int32_t r = 0; r < 12; ++r) {
+            state = state * 1664525u + 1013904223u;
+            rd.add(rand_seq(state, (int)((state >> 20) % 24), alphabet));
+        }
+        rd.add(ct.at(0));
+        const int32_t* s = scorings[round % 4];
+        expect_matches_plain(rd, ct, 12, s[0], s[1], s[2]);
+    }
+    // no contigs, no reads
+    {
+        Seqs rd, ct;
+        rd.add("ACGT");
+        Out o(1, 0);
+        EXPECT(run_host(rd, ct, 4, 10, -1, -1, o) == OVL_OK);
+        EXPECT(o.best[0] == 0 && o.first[0] == -1 && o.nb[0] == 0 && o.start[0] == 0 && o.end[0] == 0);
+        EXPECT(o.best[1] == 77);
+        Seqs none;
+        ct.add("ACGT");
+        Out e(0, 1);
+        EXPECT(ovl_read_best_host(nullptr, nullptr, 0, ct.data(), ct.off.data(), 1, 4, 10, -1, -1, nullptr, nullptr,
+                                  nullptr, nullptr, nullptr, nullptr, nullptr) == OVL_OK);
+        EXPECT(run_host(none, ct, 4, 10, -1, -1, e) == OVL_OK && e.best[0] == 77);
+    }
+    // argument errors: nothing is written
+    {
+        Seqs rd, ct;
+        rd.add("ACGT");
+        ct.add("ACGT");
+        Out o(1, 1);
+        auto untouched = [&] {
+            return o.best[0] == 77 && o.first[0] == 77 && o.nb[0] == 77 && o.start[0] == 77 && o.end[0] == 77 &&
+                   o.scores[0] == 77 && o.bits[0] == 77u;
+        };
+        auto call = [&](const uint8_t* r, const int64_t* ro, int32_t nr, const uint8_t* c, const int64_t* co,
+                        int32_t nc, int32_t rl, int32_t match, int32_t* best) {
+            return ovl_read_best_host(r, ro, nr, c, co, nc, rl, match, -1, -1, best, o.first.data(), o.nb.data(),
+                                      o.start.data(), o.end.data(), o.bits.data(), o.scores.data());
+        };
+        const int64_t bad_off[2] = {4, 0};
+        EXPECT(call(rd.data(), rd.off.data(), -1, ct.data(), ct.off.data(), 1, 4, 10, o.best.data()) == OVL_E_ARG);
+        EXPECT(call(rd.data(), rd.off.data(), 1, ct.data(), ct.off.data(), -1, 4, 10, o.best.data()) == OVL_E_ARG);
+        EXPECT(call(rd.data(), rd.off.data(), 1, ct.data(), ct.off.data(), 1, -1, 10, o.best.data()) == OVL_E_ARG);
+        EXPECT(call(rd.data(), nullptr, 1, ct.data(), ct.off.data(), 1, 4, 10, o.best.data()) == OVL_E_ARG);
+        EXPECT(call(rd.data(), rd.off.data(), 1, ct.data(), nullptr, 1, 4, 10, o.best.data()) == OVL_E_ARG);
+        EXPECT(call(nullptr, rd.off.data(), 1, ct.data(), ct.off.data(), 1, 4, 10, o.best.data()) == OVL_E_ARG);
+        EXPECT(call(rd.data(), rd.off.data(), 1, nullptr, ct.off.data(), 1, 4, 10, o.best.data()) == OVL_E_ARG);
+        EXPECT(call(rd.data(), bad_off, 1, ct.data(), ct.off.data(), 1, 4, 10, o.best.data()) == OVL_E_ARG);
+        EXPECT(call(rd.data(), rd.off.data(), 1, ct.data(), bad_off, 1, 4, 10, o.best.data()) == OVL_E_ARG);
+        EXPECT(call(rd.data(), rd.off.data(), 1, ct.data(), ct.off.data(), 1, 4, 10, nullptr) == OVL_E_ARG);
+        EXPECT(call(rd.data(), rd.off.data(), 1, ct.data(), ct.off.data(), 1, 4, 1 << 22, o.best.data()) ==
+               OVL_E_UNSUPPORTED);
+        const int64_t long_off[2] = {0, int64_t(1) << 20};  // (the bytes are never read: the check comes first)
+        EXPECT(call(rd.data(), long_off, 1, ct.data(), ct.off.data(), 1, 4, 10, o.best.data()) == OVL_E_UNSUPPORTED);
+        EXPECT(untouched());
+        EXPECT(!g_err.empty());
+    }
+    if (g_failed) {
+        fprintf(stderr, "read_best_host_check: %d checks failed\n", g_failed);
+        return 1;
+    }
+    printf("read_best_host_check: ok\n");
+    return 0;
+}
