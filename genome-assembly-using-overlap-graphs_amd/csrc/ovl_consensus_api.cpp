@@ -1,0 +1,393 @@
+// ovl_consensus_api.cpp — consensus polishing: every placed read is aligned to its contig as
+// align_read_or_contig_to_reference does it (aligners.py:170-202, the window rule of ovl_ctx.h), the walks are piled
+// up into six vote channels per contig base, and every base with enough votes is called by majority.  The host form
+// (ovl_consensus_host) and the device call (ovl_consensus: the batch kernel's walks stay in device memory and
+// ovl_consensus.hip piles them up and votes there).  The pileup routine and the vote rule below are the one
+// statement both forms share.
+#include "ovl_ctx.h"
+
+namespace {
+
+constexpr int64_t kOpsBudget = int64_t(256) << 20;  // the walks of one chunk of reads (bytes of Dev::lb_ops)
+
+inline int32_t channel(uint8_t b) { return b == 'A' ? 0 : (b == 'C' ? 1 : (b == 'G' ? 2 : (b == 'T' ? 3 : -1))); }
+
+template <typename C>
+int check_consensus(const C* c, const uint8_t* reads, const int64_t* r_off, int32_t n_reads, const uint8_t* contigs,
+                    const int64_t* c_off, int32_t n_contigs, const int32_t* place, int32_t read_length, int32_t match,
+                    int32_t min_depth, const uint8_t* called, const int64_t* n_changed, const int64_t* n_other,
+                    int64_t* total) {
+    if (n_reads < 0 || n_contigs < 0 || read_length < 0) return fail(c, OVL_E_ARG, "negative count or read_length");
+    if (min_depth < 1) return fail(c, OVL_E_ARG, "min_depth %d < 1", min_depth);
+    if ((n_reads > 0 && (!r_off || !place)) || (n_contigs > 0 && !c_off))
+        return fail(c, OVL_E_ARG, "NULL offsets or placement");
+    if (!n_changed || !n_other) return fail(c, OVL_E_ARG, "NULL output pointer");
+    if (n_reads > 0 && r_off[0] < 0) return fail(c, OVL_E_ARG, "r_off[0] < 0");
+    if (n_contigs > 0 && c_off[0] < 0) return fail(c, OVL_E_ARG, "c_off[0] < 0");
+    int64_t max_n = 0, max_m = 0;
+    for (int32_t r = 0; r < n_reads; ++r) {
+        const int64_t n = r_off[r + 1] - r_off[r];
+        if (n < 0) return fail(c, OVL_E_ARG, "read %d: offsets decrease", r);
+        max_n = std::max(max_n, n);
+    }
+    for (int32_t k = 0; k < n_contigs; ++k) {
+        const int64_t m = c_off[k + 1] - c_off[k];
+        if (m < 0) return fail(c, OVL_E_ARG, "contig %d: offsets decrease", k);
+        max_m = std::max(max_m, m);
+    }
+    *total = n_contigs > 0 ? c_off[n_contigs] - c_off[0] : 0;
+    if ((max_n > 0 && !reads) || (max_m > 0 && !contigs)) return fail(c, OVL_E_ARG, "NULL sequence");
+    if (*total > 0 && !called) return fail(c, OVL_E_ARG, "NULL output pointer");
+    for (int32_t r = 0; r < n_reads; ++r)
+        if (place[r] < -1 || place[r] >= n_contigs)
+            return fail(c, OVL_E_INDEX, "read %d placed on contig %d outside [-1, %d)", r, place[r], n_contigs);
+    if (*total >= (int64_t(1) << 31))
+        return fail(c, OVL_E_UNSUPPORTED, "consensus: the contigs together must stay below 2^31 bases");
+    for (int32_t r = 0; r < n_reads; ++r) {
+        if (place[r] < 0) continue;
+        const int64_t n = r_off[r + 1] - r_off[r], m = c_off[place[r] + 1] - c_off[place[r]];
+        const int64_t wl = window_of(n, m, read_length).len;
+        if (n > 0xFFFFF || m > 0xFFFFF || std::max<int64_t>(0, match) * std::min(n, wl) >= (int64_t(1) << 24))
+            return fail(c, OVL_E_UNSUPPORTED,
+                        "consensus, read %d: lengths < 2^20 and match * min(n, m) < 2^24 required", r);
+    }
+    return OVL_OK;
+}
+
+// scores at or below -2^40 all mean "never taken" for cells below 2^24, and keep int64 sums far from overflow
+inline int64_t clamp_score(int64_t v) {
+    const int64_t lim = int64_t(1) << 40;
+    return v < -lim ? -lim : (v > lim ? lim : v);
+}
+
+struct Walk {
+    int64_t score = 0;
+    int32_t bi = 0, bj = 0, sj = 0;  // the best cell and the column where the walk stops, window-relative
+};
+
+// aligners.py:106-161 over q[0..n) x t[0..m): the fill with its traceback table, the first strict maximum and the
+// walk from it, whose ops (1 diag, 2 up, 3 left) are left in `ops` in walk order
+Walk align_host(const uint8_t* q, int32_t n, const uint8_t* t, int32_t m, int64_t match, int64_t mismatch,
+                int64_t indel, std::vector<int8_t>& tb, std::vector<int64_t>& row, std::vector<int8_t>& ops) {
+    Walk w;
+    ops.clear();
+    const size_t pitch = (size_t)m + 1;
+    tb.assign(((size_t)n + 1) * pitch, 0);
+    row.assign(pitch, 0);
+    for (int32_t i = 1; i <= n; ++i) {
+        int64_t diag = 0, left = 0;
+        for (int32_t j = 1; j <= m; ++j) {
+            const int64_t upv = row[(size_t)j];
+            const int64_t d = diag + (q[i - 1] == t[j - 1] ? match : mismatch), u = upv + indel, l = left + indel;
+            int64_t v = 0;
+            int8_t op = 0;
+            if (d >= u && d >= l && d >= 0) { v = d; op = 1; }
+            else if (u >= l && u >= 0) { v = u; op = 2; }
+            else if (l >= 0) { v = l; op = 3; }
+            diag = upv;
+            row[(size_t)j] = left = v;
+            tb[(size_t)i * pitch + (size_t)j] = v > 0 ? op : 0;
+            if (v > w.score) { w.score = v; w.bi = i; w.bj = j; }
+        }
+    }
+    int32_t i = w.bi, j = w.bj;
+    while (i > 0 && j > 0) {
+        const int8_t op = tb[(size_t)i * pitch + (size_t)j];
+        if (op == 1) { --i; --j; }
+        else if (op == 2) --i;
+        else if (op == 3) --j;
+        else break;
+        ops.push_back(op);
+    }
+    w.sj = j;
+    return w;
+}
+
+// The pileup of one walk from cell (bi, bj): every op votes at the contig base of its cell's column (DP column j is
+// base col0 + j - 1) -- a diag in the channel of the read's byte (none for a byte outside ACGT: counted and
+// returned), a left in channel 4 (gap), an up in channel 5 (ins: the column at the left of the inserted base).
+// vote(k) receives the flat index k = base * 6 + channel.
+template <typename Vote>
+int64_t pile_ops(const int8_t* ops, int64_t cnt, const uint8_t* q, int32_t bi, int32_t bj, int64_t col0, Vote&& vote) {
+    int64_t other = 0;
+    int32_t i = bi, j = bj;
+    for (int64_t t = 0; t < cnt; ++t) {
+        const int64_t at = (col0 + j - 1) * 6;
+        if (ops[t] == 1) {
+            const int32_t ch = channel(q[i - 1]);
+            if (ch >= 0) vote(at + ch);
+            else ++other;
+            --i;
+            --j;
+        } else if (ops[t] == 2) {
+            vote(at + 5);
+            --i;
+        } else {
+            vote(at + 4);
+            --j;
+        }
+    }
+    return other;
+}
+
+// The call per contig base: with fewer than min_depth base votes it keeps its byte; else the largest of A, C, G, T
+// wins, a tie going to the contig's own byte when it is among the tied and else to the first in that order.
+inline uint8_t call_base(const int32_t* v, uint8_t own, int32_t min_depth) {
+    if ((int64_t)v[0] + v[1] + v[2] + v[3] < min_depth) return own;
+    const int32_t top = std::max(std::max(v[0], v[1]), std::max(v[2], v[3]));
+    const int32_t oc = channel(own);
+    if (oc >= 0 && v[oc] == top) return own;
+    return v[0] == top ? 'A' : (v[1] == top ? 'C' : (v[2] == top ? 'G' : 'T'));
+}
+
+void zero_aln(int32_t* aln, int32_t n_reads) {
+    if (aln) std::fill(aln, aln + (int64_t)n_reads * 3, 0);
+}
+
+}  // namespace
+
+OVL_API int ovl_consensus_host(const uint8_t* reads, const int64_t* r_off, int32_t n_reads, const uint8_t* contigs,
+                               const int64_t* c_off, int32_t n_contigs, const int32_t* place, int32_t read_length,
+                               int32_t match, int32_t mismatch, int64_t indel, int32_t min_depth, int32_t* counts,
+                               uint8_t* called, int64_t* n_changed, int64_t* n_other, int32_t* aln) {
+    const ovl_ctx* none = nullptr;
+    int64_t total = 0;
+    const int rc = check_consensus(none, reads, r_off, n_reads, contigs, c_off, n_contigs, place, read_length, match,
+                                   min_depth, called, n_changed, n_other, &total);
+    if (rc != OVL_OK) return rc;
+    zero_aln(aln, n_reads);
+    *n_changed = *n_other = 0;
+    try {
+        std::vector<int32_t> own_counts;
+        if (!counts) {
+            own_counts.assign((size_t)total * 6, 0);
+            counts = own_counts.data();
+        } else {
+            std::fill(counts, counts + total * 6, 0);
+        }
+        const int64_t ind = clamp_score(indel);
+        std::vector<int8_t> tb, ops;
+        std::vector<int64_t> row;
+        for (int32_t r = 0; r < n_reads; ++r) {
+            const int32_t f = place[r];
+            if (f < 0) continue;
+            const uint8_t* q = reads + r_off[r];
+            const int32_t L = (int32_t)(r_off[r + 1] - r_off[r]);
+            const Window w = window_of(L, c_off[f + 1] - c_off[f], read_length);
+            if (L == 0 || w.len == 0) continue;
+            const Walk a = align_host(q, L, contigs + c_off[f] + w.lo, w.len, match, mismatch, ind, tb, row, ops);
+            if (a.score <= 0) continue;
+            *n_other += pile_ops(ops.data(), (int64_t)ops.size(), q, a.bi, a.bj, (c_off[f] - c_off[0]) + w.lo,
+                                 [&](int64_t k) { ++counts[k]; });
+            if (aln) {
+                aln[3 * (int64_t)r] = (int32_t)a.score;
+                aln[3 * (int64_t)r + 1] = w.lo + a.sj;
+                aln[3 * (int64_t)r + 2] = w.lo + a.bj;
+            }
+        }
+        const uint8_t* ref = contigs + (n_contigs > 0 ? c_off[0] : 0);
+        for (int64_t b = 0; b < total; ++b) {
+            called[b] = call_base(counts + b * 6, ref[b], min_depth);
+            *n_changed += called[b] != ref[b];
+        }
+    } catch (const std::bad_alloc&) {
+        return fail(none, OVL_E_OOM, "no memory for the counts or a traceback table");
+    }
+    return OVL_OK;
+}
+
+OVL_API int ovl_consensus(ovl_ctx* ctx, const uint8_t* reads, const int64_t* r_off, int32_t n_reads,
+                          const uint8_t* contigs, const int64_t* c_off, int32_t n_contigs, const int32_t* place,
+                          int32_t read_length, int32_t match, int32_t mismatch, int64_t indel, int32_t min_depth,
+                          int32_t* counts, uint8_t* called, int64_t* n_changed, int64_t* n_other, int32_t* aln) {
+    if (!ctx) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
+    quiet(ctx);
+    Dev* c = ctx->devs[0];
+    DeviceGuard guard;
+    const auto t_call = std::chrono::steady_clock::now();
+    int64_t total = 0;
+    const int rc = check_consensus(c, reads, r_off, n_reads, contigs, c_off, n_contigs, place, read_length, match,
+                                   min_depth, called, n_changed, n_other, &total);
+    if (rc != OVL_OK) return rc;
+    zero_aln(aln, n_reads);
+    *n_changed = *n_other = 0;
+    ctx->x_cs_batch = ctx->x_cs_single = ctx->x_cs_ops = 0;
+    ctx->x_cs_launches = 0;
+    ctx->x_cs_ms[0] = ctx->x_cs_ms[1] = ctx->x_cs_ms[2] = 0.0;
+    ctx->t_kernel_ms = ctx->t_call_ms = 0.0;
+    if (total == 0) return OVL_OK;  // no base to vote on, and every window is empty
+    const uint8_t* ref = contigs + c_off[0];
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    HIPCHK(c, ensure(c->cs_ref, (size_t)total));
+    HIPCHK(c, ensure(c->cs_counts, sizeof(int32_t) * 6 * (size_t)total));
+    HIPCHK(c, ensure(c->cs_called, (size_t)total));
+    HIPCHK(c, ensure(c->cs_ctr, 32));
+    HIPCHK(c, hipMemcpyAsync(c->cs_ref.p, ref, (size_t)total, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemsetAsync(c->cs_counts.p, 0, sizeof(int32_t) * 6 * (size_t)total, s));
+    HIPCHK(c, hipMemsetAsync(c->cs_ctr.p, 0, 32, s));
+    if (ctx->timing)
+        for (hipEvent_t& e : c->cs_ev)
+            if (!e) HIPCHK(c, hipEventCreate(&e));
+    unsigned long long* d_ctr = as<unsigned long long>(c->cs_ctr);  // {n_other, n_changed, bad ops}, pileup's counter
+    uint32_t* d_take = reinterpret_cast<uint32_t*>(d_ctr + 3);
+
+    const int64_t M = std::max(std::max(iabs64(match), iabs64(mismatch)), iabs64(indel));
+    const int64_t pos_match = std::max<int64_t>(0, match);
+    int64_t host_other = 0;
+    std::vector<LocalBatchQuery> batch;
+    std::vector<int32_t> single, res;
+    std::vector<int64_t> hits;
+    std::vector<int8_t> ops;
+    for (int32_t r0 = 0; r0 < n_reads;) {
+        // a chunk of reads: what the ops budget holds (and no more reads than the test knob allows)
+        int32_t r1 = r0;
+        int64_t budget = 0;
+        batch.clear();
+        single.clear();
+        hits.clear();
+        while (r1 < n_reads) {
+            const int32_t f = place[r1];
+            const int64_t L = r_off[r1 + 1] - r_off[r1];
+            const Window w = f < 0 ? Window{0, 0, 0} : window_of(L, c_off[f + 1] - c_off[f], read_length);
+            const bool votes = f >= 0 && L > 0 && w.len > 0;
+            if (votes && r1 > r0 && budget + L + w.len > kOpsBudget) break;
+            if (c->k.consensus_chunk > 0 && r1 - r0 >= c->k.consensus_chunk) break;
+            if (votes) {
+                budget += L + w.len;
+                const int64_t top = pos_match * std::min<int64_t>(L, w.len);
+                const bool wide = M >= (int64_t(1) << 30) || top + M >= (int64_t(1) << 31);
+                const int64_t n_strips = (L + 63) / 64, steps = (((int64_t)w.len + 126) / 64) * 64;
+                if (wide || n_strips > kBatchMaxStrips || (size_t)n_strips * (size_t)steps * 64 > kBatchSlabMax)
+                    single.push_back(r1);
+                else
+                    batch.push_back({r1, (int32_t)L, (int32_t)(c_off[f] - c_off[0]) + w.lo, w.len, L * w.len});
+            }
+            ++r1;
+        }
+        if (!batch.empty()) {
+            LocalBatchRun run;
+            if (ctx->timing) HIPCHK(c, hipEventRecord(c->cs_ev[0], s));
+            const int rl = local_batch_launch(ctx, c, reads, r_off, batch, nullptr, (int32_t)total,
+                                              as<uint8_t>(c->cs_ref), true, match, mismatch, (int32_t)indel, &run);
+            if (rl != OVL_OK) return rl;
+            if (ctx->timing) HIPCHK(c, hipEventRecord(c->cs_ev[1], s));
+            HIPCHK(c, hipMemsetAsync(d_take, 0, sizeof(uint32_t), s));
+            OvlPileupArgs p{};
+            p.items = as<OvlLocalBatchItem>(c->lb_in);
+            p.q = as<uint8_t>(c->lb_in) + run.o_q;
+            p.out = as<int32_t>(c->lb_out);
+            p.ops = as<int8_t>(c->lb_ops);
+            p.n_items = run.nb;
+            p.counter = d_take;
+            p.counts = as<int32_t>(c->cs_counts);
+            p.ctr = d_ctr;
+            const int32_t waves = (int32_t)std::min<int64_t>(run.nb, (int64_t)c->cu_count * 16);
+            HIPCHK(c, ovl_launch_consensus_pileup(&p, waves, s));
+            if (ctx->timing) HIPCHK(c, hipEventRecord(c->cs_ev[2], s));
+            // the records come back (score and columns for aln, the op counts); the ops stay where they are
+            res.resize((size_t)run.nb * 8);
+            unsigned long long lb_ctr[2] = {0, 0};
+            HIPCHK(c, hipMemcpyAsync(res.data(), c->lb_out.p, res.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            HIPCHK(c, hipMemcpyAsync(lb_ctr, c->lb_ctr.p, sizeof(lb_ctr), hipMemcpyDeviceToHost, s));
+            HIPCHK(c, hipStreamSynchronize(s));
+            if (lb_ctr[1] > (unsigned long long)run.nm_sum)
+                return fail(c, OVL_E_INTERNAL, "consensus: %llu ops for a capacity of %lld", lb_ctr[1],
+                            (long long)run.nm_sum);
+            if (ctx->timing) {
+                float ms = 0.f;
+                HIPCHK(c, hipEventElapsedTime(&ms, c->cs_ev[0], c->cs_ev[1]));
+                ctx->x_cs_ms[0] += ms;
+                HIPCHK(c, hipEventElapsedTime(&ms, c->cs_ev[1], c->cs_ev[2]));
+                ctx->x_cs_ms[1] += ms;
+            }
+            for (int32_t b = 0; b < run.nb; ++b) {
+                const int32_t r = batch[(size_t)b].k, f = place[r];
+                const int32_t* o = res.data() + (size_t)b * 8;
+                ctx->x_cs_ops += o[5];
+                if (aln && o[0] > 0) {
+                    const int32_t lo = batch[(size_t)b].lo - (int32_t)(c_off[f] - c_off[0]);  // in the contig
+                    aln[3 * (int64_t)r] = o[0];
+                    aln[3 * (int64_t)r + 1] = lo + o[4];
+                    aln[3 * (int64_t)r + 2] = lo + o[2];
+                }
+            }
+            ctx->x_cs_batch += run.nb;
+            ++ctx->x_cs_launches;
+        }
+        // the reads the batch kernel does not take: one by one, their walks piled up by the host form's routine
+        for (int32_t r : single) {
+            const int32_t f = place[r], L = (int32_t)(r_off[r + 1] - r_off[r]);
+            const Window w = window_of(L, c_off[f + 1] - c_off[f], read_length);
+            ops.resize((size_t)L + (size_t)w.len);
+            int32_t sc = 0, ei = 0, ej = 0, si = 0, sj = 0;
+            int64_t n_ops = 0;
+            const int ra = ovl_local_align(ctx, reads + r_off[r], L, contigs + c_off[f] + w.lo, w.len, match, mismatch,
+                                           indel, &sc, &ei, &ej, &si, &sj, ops.data(), (int64_t)ops.size(), &n_ops);
+            if (ra != OVL_OK) return ra;
+            if (sc <= 0) continue;
+            host_other += pile_ops(ops.data(), n_ops, reads + r_off[r], ei, ej, (c_off[f] - c_off[0]) + w.lo,
+                                   [&](int64_t k) { hits.push_back(k); });
+            ctx->x_cs_ops += n_ops;
+            if (aln) {
+                aln[3 * (int64_t)r] = sc;
+                aln[3 * (int64_t)r + 1] = w.lo + sj;
+                aln[3 * (int64_t)r + 2] = w.lo + ej;
+            }
+        }
+        ctx->x_cs_single += (int64_t)single.size();
+        if (!hits.empty()) {
+            HIPCHK(c, hipSetDevice(c->device));
+            HIPCHK(c, ensure(c->cs_hits, sizeof(int64_t) * hits.size()));
+            HIPCHK(c, hipMemcpyAsync(c->cs_hits.p, hits.data(), sizeof(int64_t) * hits.size(), hipMemcpyHostToDevice,
+                                     s));
+            HIPCHK(c, ovl_launch_consensus_add(as<int64_t>(c->cs_hits), (int64_t)hits.size(),
+                                               as<int32_t>(c->cs_counts), s));
+            HIPCHK(c, hipStreamSynchronize(s));  // `hits` is refilled by the next chunk
+        }
+        r0 = r1;
+    }
+
+    HIPCHK(c, hipSetDevice(c->device));
+    if (ctx->timing) HIPCHK(c, hipEventRecord(c->cs_ev[0], s));
+    HIPCHK(c, ovl_launch_consensus_vote(as<uint8_t>(c->cs_ref), as<int32_t>(c->cs_counts), total, min_depth,
+                                        as<uint8_t>(c->cs_called), d_ctr, s));
+    if (ctx->timing) HIPCHK(c, hipEventRecord(c->cs_ev[3], s));
+    unsigned long long ctr[3] = {0, 0, 0};
+    HIPCHK(c, hipMemcpyAsync(called, c->cs_called.p, (size_t)total, hipMemcpyDeviceToHost, s));
+    if (counts)
+        HIPCHK(c, hipMemcpyAsync(counts, c->cs_counts.p, sizeof(int32_t) * 6 * (size_t)total, hipMemcpyDeviceToHost,
+                                 s));
+    HIPCHK(c, hipMemcpyAsync(ctr, c->cs_ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (ctx->timing) {
+        float ms = 0.f;
+        HIPCHK(c, hipEventElapsedTime(&ms, c->cs_ev[0], c->cs_ev[3]));
+        ctx->x_cs_ms[2] = ms;
+    }
+    if (ctr[2])
+        return fail(c, OVL_E_INTERNAL, "consensus: %llu ops of the walks fell outside their alignments", ctr[2]);
+    *n_other = (int64_t)ctr[0] + host_other;
+    *n_changed = (int64_t)ctr[1];
+    ctx->t_kernel_ms = ctx->x_cs_ms[0] + ctx->x_cs_ms[1] + ctx->x_cs_ms[2];
+    ctx->t_call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+    return OVL_OK;
+}
+
+OVL_API int ovl_last_consensus(const ovl_ctx* ctx, int64_t* batch_reads, int64_t* single_reads, int64_t* ops,
+                               int32_t* launches) {
+    if (!ctx) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
+    if (batch_reads) *batch_reads = ctx->x_cs_batch;
+    if (single_reads) *single_reads = ctx->x_cs_single;
+    if (ops) *ops = ctx->x_cs_ops;
+    if (launches) *launches = ctx->x_cs_launches;
+    return OVL_OK;
+}
+
+OVL_API int ovl_last_consensus_timing(const ovl_ctx* ctx, double* align_ms, double* pileup_ms, double* vote_ms) {
+    if (!ctx) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
+    if (align_ms) *align_ms = ctx->x_cs_ms[0];
+    if (pileup_ms) *pileup_ms = ctx->x_cs_ms[1];
+    if (vote_ms) *vote_ms = ctx->x_cs_ms[2];
+    return OVL_OK;
+}

@@ -115,6 +115,7 @@ Knobs read_knobs() {
     if (const char* e = getenv("OVL_TR_WINDOW")) k.tr_window = std::max(0, atoi(e));
     if (const char* e = getenv("OVL_REACH_WINDOW")) k.reach_window = std::max(0, atoi(e));
     if (const char* e = getenv("OVL_READ_BEST_CHUNK")) k.read_best_chunk = std::max(0, atoi(e));
+    if (const char* e = getenv("OVL_CONSENSUS_CHUNK")) k.consensus_chunk = std::max(0, atoi(e));
     if (const char* e = getenv("OVL_PIPE_CHUNK")) {
         const long long v = atoll(e);
         if (v >= 64) k.pipe_chunk = v;
@@ -136,7 +137,8 @@ void destroy_dev(Dev* d) {
                       &d->lane_col, &d->seed_s, &d->seed_e, &d->tile_flags, &d->heavy_ids, &d->cp_hbm, &d->lb_in,
                       &d->lb_ctr, &d->lb_rows, &d->lb_slabs, &d->lb_wops, &d->lb_out, &d->lb_ops, &d->tr_off,
                       &d->tr_edge, &d->tr_order, &d->tr_ctr, &d->tr_out, &d->rc_off, &d->rc_head, &d->rc_order,
-                      &d->rc_matrix, &d->rc_pivot, &d->rc_out, &d->rb_in, &d->rb_tile, &d->rb_res, &d->rb_bits})
+                      &d->rc_matrix, &d->rc_pivot, &d->rc_out, &d->rb_in, &d->rb_tile, &d->rb_res, &d->rb_bits, &d->cs_ref,
+                      &d->cs_counts, &d->cs_called, &d->cs_ctr, &d->cs_hits})
         release(*b);
     if (d->l_tb_host) (void)hipHostFree(d->l_tb_host);
     for (hipEvent_t e : d->lb_ev)
@@ -146,6 +148,8 @@ void destroy_dev(Dev* d) {
     for (hipEvent_t e : d->rc_ev)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : d->rb_ev)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : d->cs_ev)
         if (e) (void)hipEventDestroy(e);
     free_staging(d->st_in);
     free_staging(d->st_out);

@@ -2,7 +2,8 @@
 // per-device state, and the functions that cross the host files ovl_ctx.cpp (contexts, devices, pinned memory),
 // ovl_plan.cpp (planner, kernel launch), ovl_pipeline.cpp (host-array pipeline), ovl_reads.cpp (read upload),
 // ovl_cand.cpp (candidate lists, resident grid), ovl_local_api.cpp (single alignments), ovl_depth_api.cpp (read
-// depth) and the graph stages ovl_reduce_api.cpp / ovl_reach_api.cpp.
+// depth), ovl_consensus_api.cpp (read pileup and consensus) and the graph stages ovl_reduce_api.cpp /
+// ovl_reach_api.cpp.
 //
 // A context (ovl_ctx) drives one or more HIP devices from one host thread.  Each
 // device (Dev) owns: a compute stream and two copy streams (H2D, D2H), its copy
@@ -136,6 +137,8 @@ struct Knobs {
                                   // ovl_transitive_reduce (0: kReduceWindow; tests force several passes)
     int32_t read_best_chunk = 0;  // OVL_READ_BEST_CHUNK: contigs per launch of ovl_read_best's score pass (0: what
                                   // the tile budget allows; tests force several chunks)
+    int32_t consensus_chunk = 0;  // OVL_CONSENSUS_CHUNK: reads per chunk of ovl_consensus (0: what the ops budget
+                                  // allows; tests force several chunks)
     int32_t reach_window = 0;     // OVL_REACH_WINDOW: columns (bits) of the reachability rows that ovl_reach_reduce's
                                   // marking holds in registers per pass (0: 16,384; tests force several passes)
     int32_t pack_direct_pct = 18; // OVL_PACK_DIRECT_PCT: packed calls into pinned arrays store this share of the
@@ -238,6 +241,10 @@ struct Dev {
     // a chunk's score / cell tile, the per-read results and the tie bits
     DevBuf rb_in, rb_tile, rb_res, rb_bits;
     hipEvent_t rb_ev[2] = {};  // timing on: around the score pass and its folds
+    // consensus (ovl_consensus_api.cpp): the contigs' bytes, the vote counts (6 int32 per base), the called bytes,
+    // the counters {n_other, n_changed, bad ops}, and the flat count indices of the single-pair reads' votes
+    DevBuf cs_ref, cs_counts, cs_called, cs_ctr, cs_hits;
+    hipEvent_t cs_ev[4] = {};  // timing on: a chunk's start, after its alignment launch, after its pileup; the vote
     // host-array pipeline: events per slot and pinned staging (slots x cap pairs x {a, b} / {score, end})
     hipEvent_t ev_k[kSlots] = {};
     int32_t* st_in = nullptr;
@@ -322,6 +329,9 @@ struct ovl_ctx {
     int32_t x_rc_words = 0, x_rc_blocks = 0, x_rc_window = 0;   // ovl_last_reach
     int64_t x_rb_lane = 0, x_rb_fallback = 0;                   // ovl_last_read_best
     int32_t x_rb_launches = 0;
+    int64_t x_cs_batch = 0, x_cs_single = 0, x_cs_ops = 0;      // ovl_last_consensus
+    int32_t x_cs_launches = 0;
+    double x_cs_ms[3] = {0.0, 0.0, 0.0};                        // ovl_last_consensus_timing
 };
 
 int fail(const ovl_ctx* c, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
@@ -377,6 +387,31 @@ struct DeviceGuard {
     ~DeviceGuard() {
         if (dev >= 0) (void)hipSetDevice(dev);
     }
+};
+
+// The window of contig length m that a read of length L is aligned to, and what is added to window-relative
+// positions (aligners.py:187-195): a read shorter than read_length takes the contig's last L bases -- the whole
+// contig when L is 0 or above m, as the reference's slice [-L:] does -- and is shifted by m - L in every case.
+struct Window {
+    int32_t lo, len;
+    int64_t shift;
+};
+inline Window window_of(int64_t L, int64_t m, int32_t read_length) {
+    if (L >= read_length) return {0, (int32_t)m, 0};
+    const int64_t wl = (L > 0 && L < m) ? L : m;
+    return {(int32_t)(m - wl), (int32_t)wl, m - L};
+}
+
+// One launch of the batch kernel as its callers describe and receive it (local_batch_launch, ovl_local_api.cpp)
+struct LocalBatchQuery {
+    int32_t k, n, lo, m;  // caller's query index, its length, its window of the reference
+    int64_t cost;
+};
+struct LocalBatchRun {
+    std::vector<char> blob;  // the upload block: alive until the stream has been synchronised
+    size_t o_q = 0;          // offset of the queries' bytes in it (and in Dev::lb_in)
+    int32_t nb = 0, waves = 0;
+    int64_t nm_sum = 0;      // capacity of Dev::lb_ops
 };
 
 struct Plan {
@@ -478,5 +513,14 @@ int device_cuts(Dev* d, int64_t lo, int64_t hi, int32_t shards, std::vector<int6
 bool pack_ok(const ovl_ctx* c, const Plan& p, int64_t n_pairs, bool out_pinned, int32_t n_devices);
 int32_t devices_for(const ovl_ctx* c, int64_t n_pairs);
 int32_t devices_used(const ovl_ctx* c, int64_t n_pairs);
+// ovl_local_api.cpp: the batch kernel over `batch` (routed by the caller: every query fits the kernel), issued on
+// the device's stream and not waited for.  It sorts `batch` by descending cost; query batch[b] becomes item b, whose
+// eight-int32 record is Dev::lb_out[8 * b] and whose ops (with_ops) lie packed in Dev::lb_ops, their total at
+// Dev::lb_ctr + 8.  The windows are of `reference` (host, uploaded behind the queries) or, when d_reference is not
+// NULL, of that device copy of it.
+int local_batch_launch(ovl_ctx* ctx, Dev* c, const uint8_t* queries, const int64_t* q_off,
+                       std::vector<LocalBatchQuery>& batch, const uint8_t* reference, int32_t ref_len,
+                       const uint8_t* d_reference, bool with_ops, int32_t match, int32_t mismatch, int32_t indel,
+                       LocalBatchRun* run);
 // ovl_reads.cpp
 int set_reads(ovl_ctx* c, const uint8_t* seqs, const int64_t* offsets, int32_t n_reads, bool sync);

@@ -14,19 +14,6 @@ struct Shape {
     int64_t max_n = 0, max_m = 0, c_total = 0;
 };
 
-// The window of contig length m that a read of length L is aligned to, and what is added to window-relative
-// positions (aligners.py:187-195): a read shorter than read_length takes the contig's last L bases -- the whole
-// contig when L is 0 or above m, as the reference's slice [-L:] does -- and is shifted by m - L in every case.
-struct Window {
-    int32_t lo, len;
-    int64_t shift;
-};
-inline Window window_of(int64_t L, int64_t m, int32_t read_length) {
-    if (L >= read_length) return {0, (int32_t)m, 0};
-    const int64_t wl = (L > 0 && L < m) ? L : m;
-    return {(int32_t)(m - wl), (int32_t)wl, m - L};
-}
-
 template <typename C>
 int check_read_best(const C* c, const uint8_t* reads, const int64_t* r_off, int32_t n_reads, const uint8_t* contigs,
                     const int64_t* c_off, int32_t n_contigs, int32_t read_length, int32_t match,

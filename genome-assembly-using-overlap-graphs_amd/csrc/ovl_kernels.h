@@ -218,6 +218,31 @@ extern "C" hipError_t ovl_launch_read_best_fold(const OvlLocalLaneArgs* a, int32
                                                 int32_t* best, int32_t* first, int32_t* n_best, uint32_t* cell,
                                                 uint32_t* tie_bits, hipStream_t stream);
 
+// consensus (ovl_consensus.hip).  pileup: one-wavefront blocks take items[0 .. n_items) of a finished batch launch
+// from *counter (zeroed by the caller), read each item's record out[8 * item.out] = {., bi, bj, ., ., cnt, base lo,
+// base hi} and its walk ops[base .. base + cnt) (1 diag, 2 up, 3 left from cell (bi, bj)), and add one vote per op
+// to counts[(item.win_lo + column) * 6 + channel]: A, C, G, T by the query byte of a diag, 4 for a left, 5 for an up.
+// ctr[0] counts the diag ops whose byte is none of ACGT, ctr[2] the ops that fell outside their item (none, unless
+// the walk is broken; they cast no vote).  add: counts[hits[i]] += 1.  vote: called[b] for b < n_bases from
+// counts[6 * b ..] and ref[b] (the largest of the four base channels once they hold min_depth votes; ties to the
+// contig's own byte, else the first of A, C, G, T), ctr[1] += the bases that changed.
+struct OvlPileupArgs {
+    const OvlLocalBatchItem* items;
+    const uint8_t* q;
+    const int32_t* out;
+    const int8_t* ops;
+    int32_t n_items;
+    uint32_t* counter;
+    int32_t* counts;
+    unsigned long long* ctr;
+};
+extern "C" hipError_t ovl_launch_consensus_pileup(const OvlPileupArgs* a, int32_t waves, hipStream_t stream);
+extern "C" hipError_t ovl_launch_consensus_add(const int64_t* hits, int64_t n_hits, int32_t* counts,
+                                               hipStream_t stream);
+extern "C" hipError_t ovl_launch_consensus_vote(const uint8_t* ref, const int32_t* counts, int64_t n_bases,
+                                                int32_t min_depth, uint8_t* called, unsigned long long* ctr,
+                                                hipStream_t stream);
+
 // transitive reduction of an overlap graph (ovl_reduce.hip): `blocks` persistent workgroups of kReduceThreads take
 // order[0 .. n_order) -- the nodes with out-edges, heaviest first by two-hop work -- from *counter (zeroed by the
 // caller).  edge[e] = {head, weight} of CSR edge e (heads validated in [0, n_nodes), |weight| < 2^30); a window of

@@ -173,6 +173,90 @@ OVL_API int ovl_local_align(ovl_ctx* ctx, const uint8_t* query, int32_t n, const
     return OVL_OK;
 }
 
+// One launch of the batch kernel, issued and not waited for (ovl_ctx.h): the records and the packed ops stay in
+// device memory for the caller -- ovl_local_align_batch copies them back, ovl_consensus piles them up in place.
+int local_batch_launch(ovl_ctx* ctx, Dev* c, const uint8_t* queries, const int64_t* q_off,
+                       std::vector<LocalBatchQuery>& batch, const uint8_t* reference, int32_t ref_len,
+                       const uint8_t* d_reference, bool with_ops, int32_t match, int32_t mismatch, int32_t indel,
+                       LocalBatchRun* run) {
+    // long queries first: the wavefronts that take the short ones last even the launch's tail out
+    std::stable_sort(batch.begin(), batch.end(),
+                     [](const LocalBatchQuery& x, const LocalBatchQuery& y) { return x.cost > y.cost; });
+    const int32_t nb = (int32_t)batch.size();
+    size_t slab_max = 0;
+    int64_t row_max = 0, nm_max = 0, nm_sum = 0, q_bytes = 0;
+    for (const LocalBatchQuery& x : batch) {
+        const int64_t n_strips = ((int64_t)x.n + 63) / 64, steps = (((int64_t)x.m + 126) / 64) * 64;
+        slab_max = std::max(slab_max, (size_t)n_strips * (size_t)steps * 64);
+        row_max = std::max(row_max, steps);
+        nm_max = std::max<int64_t>(nm_max, (int64_t)x.n + x.m);
+        nm_sum += (int64_t)x.n + x.m;
+        q_bytes += x.n;
+    }
+    const size_t slab_pitch = (slab_max + 255) & ~size_t(255);
+    int64_t waves = std::min<int64_t>(nb, (int64_t)c->cu_count * kBatchWavesPerCu);
+    if (with_ops) waves = std::min<int64_t>(waves, std::max<int64_t>(1, (int64_t)(kBatchSlabBudget / slab_pitch)));
+    if (c->k.local_batch_waves > 0) waves = std::min<int64_t>(waves, c->k.local_batch_waves);
+    const bool row_lds = row_max <= kBatchLdsRow;
+    const int64_t wops_pitch = (nm_max + 63) & ~int64_t(63);
+    // one upload block: the items, the batched queries' bytes, the reference (unless it is on the device already)
+    const size_t o_q = sizeof(OvlLocalBatchItem) * (size_t)nb, o_r = o_q + (size_t)q_bytes;
+    std::vector<char>& blob = run->blob;
+    blob.assign(o_r + (d_reference ? 0 : (size_t)ref_len), 0);
+    OvlLocalBatchItem* items = reinterpret_cast<OvlLocalBatchItem*>(blob.data());
+    int64_t qo = 0;
+    for (int32_t b = 0; b < nb; ++b) {
+        const LocalBatchQuery& x = batch[b];
+        items[b] = {qo, x.n, x.lo, x.m, b};
+        memcpy(blob.data() + o_q + qo, queries + q_off[x.k], (size_t)x.n);
+        qo += x.n;
+    }
+    if (!d_reference) memcpy(blob.data() + o_r, reference, (size_t)ref_len);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    HIPCHK(c, ensure(c->lb_in, blob.size()));
+    HIPCHK(c, ensure(c->lb_ctr, 16));
+    HIPCHK(c, ensure(c->lb_out, sizeof(int32_t) * 8 * (size_t)nb));
+    if (!row_lds) HIPCHK(c, ensure(c->lb_rows, sizeof(int32_t) * (size_t)row_max * (size_t)waves));
+    if (with_ops) {
+        HIPCHK(c, ensure(c->lb_slabs, slab_pitch * (size_t)waves));
+        HIPCHK(c, ensure(c->lb_wops, (size_t)wops_pitch * (size_t)waves));
+        HIPCHK(c, ensure(c->lb_ops, (size_t)nm_sum));
+    }
+    HIPCHK(c, hipMemcpyAsync(c->lb_in.p, blob.data(), blob.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemsetAsync(c->lb_ctr.p, 0, 16, s));
+    OvlLocalBatchArgs a{};
+    a.items = as<OvlLocalBatchItem>(c->lb_in);
+    a.q = as<uint8_t>(c->lb_in) + o_q;
+    a.ref = d_reference ? d_reference : as<uint8_t>(c->lb_in) + o_r;
+    a.n_items = nb;
+    a.match = match;
+    a.mismatch = mismatch;
+    a.indel = indel;
+    a.counter = as<uint32_t>(c->lb_ctr);
+    a.ops_total = reinterpret_cast<unsigned long long*>(as<char>(c->lb_ctr) + 8);
+    a.rows = row_lds ? nullptr : as<int32_t>(c->lb_rows);
+    a.row_pitch = row_lds ? 0 : row_max;
+    a.slabs = with_ops ? as<int8_t>(c->lb_slabs) : nullptr;
+    a.slab_pitch = (int64_t)slab_pitch;
+    a.wave_ops = with_ops ? as<int8_t>(c->lb_wops) : nullptr;
+    a.wave_ops_pitch = wops_pitch;
+    a.out = as<int32_t>(c->lb_out);
+    a.ops = with_ops ? as<int8_t>(c->lb_ops) : nullptr;
+    if (ctx->timing) {
+        for (hipEvent_t& e : c->lb_ev)
+            if (!e) HIPCHK(c, hipEventCreate(&e));
+        HIPCHK(c, hipEventRecord(c->lb_ev[0], s));
+    }
+    HIPCHK(c, ovl_launch_local_batch(&a, (int32_t)waves, row_lds ? (uint32_t)(row_max * 4) : 0u, s));
+    if (ctx->timing) HIPCHK(c, hipEventRecord(c->lb_ev[1], s));
+    run->o_q = o_q;
+    run->nb = nb;
+    run->waves = (int32_t)waves;
+    run->nm_sum = nm_sum;
+    return OVL_OK;
+}
+
 // Many queries against windows of one reference in one call (ovl_local_batch.hip): every query that fits one
 // wavefront goes through one launch of the batch kernel; the rest (long, wide-scoring or with a traceback table
 // beyond kBatchSlabMax) go through ovl_local_align afterwards.
@@ -217,14 +301,8 @@ OVL_API int ovl_local_align_batch(ovl_ctx* ctx, const uint8_t* queries, const in
     ctx->t_kernel_ms = ctx->t_call_ms = 0.0;
     // route the queries
     const int64_t M = std::max(std::max(iabs64(match), iabs64(mismatch)), iabs64(indel));
-    struct Q {
-        int32_t k, n, lo, m;
-        int64_t cost;
-    };
-    std::vector<Q> batch;
+    std::vector<LocalBatchQuery> batch;
     std::vector<int32_t> single;
-    size_t slab_max = 0;
-    int64_t row_max = 0, nm_max = 0, nm_sum = 0, q_bytes = 0;
     for (int32_t k = 0; k < n_queries; ++k) {
         out_score[k] = 0; out_end_i[k] = 0; out_end_j[k] = 0; out_start_i[k] = 0; out_start_j[k] = 0;
         out_n_ops[k] = 0;
@@ -239,72 +317,16 @@ OVL_API int ovl_local_align_batch(ovl_ctx* ctx, const uint8_t* queries, const in
             continue;
         }
         batch.push_back({k, (int32_t)n, win_lo ? win_lo[k] : 0, (int32_t)m, n * m});
-        slab_max = std::max(slab_max, table);
-        row_max = std::max(row_max, steps);
-        nm_max = std::max(nm_max, n + m);
-        nm_sum += n + m;
-        q_bytes += n;
     }
     if (!batch.empty()) {
-        // long queries first: the wavefronts that take the short ones last even the launch's tail out
-        std::stable_sort(batch.begin(), batch.end(), [](const Q& x, const Q& y) { return x.cost > y.cost; });
-        const int32_t nb = (int32_t)batch.size();
-        const size_t slab_pitch = (slab_max + 255) & ~size_t(255);
-        int64_t waves = std::min<int64_t>(nb, (int64_t)c->cu_count * kBatchWavesPerCu);
-        if (ops) waves = std::min<int64_t>(waves, std::max<int64_t>(1, (int64_t)(kBatchSlabBudget / slab_pitch)));
-        if (c->k.local_batch_waves > 0) waves = std::min<int64_t>(waves, c->k.local_batch_waves);
-        const bool row_lds = row_max <= kBatchLdsRow;
-        const int64_t wops_pitch = (nm_max + 63) & ~int64_t(63);
-        // one upload block: the items, the batched queries' bytes, the reference
-        const size_t o_q = sizeof(OvlLocalBatchItem) * (size_t)nb, o_r = o_q + (size_t)q_bytes;
-        std::vector<char> blob(o_r + (size_t)ref_len);
-        OvlLocalBatchItem* items = reinterpret_cast<OvlLocalBatchItem*>(blob.data());
-        int64_t qo = 0;
-        for (int32_t b = 0; b < nb; ++b) {
-            const Q& x = batch[b];
-            items[b] = {qo, x.n, x.lo, x.m, b};
-            memcpy(blob.data() + o_q + qo, queries + q_off[x.k], (size_t)x.n);
-            qo += x.n;
-        }
-        memcpy(blob.data() + o_r, reference, (size_t)ref_len);
-        HIPCHK(c, hipSetDevice(c->device));
+        LocalBatchRun run;
+        // |indel| < 2^30 here: wider scorings went to `single`
+        const int rl = local_batch_launch(ctx, c, queries, q_off, batch, reference, ref_len, nullptr, ops != nullptr,
+                                          match, mismatch, (int32_t)indel, &run);
+        if (rl != OVL_OK) return rl;
         hipStream_t s = c->stream;
-        HIPCHK(c, ensure(c->lb_in, blob.size()));
-        HIPCHK(c, ensure(c->lb_ctr, 16));
-        HIPCHK(c, ensure(c->lb_out, sizeof(int32_t) * 8 * (size_t)nb));
-        if (!row_lds) HIPCHK(c, ensure(c->lb_rows, sizeof(int32_t) * (size_t)row_max * (size_t)waves));
-        if (ops) {
-            HIPCHK(c, ensure(c->lb_slabs, slab_pitch * (size_t)waves));
-            HIPCHK(c, ensure(c->lb_wops, (size_t)wops_pitch * (size_t)waves));
-            HIPCHK(c, ensure(c->lb_ops, (size_t)nm_sum));
-        }
-        HIPCHK(c, hipMemcpyAsync(c->lb_in.p, blob.data(), blob.size(), hipMemcpyHostToDevice, s));
-        HIPCHK(c, hipMemsetAsync(c->lb_ctr.p, 0, 16, s));
-        OvlLocalBatchArgs a{};
-        a.items = as<OvlLocalBatchItem>(c->lb_in);
-        a.q = as<uint8_t>(c->lb_in) + o_q;
-        a.ref = as<uint8_t>(c->lb_in) + o_r;
-        a.n_items = nb;
-        a.match = match;
-        a.mismatch = mismatch;
-        a.indel = (int32_t)indel;  // |indel| < 2^30 here: wider scorings went to `single`
-        a.counter = as<uint32_t>(c->lb_ctr);
-        a.ops_total = reinterpret_cast<unsigned long long*>(as<char>(c->lb_ctr) + 8);
-        a.rows = row_lds ? nullptr : as<int32_t>(c->lb_rows);
-        a.row_pitch = row_lds ? 0 : row_max;
-        a.slabs = ops ? as<int8_t>(c->lb_slabs) : nullptr;
-        a.slab_pitch = (int64_t)slab_pitch;
-        a.wave_ops = ops ? as<int8_t>(c->lb_wops) : nullptr;
-        a.wave_ops_pitch = wops_pitch;
-        a.out = as<int32_t>(c->lb_out);
-        a.ops = ops ? as<int8_t>(c->lb_ops) : nullptr;
-        if (ctx->timing) {
-            for (hipEvent_t& e : c->lb_ev)
-                if (!e) HIPCHK(c, hipEventCreate(&e));
-            HIPCHK(c, hipEventRecord(c->lb_ev[0], s));
-        }
-        HIPCHK(c, ovl_launch_local_batch(&a, (int32_t)waves, row_lds ? (uint32_t)(row_max * 4) : 0u, s));
-        if (ctx->timing) HIPCHK(c, hipEventRecord(c->lb_ev[1], s));
+        const int32_t nb = run.nb;
+        const int64_t nm_sum = run.nm_sum;
         std::vector<int32_t> res((size_t)nb * 8);
         unsigned long long ctr[2] = {0, 0};
         HIPCHK(c, hipMemcpyAsync(res.data(), c->lb_out.p, res.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
@@ -340,7 +362,7 @@ OVL_API int ovl_local_align_batch(ovl_ctx* ctx, const uint8_t* queries, const in
             }
         }
         ctx->x_lb_batched = nb;
-        ctx->x_lb_waves = (int32_t)waves;
+        ctx->x_lb_waves = run.waves;
     }
     for (int32_t k : single) {
         const int32_t n = (int32_t)(q_off[k + 1] - q_off[k]);

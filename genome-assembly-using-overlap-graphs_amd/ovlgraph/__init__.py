@@ -14,7 +14,7 @@ from .engine import INDEL_DEFAULT, OverlapEngine, default_engine, encode_reads, 
 
 __all__ = ["OvlError", "OverlapEngine", "default_engine", "encode_reads", "score_reads", "INDEL_DEFAULT",
            "transitive_reduction", "assemble_contigs_string", "transitive_reduction2", "find_unitigs",
-           "assemble_contigs"]
+           "assemble_contigs", "pileup", "polish_contigs"]
 
 
 def __getattr__(name):
@@ -24,4 +24,7 @@ def __getattr__(name):
                 "assemble_contigs"):
         from . import overlapGraphs
         return getattr(overlapGraphs, name)
+    if name in ("pileup", "polish_contigs"):
+        from . import consensus
+        return getattr(consensus, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

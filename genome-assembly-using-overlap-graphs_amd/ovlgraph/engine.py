@@ -160,6 +160,44 @@ def read_best_host(reads, contigs, read_length: int, match: int = 10, mismatch: 
     return _read_best_result(R, C, outs, bits, sc)
 
 
+def _consensus_arrays(reads, contigs, place, counts: bool):
+    """Reads, contigs and the placement as the C ABI of ovl_consensus takes them, with the arrays to receive the
+    results: the counts (total bases x 6 int32, when asked for), the called bytes and three int32 per read."""
+    reads, contigs = list(reads), list(contigs)
+    R, C = len(reads), len(contigs)
+    if not all(s.isascii() for s in reads + contigs):
+        raise OvlError(-4, "consensus needs ASCII reads and contigs (the called bases are bytes)")
+    buf, offs = encode_reads(reads + contigs)
+    place = np.ascontiguousarray(place, dtype=np.int32)
+    if place.shape != (R,):
+        raise OvlError(-1, "place must hold one contig position (or -1) per read")
+    total = int(offs[-1] - offs[R])
+    cnt = np.zeros((max(total, 1), 6), dtype=np.int32) if counts else None
+    called = np.zeros(max(total, 1), dtype=np.uint8)
+    aln = np.zeros((max(R, 1), 3), dtype=np.int32)
+    return R, C, buf, np.ascontiguousarray(offs[: R + 1]), np.ascontiguousarray(offs[R:]), place, total, cnt, called, aln
+
+
+def _consensus_result(R, total, cnt, called, aln, n_changed, n_other) -> Dict[str, object]:
+    res = {"called": called[:total], "n_changed": int(n_changed.value), "n_other": int(n_other.value),
+           "aln": aln[:R]}
+    if cnt is not None:
+        res["counts"] = cnt[:total]
+    return res
+
+
+def consensus_host(reads, contigs, place, read_length: int, match: int = 10, mismatch: int = -1, indel: int = -1,
+                   min_depth: int = 3, counts: bool = True) -> Dict[str, object]:
+    """``OverlapEngine.consensus`` on one host thread (ovl_consensus_host): no context, no GPU."""
+    R, C, buf, r_off, c_off, place, total, cnt, called, aln = _consensus_arrays(reads, contigs, place, counts)
+    n_changed, n_other = ctypes.c_int64(0), ctypes.c_int64(0)
+    check(_lib.load().ovl_consensus_host(_ptr(buf), _ptr(r_off), R, _ptr(buf), _ptr(c_off), C, _ptr(place),
+                                         int(read_length), int(match), int(mismatch), int(indel), int(min_depth),
+                                         _ptr(cnt) if counts else None, _ptr(called), ctypes.byref(n_changed),
+                                         ctypes.byref(n_other), _ptr(aln)))
+    return _consensus_result(R, total, cnt, called, aln, n_changed, n_other)
+
+
 def host_pool() -> Dict[str, int]:
     """The host thread pool's plan, recounted now (ovl_host_pool): {threads, sharers, cpus, packed}."""
     v = [ctypes.c_int32() for _ in range(4)]
@@ -488,6 +526,33 @@ class OverlapEngine:
         a, b, n = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32()
         check(self._L.ovl_last_read_best(self._ctx, ctypes.byref(a), ctypes.byref(b), ctypes.byref(n)), self._ctx)
         return {"lane_pairs": a.value, "fallback_pairs": b.value, "launches": n.value}
+
+    def consensus(self, reads, contigs, place, read_length: int, match: int = 10, mismatch: int = -1,
+                  indel: int = -1, min_depth: int = 3, counts: bool = True) -> Dict[str, object]:
+        """The read pileup and the per-base vote (ovl_consensus): read r, aligned to contig position ``place[r]`` (-1:
+        no vote) by ``align_read_or_contig_to_reference``, votes along its walk.  Returns ``called`` (uint8 over the
+        concatenated contigs), ``n_changed``, ``n_other`` (read bytes outside ACGT on a diagonal), ``aln`` (reads x 3
+        int32: score, first column, one past the last column, in the contig's own coordinates) and, with
+        ``counts=True``, ``counts`` (bases x 6 int32: A, C, G, T, gap, ins)."""
+        R, C, buf, r_off, c_off, place, total, cnt, called, aln = _consensus_arrays(reads, contigs, place, counts)
+        n_changed, n_other = ctypes.c_int64(0), ctypes.c_int64(0)
+        check(self._L.ovl_consensus(self._ctx, _ptr(buf), _ptr(r_off), R, _ptr(buf), _ptr(c_off), C, _ptr(place),
+                                    int(read_length), int(match), int(mismatch), int(indel), int(min_depth),
+                                    _ptr(cnt) if counts else None, _ptr(called), ctypes.byref(n_changed),
+                                    ctypes.byref(n_other), _ptr(aln)), self._ctx)
+        return _consensus_result(R, total, cnt, called, aln, n_changed, n_other)
+
+    def last_consensus(self) -> Dict[str, float]:
+        """{batch_reads, single_reads, ops, launches} of the last ``consensus`` (ovl_last_consensus): the reads that
+        took the batch kernel and the single-pair path, the ops piled up and the batch kernel's launches; with timing
+        on also {align_ms, pileup_ms, vote_ms} (ovl_last_consensus_timing)."""
+        a, b, o, n = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32()
+        check(self._L.ovl_last_consensus(self._ctx, ctypes.byref(a), ctypes.byref(b), ctypes.byref(o),
+                                         ctypes.byref(n)), self._ctx)
+        t = [ctypes.c_double() for _ in range(3)]
+        check(self._L.ovl_last_consensus_timing(self._ctx, *[ctypes.byref(x) for x in t]), self._ctx)
+        return {"batch_reads": a.value, "single_reads": b.value, "ops": o.value, "launches": n.value,
+                "align_ms": t[0].value, "pileup_ms": t[1].value, "vote_ms": t[2].value}
 
     # ---------------------------------------------------------------- graph stages
     def transitive_reduce(self, off, heads, weights) -> np.ndarray:

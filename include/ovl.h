@@ -392,6 +392,53 @@ int ovl_read_best_host(const uint8_t* reads, const int64_t* r_off, int32_t n_rea
                        int32_t* best_end, uint32_t* tie_bits, int32_t* scores);
 int ovl_last_read_best(const ovl_ctx* ctx, int64_t* lane_pairs, int64_t* fallback_pairs, int32_t* launches);
 
+/*
+ * Consensus polishing on the context's first device: the reads vote on the bases of the contigs they are placed on.
+ * Reads and contigs are given as for ovl_read_best (repeated contigs are separate positions); place[r] is the contig
+ * position read r votes on, or -1 for none.  Read r is aligned to contig place[r] by
+ * align_read_or_contig_to_reference (aligners.py:170-202: the same window, best cell and walk as ovl_read_best); a
+ * read with score 0 casts no vote.  Every column below is the contig's own column, window start + window-relative
+ * column, not the reference's shifted start / end.  The walk's ops vote, at the column of the cell they are taken at:
+ *   diag   +1 in channel A, C, G or T of the column, by the read's byte (upper case); any other byte casts no vote
+ *          and adds one to *n_other,
+ *   left   +1 in channel gap of the column (a contig base with no read base),
+ *   up     +1 in channel ins of the column at the left of the inserted read base.
+ * counts (may be NULL) receives total_bases x 6 int32, row-major, channels A, C, G, T, gap, ins, where base b is
+ * byte contigs[c_off[0] + b] and total_bases = c_off[n_contigs] - c_off[0].  called receives total_bases bytes: with
+ * n = A + C + G + T < min_depth the contig's byte; else the byte of the largest of the four channels, a tie going to
+ * the contig's own byte when it is among the tied and else to the first of A, C, G, T.  gap and ins never change a
+ * base, so polished contigs keep their lengths.  *n_changed counts the bases where called differs from the contig.
+ * aln (may be NULL) receives three int32 per read: the score, the first column and one past the last column of its
+ * alignment; zeros for unplaced reads and reads with score 0.  The sums are integer, so the result does not depend
+ * on the order of the reads.
+ * Every argument is checked before anything is launched or written: OVL_E_ARG for null pointers, negative counts or
+ * read_length, min_depth < 1 and offsets that decrease; OVL_E_INDEX for place[r] outside [-1, n_contigs);
+ * OVL_E_UNSUPPORTED beyond ovl_local_align's limits (lengths < 2^20, match * min(n, m) < 2^24) for a placed read or
+ * when the contigs together reach 2^31 bases.
+ * The alignments run in the batch kernel of ovl_local_align_batch, one item per placed read, whose walks stay in
+ * device memory; a second kernel piles them up (one wavefront per read, one int32 atomic add per op) and a third
+ * votes (one thread per base).  Reads beyond the batch kernel's limits go through ovl_local_align one by one and
+ * their votes are added before the vote kernel runs.  Reads are taken in chunks bounded by a 256 MiB budget of ops
+ * (OVL_CONSENSUS_CHUNK at context creation caps the reads per chunk, for tests), so device memory is bounded by the
+ * contigs (31 bytes per base) plus one chunk.  With ovl_set_timing on, ovl_last_timing reports the kernels and the
+ * call.
+ * ovl_consensus_host: the same checks and results on one host thread, with no context and no GPU.
+ * ovl_last_consensus: the reads of the last ovl_consensus that took the batch kernel and the single-pair path, the
+ * ops piled up and the batch kernel's launches.  ovl_last_consensus_timing (timing on): the kernel time by part, in
+ * ms -- the alignment launches with their uploads, the pileup kernel, the vote kernel.
+ */
+int ovl_consensus(ovl_ctx* ctx, const uint8_t* reads, const int64_t* r_off, int32_t n_reads, const uint8_t* contigs,
+                  const int64_t* c_off, int32_t n_contigs, const int32_t* place, int32_t read_length, int32_t match,
+                  int32_t mismatch, int64_t indel, int32_t min_depth, int32_t* counts, uint8_t* called,
+                  int64_t* n_changed, int64_t* n_other, int32_t* aln);
+int ovl_consensus_host(const uint8_t* reads, const int64_t* r_off, int32_t n_reads, const uint8_t* contigs,
+                       const int64_t* c_off, int32_t n_contigs, const int32_t* place, int32_t read_length,
+                       int32_t match, int32_t mismatch, int64_t indel, int32_t min_depth, int32_t* counts,
+                       uint8_t* called, int64_t* n_changed, int64_t* n_other, int32_t* aln);
+int ovl_last_consensus(const ovl_ctx* ctx, int64_t* batch_reads, int64_t* single_reads, int64_t* ops,
+                       int32_t* launches);
+int ovl_last_consensus_timing(const ovl_ctx* ctx, double* align_ms, double* pileup_ms, double* vote_ms);
+
 #ifdef __cplusplus
 }
 #endif
