@@ -39,9 +39,10 @@ __global__ __launch_bounds__(64) void consensus_pileup_kernel(OvlPileupArgs a) {
         const uint32_t k = (uint32_t)__builtin_amdgcn_readlane((int32_t)old, 0);
         if (k >= (uint32_t)a.n_items) break;
         const OvlLocalBatchItem it = a.items[k];
-        const int32_t* rec = a.out + (int64_t)it.out * 8;
-        const int32_t bi = rec[1], bj = rec[2], cnt = rec[5];
-        const unsigned long long base = (unsigned long long)(uint32_t)rec[6] | ((unsigned long long)(uint32_t)rec[7] << 32);
+        const OvlLocalBatchRecord* rec = a.out + it.out;
+        const int32_t bi = rec->end_i, bj = rec->end_j, cnt = rec->n_ops;
+        const unsigned long long hi = rec->ops_hi;
+        const unsigned long long base = rec->ops_lo | (hi << 32);  // ops_base()
         const uint8_t* q = a.q + it.q_off;
         int32_t cols = 0, rows = 0;  // ops before this chunk that consumed a column / a row
         uint32_t other = 0, bad = 0;

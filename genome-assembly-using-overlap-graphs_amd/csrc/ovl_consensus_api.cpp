@@ -1,10 +1,10 @@
 // ovl_consensus_api.cpp — consensus polishing: every placed read is aligned to its contig as
-// align_read_or_contig_to_reference does it (aligners.py:170-202, the window rule of ovl_ctx.h), the walks are piled
-// up into six vote channels per contig base, and every base with enough votes is called by majority.  The host form
-// (ovl_consensus_host) and the device call (ovl_consensus: the batch kernel's walks stay in device memory and
-// ovl_consensus.hip piles them up and votes there).  The pileup routine and the vote rule below are the one
-// statement both forms share.
-#include "ovl_ctx.h"
+// align_read_or_contig_to_reference does it (aligners.py:170-202, the window rule of ovl_local_host.h), the walks are
+// piled up into six vote channels per contig base, and every base with enough votes is called by majority.  The host
+// form (ovl_consensus_host, over ovl_local_host.h's fill and walk) and the device call (ovl_consensus: the batch
+// kernel's walks stay in device memory and ovl_consensus.hip piles them up and votes there).  The pileup routine and
+// the vote rule below are the one statement both forms share.
+#include "ovl_local_host.h"
 
 namespace {
 
@@ -17,26 +17,14 @@ int check_consensus(const C* c, const uint8_t* reads, const int64_t* r_off, int3
                     const int64_t* c_off, int32_t n_contigs, const int32_t* place, int32_t read_length, int32_t match,
                     int32_t min_depth, const uint8_t* called, const int64_t* n_changed, const int64_t* n_other,
                     int64_t* total) {
-    if (n_reads < 0 || n_contigs < 0 || read_length < 0) return fail(c, OVL_E_ARG, "negative count or read_length");
+    if (int rc = check_seq_counts(c, n_reads, n_contigs, read_length)) return rc;
     if (min_depth < 1) return fail(c, OVL_E_ARG, "min_depth %d < 1", min_depth);
     if ((n_reads > 0 && (!r_off || !place)) || (n_contigs > 0 && !c_off))
         return fail(c, OVL_E_ARG, "NULL offsets or placement");
     if (!n_changed || !n_other) return fail(c, OVL_E_ARG, "NULL output pointer");
-    if (n_reads > 0 && r_off[0] < 0) return fail(c, OVL_E_ARG, "r_off[0] < 0");
-    if (n_contigs > 0 && c_off[0] < 0) return fail(c, OVL_E_ARG, "c_off[0] < 0");
-    int64_t max_n = 0, max_m = 0;
-    for (int32_t r = 0; r < n_reads; ++r) {
-        const int64_t n = r_off[r + 1] - r_off[r];
-        if (n < 0) return fail(c, OVL_E_ARG, "read %d: offsets decrease", r);
-        max_n = std::max(max_n, n);
-    }
-    for (int32_t k = 0; k < n_contigs; ++k) {
-        const int64_t m = c_off[k + 1] - c_off[k];
-        if (m < 0) return fail(c, OVL_E_ARG, "contig %d: offsets decrease", k);
-        max_m = std::max(max_m, m);
-    }
-    *total = n_contigs > 0 ? c_off[n_contigs] - c_off[0] : 0;
-    if ((max_n > 0 && !reads) || (max_m > 0 && !contigs)) return fail(c, OVL_E_ARG, "NULL sequence");
+    SeqShape sh;
+    if (int rc = check_seq_sets(c, reads, r_off, n_reads, contigs, c_off, n_contigs, &sh)) return rc;
+    *total = sh.c_total;
     if (*total > 0 && !called) return fail(c, OVL_E_ARG, "NULL output pointer");
     for (int32_t r = 0; r < n_reads; ++r)
         if (place[r] < -1 || place[r] >= n_contigs)
@@ -46,61 +34,12 @@ int check_consensus(const C* c, const uint8_t* reads, const int64_t* r_off, int3
     for (int32_t r = 0; r < n_reads; ++r) {
         if (place[r] < 0) continue;
         const int64_t n = r_off[r + 1] - r_off[r], m = c_off[place[r] + 1] - c_off[place[r]];
-        const int64_t wl = window_of(n, m, read_length).len;
-        if (n > 0xFFFFF || m > 0xFFFFF || std::max<int64_t>(0, match) * std::min(n, wl) >= (int64_t(1) << 24))
+        // the lengths of the read and its whole contig, the product over its window
+        if (!local_limits_ok(n, m, 0) || !local_limits_ok(n, window_of(n, m, read_length).len, match))
             return fail(c, OVL_E_UNSUPPORTED,
                         "consensus, read %d: lengths < 2^20 and match * min(n, m) < 2^24 required", r);
     }
     return OVL_OK;
-}
-
-// scores at or below -2^40 all mean "never taken" for cells below 2^24, and keep int64 sums far from overflow
-inline int64_t clamp_score(int64_t v) {
-    const int64_t lim = int64_t(1) << 40;
-    return v < -lim ? -lim : (v > lim ? lim : v);
-}
-
-struct Walk {
-    int64_t score = 0;
-    int32_t bi = 0, bj = 0, sj = 0;  // the best cell and the column where the walk stops, window-relative
-};
-
-// aligners.py:106-161 over q[0..n) x t[0..m): the fill with its traceback table, the first strict maximum and the
-// walk from it, whose ops (1 diag, 2 up, 3 left) are left in `ops` in walk order
-Walk align_host(const uint8_t* q, int32_t n, const uint8_t* t, int32_t m, int64_t match, int64_t mismatch,
-                int64_t indel, std::vector<int8_t>& tb, std::vector<int64_t>& row, std::vector<int8_t>& ops) {
-    Walk w;
-    ops.clear();
-    const size_t pitch = (size_t)m + 1;
-    tb.assign(((size_t)n + 1) * pitch, 0);
-    row.assign(pitch, 0);
-    for (int32_t i = 1; i <= n; ++i) {
-        int64_t diag = 0, left = 0;
-        for (int32_t j = 1; j <= m; ++j) {
-            const int64_t upv = row[(size_t)j];
-            const int64_t d = diag + (q[i - 1] == t[j - 1] ? match : mismatch), u = upv + indel, l = left + indel;
-            int64_t v = 0;
-            int8_t op = 0;
-            if (d >= u && d >= l && d >= 0) { v = d; op = 1; }
-            else if (u >= l && u >= 0) { v = u; op = 2; }
-            else if (l >= 0) { v = l; op = 3; }
-            diag = upv;
-            row[(size_t)j] = left = v;
-            tb[(size_t)i * pitch + (size_t)j] = v > 0 ? op : 0;
-            if (v > w.score) { w.score = v; w.bi = i; w.bj = j; }
-        }
-    }
-    int32_t i = w.bi, j = w.bj;
-    while (i > 0 && j > 0) {
-        const int8_t op = tb[(size_t)i * pitch + (size_t)j];
-        if (op == 1) { --i; --j; }
-        else if (op == 2) --i;
-        else if (op == 3) --j;
-        else break;
-        ops.push_back(op);
-    }
-    w.sj = j;
-    return w;
 }
 
 // The pileup of one walk from cell (bi, bj): every op votes at the contig base of its cell's column (DP column j is
@@ -175,13 +114,15 @@ OVL_API int ovl_consensus_host(const uint8_t* reads, const int64_t* r_off, int32
             const int32_t L = (int32_t)(r_off[r + 1] - r_off[r]);
             const Window w = window_of(L, c_off[f + 1] - c_off[f], read_length);
             if (L == 0 || w.len == 0) continue;
-            const Walk a = align_host(q, L, contigs + c_off[f] + w.lo, w.len, match, mismatch, ind, tb, row, ops);
+            const Cell a = sw_fill_host<true>(q, L, contigs + c_off[f] + w.lo, w.len, match, mismatch, ind, row, &tb);
             if (a.score <= 0) continue;
+            ops.clear();
+            const int32_t sj = sw_walk_host(tb, w.len, a.bi, a.bj, [&](int8_t op) { ops.push_back(op); });
             *n_other += pile_ops(ops.data(), (int64_t)ops.size(), q, a.bi, a.bj, (c_off[f] - c_off[0]) + w.lo,
                                  [&](int64_t k) { ++counts[k]; });
             if (aln) {
                 aln[3 * (int64_t)r] = (int32_t)a.score;
-                aln[3 * (int64_t)r + 1] = w.lo + a.sj;
+                aln[3 * (int64_t)r + 1] = w.lo + sj;
                 aln[3 * (int64_t)r + 2] = w.lo + a.bj;
             }
         }
@@ -226,17 +167,14 @@ OVL_API int ovl_consensus(ovl_ctx* ctx, const uint8_t* reads, const int64_t* r_o
     HIPCHK(c, hipMemcpyAsync(c->cs_ref.p, ref, (size_t)total, hipMemcpyHostToDevice, s));
     HIPCHK(c, hipMemsetAsync(c->cs_counts.p, 0, sizeof(int32_t) * 6 * (size_t)total, s));
     HIPCHK(c, hipMemsetAsync(c->cs_ctr.p, 0, 32, s));
-    if (ctx->timing)
-        for (hipEvent_t& e : c->cs_ev)
-            if (!e) HIPCHK(c, hipEventCreate(&e));
+    if (ctx->timing) HIPCHK(c, ensure_events(c->cs_ev));
     unsigned long long* d_ctr = as<unsigned long long>(c->cs_ctr);  // {n_other, n_changed, bad ops}, pileup's counter
     uint32_t* d_take = reinterpret_cast<uint32_t*>(d_ctr + 3);
 
-    const int64_t M = std::max(std::max(iabs64(match), iabs64(mismatch)), iabs64(indel));
-    const int64_t pos_match = std::max<int64_t>(0, match);
     int64_t host_other = 0;
     std::vector<LocalBatchQuery> batch;
-    std::vector<int32_t> single, res;
+    std::vector<int32_t> single;
+    std::vector<OvlLocalBatchRecord> res;
     std::vector<int64_t> hits;
     std::vector<int8_t> ops;
     for (int32_t r0 = 0; r0 < n_reads;) {
@@ -250,19 +188,17 @@ OVL_API int ovl_consensus(ovl_ctx* ctx, const uint8_t* reads, const int64_t* r_o
             const int32_t f = place[r1];
             const int64_t L = r_off[r1 + 1] - r_off[r1];
             const Window w = f < 0 ? Window{0, 0, 0} : window_of(L, c_off[f + 1] - c_off[f], read_length);
-            const bool votes = f >= 0 && L > 0 && w.len > 0;
+            // an unplaced read, an empty one or an empty window casts no vote; the others always have a traceback
+            const LocalRoute route =
+                f < 0 ? LocalRoute::Empty : local_route(L, w.len, match, mismatch, indel, true);
+            const bool votes = route != LocalRoute::Empty;
             if (votes && r1 > r0 && budget + L + w.len > kOpsBudget) break;
             if (c->k.consensus_chunk > 0 && r1 - r0 >= c->k.consensus_chunk) break;
-            if (votes) {
-                budget += L + w.len;
-                const int64_t top = pos_match * std::min<int64_t>(L, w.len);
-                const bool wide = M >= (int64_t(1) << 30) || top + M >= (int64_t(1) << 31);
-                const int64_t n_strips = (L + 63) / 64, steps = (((int64_t)w.len + 126) / 64) * 64;
-                if (wide || n_strips > kBatchMaxStrips || (size_t)n_strips * (size_t)steps * 64 > kBatchSlabMax)
-                    single.push_back(r1);
-                else
-                    batch.push_back({r1, (int32_t)L, (int32_t)(c_off[f] - c_off[0]) + w.lo, w.len, L * w.len});
-            }
+            if (votes) budget += L + w.len;
+            if (route == LocalRoute::Single)
+                single.push_back(r1);
+            else if (route == LocalRoute::Batch)
+                batch.push_back({r1, (int32_t)L, (int32_t)(c_off[f] - c_off[0]) + w.lo, w.len, L * w.len});
             ++r1;
         }
         if (!batch.empty()) {
@@ -276,7 +212,7 @@ OVL_API int ovl_consensus(ovl_ctx* ctx, const uint8_t* reads, const int64_t* r_o
             OvlPileupArgs p{};
             p.items = as<OvlLocalBatchItem>(c->lb_in);
             p.q = as<uint8_t>(c->lb_in) + run.o_q;
-            p.out = as<int32_t>(c->lb_out);
+            p.out = as<OvlLocalBatchRecord>(c->lb_out);
             p.ops = as<int8_t>(c->lb_ops);
             p.n_items = run.nb;
             p.counter = d_take;
@@ -286,9 +222,9 @@ OVL_API int ovl_consensus(ovl_ctx* ctx, const uint8_t* reads, const int64_t* r_o
             HIPCHK(c, ovl_launch_consensus_pileup(&p, waves, s));
             if (ctx->timing) HIPCHK(c, hipEventRecord(c->cs_ev[2], s));
             // the records come back (score and columns for aln, the op counts); the ops stay where they are
-            res.resize((size_t)run.nb * 8);
+            res.resize((size_t)run.nb);
             unsigned long long lb_ctr[2] = {0, 0};
-            HIPCHK(c, hipMemcpyAsync(res.data(), c->lb_out.p, res.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            HIPCHK(c, hipMemcpyAsync(res.data(), c->lb_out.p, res.size() * sizeof(res[0]), hipMemcpyDeviceToHost, s));
             HIPCHK(c, hipMemcpyAsync(lb_ctr, c->lb_ctr.p, sizeof(lb_ctr), hipMemcpyDeviceToHost, s));
             HIPCHK(c, hipStreamSynchronize(s));
             if (lb_ctr[1] > (unsigned long long)run.nm_sum)
@@ -303,13 +239,13 @@ OVL_API int ovl_consensus(ovl_ctx* ctx, const uint8_t* reads, const int64_t* r_o
             }
             for (int32_t b = 0; b < run.nb; ++b) {
                 const int32_t r = batch[(size_t)b].k, f = place[r];
-                const int32_t* o = res.data() + (size_t)b * 8;
-                ctx->x_cs_ops += o[5];
-                if (aln && o[0] > 0) {
+                const OvlLocalBatchRecord& o = res[(size_t)b];
+                ctx->x_cs_ops += o.n_ops;
+                if (aln && o.score > 0) {
                     const int32_t lo = batch[(size_t)b].lo - (int32_t)(c_off[f] - c_off[0]);  // in the contig
-                    aln[3 * (int64_t)r] = o[0];
-                    aln[3 * (int64_t)r + 1] = lo + o[4];
-                    aln[3 * (int64_t)r + 2] = lo + o[2];
+                    aln[3 * (int64_t)r] = o.score;
+                    aln[3 * (int64_t)r + 1] = lo + o.start_j;
+                    aln[3 * (int64_t)r + 2] = lo + o.end_j;
                 }
             }
             ctx->x_cs_batch += run.nb;

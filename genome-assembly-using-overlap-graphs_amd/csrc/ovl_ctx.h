@@ -3,7 +3,7 @@
 // ovl_plan.cpp (planner, kernel launch), ovl_pipeline.cpp (host-array pipeline), ovl_reads.cpp (read upload),
 // ovl_cand.cpp (candidate lists, resident grid), ovl_local_api.cpp (single alignments), ovl_depth_api.cpp (read
 // depth), ovl_consensus_api.cpp (read pileup and consensus) and the graph stages ovl_reduce_api.cpp /
-// ovl_reach_api.cpp.
+// ovl_reach_api.cpp.  What the local-alignment stages share on the host is in ovl_local_host.h.
 //
 // A context (ovl_ctx) drives one or more HIP devices from one host thread.  Each
 // device (Dev) owns: a compute stream and two copy streams (H2D, D2H), its copy
@@ -170,14 +170,6 @@ constexpr int64_t kCompactMin = int64_t(1) << 16;
 // 250 K-pair shard 22.7 -> 9.4 us, the N = 4 step 0.085 -> 0.075 ms; tools/pool_probe.cpp,
 // profiles/r04_pool_ab_*.json)
 constexpr size_t kExpandPart = size_t(1) << 14;
-// ovl_local_align_batch: a query stays on the batch kernel (one wavefront per query) up to this many 64-row
-// strips and this large a traceback table of its own; all slabs of a launch together stay inside the budget,
-// which caps the wavefront count; the carried row lives in LDS up to this many int32
-constexpr int32_t kBatchMaxStrips = 16;
-constexpr size_t kBatchSlabMax = size_t(64) << 20;
-constexpr size_t kBatchSlabBudget = size_t(4) << 30;
-constexpr int64_t kBatchLdsRow = 8192;
-constexpr int32_t kBatchWavesPerCu = 8;
 
 struct ovl_ctx;
 
@@ -228,7 +220,7 @@ struct Dev {
     int8_t* l_tb_host = nullptr;
     size_t l_tb_host_bytes = 0;
     // batched local alignment (ovl_local_align_batch): the upload block (items, query bytes, reference), the two
-    // counters, per-wavefront rows / traceback slabs / op scratch, and the results (8 int32 per query, packed ops)
+    // counters, per-wavefront rows / traceback slabs / op scratch, and the results (a record per query, packed ops)
     DevBuf lb_in, lb_ctr, lb_rows, lb_slabs, lb_wops, lb_out, lb_ops;
     hipEvent_t lb_ev[2] = {};  // timing on: around the batch kernel
     // transitive reduction (ovl_reduce_api.cpp): the CSR, the node order, the counter and the mask
@@ -389,30 +381,15 @@ struct DeviceGuard {
     }
 };
 
-// The window of contig length m that a read of length L is aligned to, and what is added to window-relative
-// positions (aligners.py:187-195): a read shorter than read_length takes the contig's last L bases -- the whole
-// contig when L is 0 or above m, as the reference's slice [-L:] does -- and is shifted by m - L in every case.
-struct Window {
-    int32_t lo, len;
-    int64_t shift;
-};
-inline Window window_of(int64_t L, int64_t m, int32_t read_length) {
-    if (L >= read_length) return {0, (int32_t)m, 0};
-    const int64_t wl = (L > 0 && L < m) ? L : m;
-    return {(int32_t)(m - wl), (int32_t)wl, m - L};
+// timing on: a stage's events (Dev::lb_ev and the like), created by the first call that records them
+template <size_t N>
+hipError_t ensure_events(hipEvent_t (&ev)[N]) {
+    for (hipEvent_t& e : ev) {
+        const hipError_t r = e ? hipSuccess : hipEventCreate(&e);
+        if (r != hipSuccess) return r;
+    }
+    return hipSuccess;
 }
-
-// One launch of the batch kernel as its callers describe and receive it (local_batch_launch, ovl_local_api.cpp)
-struct LocalBatchQuery {
-    int32_t k, n, lo, m;  // caller's query index, its length, its window of the reference
-    int64_t cost;
-};
-struct LocalBatchRun {
-    std::vector<char> blob;  // the upload block: alive until the stream has been synchronised
-    size_t o_q = 0;          // offset of the queries' bytes in it (and in Dev::lb_in)
-    int32_t nb = 0, waves = 0;
-    int64_t nm_sum = 0;      // capacity of Dev::lb_ops
-};
 
 struct Plan {
     int kernel = OVL_KERNEL_NONE;
@@ -513,14 +490,5 @@ int device_cuts(Dev* d, int64_t lo, int64_t hi, int32_t shards, std::vector<int6
 bool pack_ok(const ovl_ctx* c, const Plan& p, int64_t n_pairs, bool out_pinned, int32_t n_devices);
 int32_t devices_for(const ovl_ctx* c, int64_t n_pairs);
 int32_t devices_used(const ovl_ctx* c, int64_t n_pairs);
-// ovl_local_api.cpp: the batch kernel over `batch` (routed by the caller: every query fits the kernel), issued on
-// the device's stream and not waited for.  It sorts `batch` by descending cost; query batch[b] becomes item b, whose
-// eight-int32 record is Dev::lb_out[8 * b] and whose ops (with_ops) lie packed in Dev::lb_ops, their total at
-// Dev::lb_ctr + 8.  The windows are of `reference` (host, uploaded behind the queries) or, when d_reference is not
-// NULL, of that device copy of it.
-int local_batch_launch(ovl_ctx* ctx, Dev* c, const uint8_t* queries, const int64_t* q_off,
-                       std::vector<LocalBatchQuery>& batch, const uint8_t* reference, int32_t ref_len,
-                       const uint8_t* d_reference, bool with_ops, int32_t match, int32_t mismatch, int32_t indel,
-                       LocalBatchRun* run);
 // ovl_reads.cpp
 int set_reads(ovl_ctx* c, const uint8_t* seqs, const int64_t* offsets, int32_t n_reads, bool sync);

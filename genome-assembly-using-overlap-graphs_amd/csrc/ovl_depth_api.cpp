@@ -3,42 +3,24 @@
 // score, the contigs that attain it and the aligned stretch on the first of them.  The host form
 // (ovl_read_best_host) and the device call (ovl_read_best: ovl_local_lane.hip for the scores, the batched
 // local-alignment kernel for the start positions and for the reads the lane kernel does not take).
-#include "ovl_ctx.h"
+#include "ovl_local_host.h"
 
 namespace {
 
 constexpr size_t kTileBudget = size_t(256) << 20;  // a chunk's {score, cell} tile in HBM
 constexpr int64_t kOpsBudget = int64_t(256) << 20;  // the walks of one start-position batch
 
-struct Shape {
-    int64_t max_n = 0, max_m = 0, c_total = 0;
-};
-
 template <typename C>
 int check_read_best(const C* c, const uint8_t* reads, const int64_t* r_off, int32_t n_reads, const uint8_t* contigs,
                     const int64_t* c_off, int32_t n_contigs, int32_t read_length, int32_t match,
                     const int32_t* best_score, const int32_t* first_best, const int32_t* n_best,
-                    const int32_t* best_start, const int32_t* best_end, Shape* sh) {
-    if (n_reads < 0 || n_contigs < 0 || read_length < 0) return fail(c, OVL_E_ARG, "negative count or read_length");
+                    const int32_t* best_start, const int32_t* best_end, SeqShape* sh) {
+    if (int rc = check_seq_counts(c, n_reads, n_contigs, read_length)) return rc;
     if ((n_reads > 0 && !r_off) || (n_contigs > 0 && !c_off)) return fail(c, OVL_E_ARG, "NULL offsets");
     if (n_reads > 0 && (!best_score || !first_best || !n_best || !best_start || !best_end))
         return fail(c, OVL_E_ARG, "NULL output pointer");
-    if (n_reads > 0 && r_off[0] < 0) return fail(c, OVL_E_ARG, "r_off[0] < 0");
-    if (n_contigs > 0 && c_off[0] < 0) return fail(c, OVL_E_ARG, "c_off[0] < 0");
-    for (int32_t r = 0; r < n_reads; ++r) {
-        const int64_t n = r_off[r + 1] - r_off[r];
-        if (n < 0) return fail(c, OVL_E_ARG, "read %d: offsets decrease", r);
-        sh->max_n = std::max(sh->max_n, n);
-    }
-    for (int32_t k = 0; k < n_contigs; ++k) {
-        const int64_t m = c_off[k + 1] - c_off[k];
-        if (m < 0) return fail(c, OVL_E_ARG, "contig %d: offsets decrease", k);
-        sh->max_m = std::max(sh->max_m, m);
-    }
-    if (n_contigs > 0) sh->c_total = c_off[n_contigs] - c_off[0];
-    if ((sh->max_n > 0 && !reads) || (sh->max_m > 0 && !contigs)) return fail(c, OVL_E_ARG, "NULL sequence");
-    if (sh->max_n > 0xFFFFF || sh->max_m > 0xFFFFF ||
-        std::max<int64_t>(0, match) * std::min(sh->max_n, sh->max_m) >= (int64_t(1) << 24))
+    if (int rc = check_seq_sets(c, reads, r_off, n_reads, contigs, c_off, n_contigs, sh)) return rc;
+    if (!local_limits_ok(sh->max_n, sh->max_m, match))
         return fail(c, OVL_E_UNSUPPORTED, "read depth: lengths < 2^20 and match * min(n, m) < 2^24 required");
     if (sh->c_total >= (int64_t(1) << 31))
         return fail(c, OVL_E_UNSUPPORTED, "read depth: the contigs together must stay below 2^31 bases");
@@ -57,71 +39,6 @@ void zero_outputs(int32_t n_reads, int32_t n_contigs, int32_t* best_score, int32
     }
     if (tie_bits) std::fill(tie_bits, tie_bits + (int64_t)n_reads * words, 0u);
     if (scores) std::fill(scores, scores + (int64_t)n_reads * n_contigs, 0);
-}
-
-struct Cell {
-    int64_t score;
-    int32_t bi, bj;
-};
-
-// aligners.py:106-137 over q[0..n) x t[0..m) with one carried row: the best score and the first strict maximum
-Cell fill_host(const uint8_t* q, int32_t n, const uint8_t* t, int32_t m, int64_t match, int64_t mismatch,
-               int64_t indel, std::vector<int64_t>& row) {
-    Cell best{0, 0, 0};
-    row.assign((size_t)m + 1, 0);
-    for (int32_t i = 1; i <= n; ++i) {
-        int64_t diag = 0, left = 0;
-        for (int32_t j = 1; j <= m; ++j) {
-            const int64_t upv = row[(size_t)j];
-            const int64_t d = diag + (q[i - 1] == t[j - 1] ? match : mismatch), u = upv + indel, l = left + indel;
-            int64_t v = 0;
-            if (d >= u && d >= l && d >= 0) v = d;
-            else if (u >= l && u >= 0) v = u;
-            else if (l >= 0) v = l;
-            diag = upv;
-            row[(size_t)j] = left = v;
-            if (v > best.score) best = {v, i, j};
-        }
-    }
-    return best;
-}
-
-// aligners.py:139-161 from (bi, bj): the column where the walk stops.  Only rows <= bi and columns <= bj matter.
-int32_t walk_host(const uint8_t* q, const uint8_t* t, int32_t bi, int32_t bj, int64_t match, int64_t mismatch,
-                  int64_t indel) {
-    const size_t pitch = (size_t)bj + 1;
-    std::vector<int8_t> tb(((size_t)bi + 1) * pitch, 0);
-    std::vector<int64_t> row(pitch, 0);
-    for (int32_t i = 1; i <= bi; ++i) {
-        int64_t diag = 0, left = 0;
-        for (int32_t j = 1; j <= bj; ++j) {
-            const int64_t upv = row[(size_t)j];
-            const int64_t d = diag + (q[i - 1] == t[j - 1] ? match : mismatch), u = upv + indel, l = left + indel;
-            int64_t v = 0;
-            int8_t op = 0;
-            if (d >= u && d >= l && d >= 0) { v = d; op = 1; }
-            else if (u >= l && u >= 0) { v = u; op = 2; }
-            else if (l >= 0) { v = l; op = 3; }
-            diag = upv;
-            row[(size_t)j] = left = v;
-            tb[(size_t)i * pitch + (size_t)j] = v > 0 ? op : 0;
-        }
-    }
-    int32_t i = bi, j = bj;
-    while (i > 0 && j > 0) {
-        const int8_t op = tb[(size_t)i * pitch + (size_t)j];
-        if (op == 1) { --i; --j; }
-        else if (op == 2) --i;
-        else if (op == 3) --j;
-        else break;
-    }
-    return j;
-}
-
-// scores at or below -2^40 all mean "never taken" for cells below 2^24, and keep int64 sums far from overflow
-inline int64_t clamp_score(int64_t v) {
-    const int64_t lim = int64_t(1) << 40;
-    return v < -lim ? -lim : (v > lim ? lim : v);
 }
 
 // one read's running selection over the contigs in order (plots.py:126-131)
@@ -149,7 +66,7 @@ OVL_API int ovl_read_best_host(const uint8_t* reads, const int64_t* r_off, int32
                                int32_t* n_best, int32_t* best_start, int32_t* best_end, uint32_t* tie_bits,
                                int32_t* scores) {
     const ovl_ctx* none = nullptr;
-    Shape sh;
+    SeqShape sh;
     const int rc = check_read_best(none, reads, r_off, n_reads, contigs, c_off, n_contigs, read_length, match,
                                    best_score, first_best, n_best, best_start, best_end, &sh);
     if (rc != OVL_OK) return rc;
@@ -157,6 +74,7 @@ OVL_API int ovl_read_best_host(const uint8_t* reads, const int64_t* r_off, int32
     const int64_t words = ((int64_t)n_contigs + 31) / 32;
     const int64_t ind = clamp_score(indel);
     std::vector<int64_t> row;
+    std::vector<int8_t> tb;
     try {
         for (int32_t r = 0; r < n_reads && n_contigs > 0; ++r) {
             const uint8_t* q = reads + r_off[r];
@@ -166,14 +84,19 @@ OVL_API int ovl_read_best_host(const uint8_t* reads, const int64_t* r_off, int32
             for (int32_t c = 0; c < n_contigs; ++c) {
                 const int64_t m = c_off[c + 1] - c_off[c];
                 const Window w = window_of(L, m, read_length);
-                const Cell cell = fill_host(q, L, contigs + c_off[c] + w.lo, w.len, match, mismatch, ind, row);
+                const Cell cell =
+                    sw_fill_host<false>(q, L, contigs + c_off[c] + w.lo, w.len, match, mismatch, ind, row, nullptr);
                 if (scores) scores[(int64_t)r * n_contigs + c] = (int32_t)cell.score;
                 p.take(c, cell.score, cell.bi, cell.bj, bits);
             }
             const int64_t m = c_off[p.first + 1] - c_off[p.first];
             const Window w = window_of(L, m, read_length);
             int32_t sj = 0;
-            if (p.best > 0) sj = walk_host(q, contigs + c_off[p.first] + w.lo, p.bi, p.bj, match, mismatch, ind);
+            if (p.best > 0) {
+                // only rows <= bi and columns <= bj matter to the walk: the table of that corner
+                sw_fill_host<true>(q, p.bi, contigs + c_off[p.first] + w.lo, p.bj, match, mismatch, ind, row, &tb);
+                sj = sw_walk_host(tb, p.bj, p.bi, p.bj, [](int8_t) {});
+            }
             best_score[r] = (int32_t)p.best;
             first_best[r] = p.first;
             n_best[r] = p.n;
@@ -196,7 +119,7 @@ OVL_API int ovl_read_best(ovl_ctx* ctx, const uint8_t* reads, const int64_t* r_o
     Dev* c = ctx->devs[0];
     DeviceGuard guard;
     const auto t_call = std::chrono::steady_clock::now();
-    Shape sh;
+    SeqShape sh;
     const int rc = check_read_best(c, reads, r_off, n_reads, contigs, c_off, n_contigs, read_length, match,
                                    best_score, first_best, n_best, best_start, best_end, &sh);
     if (rc != OVL_OK) return rc;
@@ -299,8 +222,7 @@ OVL_API int ovl_read_best(ovl_ctx* ctx, const uint8_t* reads, const int64_t* r_o
         uint32_t* d_cell = reinterpret_cast<uint32_t*>(d_nbest + pitch);
         const int32_t groups = (int32_t)(pitch / 64);
         if (ctx->timing) {
-            for (hipEvent_t& e : c->rb_ev)
-                if (!e) HIPCHK(c, hipEventCreate(&e));
+            HIPCHK(c, ensure_events(c->rb_ev));
             HIPCHK(c, hipEventRecord(c->rb_ev[0], s));
         }
         std::vector<int32_t> h_tile;

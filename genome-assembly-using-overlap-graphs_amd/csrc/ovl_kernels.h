@@ -163,13 +163,21 @@ extern "C" hipError_t ovl_launch_local(const uint8_t* q, int32_t n, const uint8_
 // *counter (zeroed by the caller).  Item k aligns q[q_off .. q_off + n) to ref[win_lo .. win_lo + m), n, m >= 1,
 // in int32 cells.  Per wavefront w: rows + w * row_pitch (int32; row_pitch 0: the row lives in the launch's
 // lds_row_bytes of dynamic LDS), and with a traceback slabs + w * slab_pitch (bytes, >= the largest item's
-// n_strips x 64 * n_chunks x 64) and wave_ops + w * wave_ops_pitch (>= the largest n + m).  out: 8 int32 per
-// item at out[8 * item.out]: score, end_i, end_j, start_i, start_j, n_ops, and the 64-bit position of its ops
-// in `ops` (reserved from *ops_total, zeroed by the caller).  slabs == NULL: score only (starts = ends, no ops).
+// n_strips x 64 * n_chunks x 64) and wave_ops + w * wave_ops_pitch (>= the largest n + m).  out: one record per
+// item at out[item.out], its ops at ops_base() of `ops` (reserved from *ops_total, zeroed by the caller).
+// slabs == NULL: score only (starts = ends, no ops).
 struct OvlLocalBatchItem {
     int64_t q_off;
     int32_t n, win_lo, m, out;
 };
+struct OvlLocalBatchRecord {
+    int32_t score, end_i, end_j, start_i, start_j, n_ops;
+    uint32_t ops_lo, ops_hi;  // the 64-bit position of the item's ops
+    __host__ __device__ unsigned long long ops_base() const {
+        return (unsigned long long)ops_lo | ((unsigned long long)ops_hi << 32);
+    }
+};
+static_assert(sizeof(OvlLocalBatchRecord) == 32, "the batch record is eight 32-bit words");
 struct OvlLocalBatchArgs {
     const uint8_t* q;
     const uint8_t* ref;
@@ -184,7 +192,7 @@ struct OvlLocalBatchArgs {
     int64_t slab_pitch;
     int8_t* wave_ops;
     int64_t wave_ops_pitch;
-    int32_t* out;
+    OvlLocalBatchRecord* out;
     int8_t* ops;
 };
 extern "C" hipError_t ovl_launch_local_batch(const OvlLocalBatchArgs* a, int32_t waves, uint32_t lds_row_bytes,
@@ -219,9 +227,10 @@ extern "C" hipError_t ovl_launch_read_best_fold(const OvlLocalLaneArgs* a, int32
                                                 uint32_t* tie_bits, hipStream_t stream);
 
 // consensus (ovl_consensus.hip).  pileup: one-wavefront blocks take items[0 .. n_items) of a finished batch launch
-// from *counter (zeroed by the caller), read each item's record out[8 * item.out] = {., bi, bj, ., ., cnt, base lo,
-// base hi} and its walk ops[base .. base + cnt) (1 diag, 2 up, 3 left from cell (bi, bj)), and add one vote per op
-// to counts[(item.win_lo + column) * 6 + channel]: A, C, G, T by the query byte of a diag, 4 for a left, 5 for an up.
+// from *counter (zeroed by the caller), read each item's record out[item.out] (end_i, end_j = bi, bj; n_ops = cnt;
+// ops_base() = base) and its walk ops[base .. base + cnt) (1 diag, 2 up, 3 left from cell (bi, bj)), and add one
+// vote per op to counts[(item.win_lo + column) * 6 + channel]: A, C, G, T by the query byte of a diag, 4 for a left,
+// 5 for an up.
 // ctr[0] counts the diag ops whose byte is none of ACGT, ctr[2] the ops that fell outside their item (none, unless
 // the walk is broken; they cast no vote).  add: counts[hits[i]] += 1.  vote: called[b] for b < n_bases from
 // counts[6 * b ..] and ref[b] (the largest of the four base channels once they hold min_depth votes; ties to the
@@ -229,7 +238,7 @@ extern "C" hipError_t ovl_launch_read_best_fold(const OvlLocalLaneArgs* a, int32
 struct OvlPileupArgs {
     const OvlLocalBatchItem* items;
     const uint8_t* q;
-    const int32_t* out;
+    const OvlLocalBatchRecord* out;
     const int8_t* ops;
     int32_t n_items;
     uint32_t* counter;

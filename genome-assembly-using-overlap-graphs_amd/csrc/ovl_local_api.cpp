@@ -1,6 +1,7 @@
 // ovl_local_api.cpp — single alignments (ovl_ctx.h): one pair's full DP with its traceback table (ovl_align_one)
-// and local alignment of two sequences (ovl_local_align, ovl_local.hip).
-#include "ovl_ctx.h"
+// and local alignment of two sequences (ovl_local_align, ovl_local.hip) or of many queries against windows of one
+// reference (ovl_local_align_batch, ovl_local_batch.hip), routed by ovl_local_host.h's local_route.
+#include "ovl_local_host.h"
 
 OVL_API int ovl_align_one(ovl_ctx* ctx, int32_t a, int32_t b, int32_t match, int32_t mismatch, int64_t indel,
                           int32_t* out_score, int32_t* out_end, int8_t* traceback) {
@@ -72,19 +73,14 @@ OVL_API int ovl_local_align(ovl_ctx* ctx, const uint8_t* query, int32_t n, const
     if (!out_score || !out_end_i || !out_end_j || !out_start_i || !out_start_j || !out_n_ops)
         return fail(c, OVL_E_ARG, "NULL output pointer");
     if (ops && ops_cap < 0) return fail(c, OVL_E_ARG, "ops_cap < 0");
-    // best-cell key: 24-bit score, 20-bit row and column
-    const int64_t mn = std::min(n, m);
-    const int64_t top = std::max<int64_t>(0, match) * mn;
-    if (n > 0xFFFFF || m > 0xFFFFF || top >= (int64_t(1) << 24))
+    if (!local_limits_ok(n, m, match))
         return fail(c, OVL_E_UNSUPPORTED, "local alignment: lengths < 2^20 and match * min(n, m) < 2^24 required");
     *out_score = 0; *out_end_i = 0; *out_end_j = 0; *out_start_i = 0; *out_start_j = 0; *out_n_ops = 0;
     if (n == 0 || m == 0) return OVL_OK;
-    const int64_t M = std::max(std::max(iabs64(match), iabs64(mismatch)), iabs64(indel));
-    const int wide = (M >= (int64_t(1) << 30) || top + M >= (int64_t(1) << 31)) ? 1 : 0;
-    const int32_t n_strips = (n + 63) / 64;
-    const int64_t n_chunks = ((int64_t)m + 126) / 64;  // 64-step chunks covering tau = 0 .. m + 62
-    const int64_t steps = n_chunks * 64;                // traceback pitch per strip
-    const size_t tb_bytes = (size_t)n_strips * (size_t)steps * 64;
+    const int wide = local_wide(n, m, match, mismatch, indel) ? 1 : 0;
+    const int32_t n_strips = (int32_t)local_strips(n);
+    const int64_t steps = local_steps(m);  // traceback pitch per strip
+    const size_t tb_bytes = local_table_bytes(n, m);
     const size_t row_bytes = (size_t)n_strips * (size_t)(steps + 64) * sizeof(uint64_t);
     if (ops && tb_bytes > (size_t(8) << 30))
         return fail(c, OVL_E_UNSUPPORTED, "local alignment traceback table would exceed 8 GiB");
@@ -173,7 +169,7 @@ OVL_API int ovl_local_align(ovl_ctx* ctx, const uint8_t* query, int32_t n, const
     return OVL_OK;
 }
 
-// One launch of the batch kernel, issued and not waited for (ovl_ctx.h): the records and the packed ops stay in
+// One launch of the batch kernel, issued and not waited for (ovl_local_host.h): the records and the packed ops stay in
 // device memory for the caller -- ovl_local_align_batch copies them back, ovl_consensus piles them up in place.
 int local_batch_launch(ovl_ctx* ctx, Dev* c, const uint8_t* queries, const int64_t* q_off,
                        std::vector<LocalBatchQuery>& batch, const uint8_t* reference, int32_t ref_len,
@@ -186,9 +182,8 @@ int local_batch_launch(ovl_ctx* ctx, Dev* c, const uint8_t* queries, const int64
     size_t slab_max = 0;
     int64_t row_max = 0, nm_max = 0, nm_sum = 0, q_bytes = 0;
     for (const LocalBatchQuery& x : batch) {
-        const int64_t n_strips = ((int64_t)x.n + 63) / 64, steps = (((int64_t)x.m + 126) / 64) * 64;
-        slab_max = std::max(slab_max, (size_t)n_strips * (size_t)steps * 64);
-        row_max = std::max(row_max, steps);
+        slab_max = std::max(slab_max, local_table_bytes(x.n, x.m));
+        row_max = std::max(row_max, local_steps(x.m));
         nm_max = std::max<int64_t>(nm_max, (int64_t)x.n + x.m);
         nm_sum += (int64_t)x.n + x.m;
         q_bytes += x.n;
@@ -216,7 +211,7 @@ int local_batch_launch(ovl_ctx* ctx, Dev* c, const uint8_t* queries, const int64
     hipStream_t s = c->stream;
     HIPCHK(c, ensure(c->lb_in, blob.size()));
     HIPCHK(c, ensure(c->lb_ctr, 16));
-    HIPCHK(c, ensure(c->lb_out, sizeof(int32_t) * 8 * (size_t)nb));
+    HIPCHK(c, ensure(c->lb_out, sizeof(OvlLocalBatchRecord) * (size_t)nb));
     if (!row_lds) HIPCHK(c, ensure(c->lb_rows, sizeof(int32_t) * (size_t)row_max * (size_t)waves));
     if (with_ops) {
         HIPCHK(c, ensure(c->lb_slabs, slab_pitch * (size_t)waves));
@@ -241,11 +236,10 @@ int local_batch_launch(ovl_ctx* ctx, Dev* c, const uint8_t* queries, const int64
     a.slab_pitch = (int64_t)slab_pitch;
     a.wave_ops = with_ops ? as<int8_t>(c->lb_wops) : nullptr;
     a.wave_ops_pitch = wops_pitch;
-    a.out = as<int32_t>(c->lb_out);
+    a.out = as<OvlLocalBatchRecord>(c->lb_out);
     a.ops = with_ops ? as<int8_t>(c->lb_ops) : nullptr;
     if (ctx->timing) {
-        for (hipEvent_t& e : c->lb_ev)
-            if (!e) HIPCHK(c, hipEventCreate(&e));
+        HIPCHK(c, ensure_events(c->lb_ev));
         HIPCHK(c, hipEventRecord(c->lb_ev[0], s));
     }
     HIPCHK(c, ovl_launch_local_batch(&a, (int32_t)waves, row_lds ? (uint32_t)(row_max * 4) : 0u, s));
@@ -278,7 +272,6 @@ OVL_API int ovl_local_align_batch(ovl_ctx* ctx, const uint8_t* queries, const in
         return fail(c, OVL_E_ARG, "NULL output pointer");
     if (ops && !ops_off) return fail(c, OVL_E_ARG, "ops without ops_off");
     // every argument check comes before anything is written or run
-    const int64_t pos_match = std::max<int64_t>(0, match);
     for (int32_t k = 0; k < n_queries; ++k) {
         const int64_t n = q_off[k + 1] - q_off[k];
         if (q_off[k] < 0 || n < 0) return fail(c, OVL_E_ARG, "query %d: bad offsets", k);
@@ -293,30 +286,24 @@ OVL_API int ovl_local_align_batch(ovl_ctx* ctx, const uint8_t* queries, const in
     }
     for (int32_t k = 0; k < n_queries; ++k) {
         const int64_t n = q_off[k + 1] - q_off[k], m = win_lo ? win_len[k] : ref_len;
-        if (n > 0xFFFFF || m > 0xFFFFF || pos_match * std::min(n, m) >= (int64_t(1) << 24))
+        if (!local_limits_ok(n, m, match))
             return fail(c, OVL_E_UNSUPPORTED,
                         "local alignment, query %d: lengths < 2^20 and match * min(n, m) < 2^24 required", k);
     }
     ctx->x_lb_batched = ctx->x_lb_single = ctx->x_lb_waves = 0;
     ctx->t_kernel_ms = ctx->t_call_ms = 0.0;
-    // route the queries
-    const int64_t M = std::max(std::max(iabs64(match), iabs64(mismatch)), iabs64(indel));
+    // route the queries: the slab limit holds only where a traceback is asked for
     std::vector<LocalBatchQuery> batch;
     std::vector<int32_t> single;
     for (int32_t k = 0; k < n_queries; ++k) {
         out_score[k] = 0; out_end_i[k] = 0; out_end_j[k] = 0; out_start_i[k] = 0; out_start_j[k] = 0;
         out_n_ops[k] = 0;
         const int64_t n = q_off[k + 1] - q_off[k], m = win_lo ? win_len[k] : ref_len;
-        if (n == 0 || m == 0) continue;
-        const int64_t top = pos_match * std::min(n, m);
-        const bool wide = M >= (int64_t(1) << 30) || top + M >= (int64_t(1) << 31);
-        const int64_t n_strips = (n + 63) / 64, steps = ((m + 126) / 64) * 64;
-        const size_t table = (size_t)n_strips * (size_t)steps * 64;
-        if (wide || n_strips > kBatchMaxStrips || (ops && table > kBatchSlabMax)) {
+        const LocalRoute route = local_route(n, m, match, mismatch, indel, ops != nullptr);
+        if (route == LocalRoute::Single)
             single.push_back(k);
-            continue;
-        }
-        batch.push_back({k, (int32_t)n, win_lo ? win_lo[k] : 0, (int32_t)m, n * m});
+        else if (route == LocalRoute::Batch)
+            batch.push_back({k, (int32_t)n, win_lo ? win_lo[k] : 0, (int32_t)m, n * m});
     }
     if (!batch.empty()) {
         LocalBatchRun run;
@@ -327,9 +314,9 @@ OVL_API int ovl_local_align_batch(ovl_ctx* ctx, const uint8_t* queries, const in
         hipStream_t s = c->stream;
         const int32_t nb = run.nb;
         const int64_t nm_sum = run.nm_sum;
-        std::vector<int32_t> res((size_t)nb * 8);
+        std::vector<OvlLocalBatchRecord> res((size_t)nb);
         unsigned long long ctr[2] = {0, 0};
-        HIPCHK(c, hipMemcpyAsync(res.data(), c->lb_out.p, res.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(res.data(), c->lb_out.p, res.size() * sizeof(res[0]), hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipMemcpyAsync(ctr, c->lb_ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipStreamSynchronize(s));
         if (ctx->timing) {
@@ -348,17 +335,16 @@ OVL_API int ovl_local_align_batch(ovl_ctx* ctx, const uint8_t* queries, const in
         }
         for (int32_t b = 0; b < nb; ++b) {
             const int32_t k = batch[b].k;
-            const int32_t* o = res.data() + (size_t)b * 8;
-            out_score[k] = o[0]; out_end_i[k] = o[1]; out_end_j[k] = o[2];
-            out_start_i[k] = ops ? o[3] : o[1];
-            out_start_j[k] = ops ? o[4] : o[2];
-            if (ops && o[5] > 0) {
-                const unsigned long long base = (unsigned long long)(uint32_t)o[6] |
-                                                ((unsigned long long)(uint32_t)o[7] << 32);
-                if (base + (unsigned long long)o[5] > total || o[5] > batch[b].n + batch[b].m)
+            const OvlLocalBatchRecord& o = res[(size_t)b];
+            out_score[k] = o.score; out_end_i[k] = o.end_i; out_end_j[k] = o.end_j;
+            out_start_i[k] = ops ? o.start_i : o.end_i;
+            out_start_j[k] = ops ? o.start_j : o.end_j;
+            if (ops && o.n_ops > 0) {
+                const unsigned long long base = o.ops_base();
+                if (base + (unsigned long long)o.n_ops > total || o.n_ops > batch[b].n + batch[b].m)
                     return fail(c, OVL_E_INTERNAL, "batched local alignment: query %d's ops lie outside the buffer", k);
-                memcpy(ops + ops_off[k], packed.data() + base, (size_t)o[5]);
-                out_n_ops[k] = o[5];
+                memcpy(ops + ops_off[k], packed.data() + base, (size_t)o.n_ops);
+                out_n_ops[k] = o.n_ops;
             }
         }
         ctx->x_lb_batched = nb;

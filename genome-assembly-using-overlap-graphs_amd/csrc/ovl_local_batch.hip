@@ -29,7 +29,7 @@
 //
 // The ops of all queries are packed: a wavefront walks into a scratch of its own, then reserves [base, base +
 // count) of one output buffer with an atomic add and copies the ops there with all lanes, so only the ops that
-// exist and eight int32 per query cross the link.
+// exist and one OvlLocalBatchRecord per query cross the link.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -207,9 +207,9 @@ __global__ __launch_bounds__(64) void sw_batch_kernel(OvlLocalBatchArgs a) {
             }
         }
         if (lane == 0) {
-            int32_t* o = a.out + (int64_t)it.out * 8;
-            o[0] = score; o[1] = bi; o[2] = bjq; o[3] = wi; o[4] = wj; o[5] = cnt;
-            o[6] = (int32_t)(uint32_t)base; o[7] = (int32_t)(uint32_t)(base >> 32);
+            OvlLocalBatchRecord* o = a.out + it.out;
+            o->score = score; o->end_i = bi; o->end_j = bjq; o->start_i = wi; o->start_j = wj; o->n_ops = cnt;
+            o->ops_lo = (uint32_t)base; o->ops_hi = (uint32_t)(base >> 32);
         }
         // the next query's stores to the row, the slab and the scratch follow this query's loads of them in
         // program order, and those loads' values have been used

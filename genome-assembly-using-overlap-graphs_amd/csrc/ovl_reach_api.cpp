@@ -145,8 +145,7 @@ OVL_API int ovl_reach_reduce(ovl_ctx* ctx, const int64_t* off, const int32_t* he
     const int32_t mark_window = std::min(words, window_words);
     const int32_t mark_group = pow2_at_least(mark_window, 64);
     if (ctx->timing) {
-        for (hipEvent_t& e : c->rc_ev)
-            if (!e) HIPCHK(c, hipEventCreate(&e));
+        HIPCHK(c, ensure_events(c->rc_ev));
         HIPCHK(c, hipEventRecord(c->rc_ev[0], s));
     }
     HIPCHK(c, ovl_launch_reach_fill(&a, s));

@@ -105,8 +105,7 @@ OVL_API int ovl_transitive_reduce(ovl_ctx* ctx, const int64_t* off, const int32_
     a.reduced = as<uint8_t>(c->tr_out);
     const int32_t blocks = (int32_t)std::min<int64_t>((int64_t)order.size(), (int64_t)c->cu_count * kReduceBlocksPerCu);
     if (ctx->timing) {
-        for (hipEvent_t& e : c->tr_ev)
-            if (!e) HIPCHK(c, hipEventCreate(&e));
+        HIPCHK(c, ensure_events(c->tr_ev));
         HIPCHK(c, hipEventRecord(c->tr_ev[0], s));
     }
     HIPCHK(c, ovl_launch_reduce(&a, blocks, s));

@@ -5,29 +5,13 @@
 //
 // compiles this file and ovl_consensus_api.cpp with -fsanitize=address,undefined (host side) and runs the result.
 // It runs hand cases with known answers (the golden file's shapes in miniature), random reads and contigs against
-// a plain full-table restatement of aligners.py:85-202 with the pileup and the vote written out again, and every
-// error case (outputs untouched).  The device call is linked but never made: its launches, the alignment entry
-// points and the context helpers are stubs here.
-#include <cstdarg>
+// a plain full-table restatement of aligners.py:85-202 with the pileup and the vote written out again, every
+// error case (outputs untouched), and the routing rule of ovl_local_host.h at its boundaries.  The device call is
+// linked but never made: its launches and the alignment entry points are stubs here, the context helpers in
+// host_check.h.
+#include "host_check.h"
+#include "ovl_local_host.h"
 
-#include "ovl_ctx.h"
-
-thread_local std::string g_err;
-
-int fail(const ovl_ctx*, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-int fail(const Dev*, int code, const char* fmt, ...) {
-    g_err = fmt;
-    return code;
-}
-void quiet(ovl_ctx*) {}
 int local_batch_launch(ovl_ctx*, Dev*, const uint8_t*, const int64_t*, std::vector<LocalBatchQuery>&, const uint8_t*,
                        int32_t, const uint8_t*, bool, int32_t, int32_t, int32_t, LocalBatchRun*) {
     return OVL_E_UNSUPPORTED;
@@ -46,28 +30,6 @@ extern "C" hipError_t ovl_launch_consensus_vote(const uint8_t*, const int32_t*, 
                                                 unsigned long long*, hipStream_t) {
     return hipErrorNotSupported;
 }
-
-static int g_failed = 0;
-#define EXPECT(cond)                                                        \
-    do {                                                                    \
-        if (!(cond)) {                                                      \
-            fprintf(stderr, "%s:%d: %s failed\n", __FILE__, __LINE__, #cond); \
-            ++g_failed;                                                     \
-        }                                                                   \
-    } while (0)
-
-struct Seqs {
-    std::vector<uint8_t> bytes;
-    std::vector<int64_t> off{0};
-    void add(const std::string& s) {
-        bytes.insert(bytes.end(), s.begin(), s.end());
-        off.push_back((int64_t)bytes.size());
-    }
-    int32_t n() const { return (int32_t)off.size() - 1; }
-    std::string at(int32_t k) const { return std::string(bytes.begin() + off[k], bytes.begin() + off[k + 1]); }
-    const uint8_t* data() const { return bytes.empty() ? nullptr : bytes.data(); }
-    int64_t total() const { return (int64_t)bytes.size(); }
-};
 
 struct Out {
     std::vector<int32_t> counts, aln;
@@ -100,33 +62,17 @@ static Aln pile_plain(const std::string& q, const std::string& contig, int32_t r
         lo = cm - L;
         t = contig.substr((size_t)lo);
     }
-    const size_t n = q.size(), m = t.size();
-    std::vector<std::vector<int64_t>> dp(n + 1, std::vector<int64_t>(m + 1, 0));
-    std::vector<std::vector<int>> tb(n + 1, std::vector<int>(m + 1, 0));
-    int64_t best = 0;
-    size_t bi = 0, bj = 0;
-    for (size_t i = 1; i <= n; ++i)
-        for (size_t j = 1; j <= m; ++j) {
-            const int64_t d = dp[i - 1][j - 1] + (q[i - 1] == t[j - 1] ? match : mismatch);
-            const int64_t u = dp[i - 1][j] + indel, l = dp[i][j - 1] + indel;
-            if (d >= u && d >= l && d >= 0) { dp[i][j] = d; tb[i][j] = 1; }
-            else if (u >= l && u >= 0) { dp[i][j] = u; tb[i][j] = 2; }
-            else if (l >= 0) { dp[i][j] = l; tb[i][j] = 3; }
-            if (dp[i][j] > best) { best = dp[i][j]; bi = i; bj = j; }
-        }
-    size_t i = bi, j = bj;
-    while (i > 0 && j > 0 && dp[i][j] > 0) {
+    const Triple a = local_plain(q, t, match, mismatch, indel, [&](size_t i, size_t j, int op) {
         const int64_t at = (base0 + lo + (int64_t)j - 1) * 6;
-        if (tb[i][j] == 1) {
+        if (op == 1) {
             if (chan(q[i - 1]) >= 0) ++counts[(size_t)(at + chan(q[i - 1]))];
             else ++other;
-            --i; --j;
-        } else if (tb[i][j] == 2) { ++counts[(size_t)(at + 5)]; --i; }
-        else if (tb[i][j] == 3) { ++counts[(size_t)(at + 4)]; --j; }
-        else break;
-    }
-    if (best == 0) return {0, 0, 0};
-    return {best, lo + (int64_t)j, lo + (int64_t)bj};
+        } else {
+            ++counts[(size_t)(at + (op == 2 ? 5 : 4))];
+        }
+    });
+    if (a.score == 0) return {0, 0, 0};
+    return {a.score, lo + a.start, lo + a.end};
 }
 
 static void expect_matches_plain(const Seqs& rd, const Seqs& ct, const std::vector<int32_t>& place,
@@ -304,6 +250,27 @@ int main() {
         EXPECT(call(rd.data(), ro, 1, ct.data(), huge_off, 1, place, 4, 10, 3, cl, nc) == OVL_E_UNSUPPORTED);
         EXPECT(untouched());
         EXPECT(!g_err.empty());
+    }
+    // the routing rule of ovl_local_align_batch and ovl_consensus (ovl_local_host.h), at each of its boundaries
+    {
+        using R = LocalRoute;
+        // 16 strips of 64 rows stay on the batch kernel, with or without a traceback
+        EXPECT(local_route(1024, 1100, 10, -1, -1, true) == R::Batch);
+        EXPECT(local_route(1025, 1100, 10, -1, -1, true) == R::Single);
+        EXPECT(local_route(1025, 1100, 10, -1, -1, false) == R::Single);
+        // 16 strips x 65,536 steps x 64 bytes is kBatchSlabMax exactly: m + 126 reaches 65,600 at m = 65,474
+        EXPECT(local_table_bytes(1024, 65473) == kBatchSlabMax);
+        EXPECT(local_route(1024, 65473, 10, -1, -1, true) == R::Batch);
+        EXPECT(local_route(1024, 65474, 10, -1, -1, true) == R::Single);
+        EXPECT(local_route(1024, 65474, 10, -1, -1, false) == R::Batch);  // no table, no slab limit
+        // wide scoring: |indel| = 2^30, and top + M = 2^31 (top = 1024 * 1,572,864 = 2^31 - 2^29, M = 2^29)
+        EXPECT(local_route(100, 100, 10, -1, -(int64_t(1) << 30), true) == R::Single);
+        EXPECT(local_route(100, 100, 10, -1, -(int64_t(1) << 30) + 1, true) == R::Batch);
+        EXPECT(local_route(1024, 1024, 1572864, -(1 << 29), -1, false) == R::Single);
+        EXPECT(local_route(1024, 1024, 1572864, -(1 << 29) + 1, -1, false) == R::Batch);
+        EXPECT(local_route(0, 100, 10, -1, -1, true) == R::Empty);
+        EXPECT(local_route(100, 0, 10, -1, -1, false) == R::Empty);
+        EXPECT(local_route(0, 0, 1572864, -1, -(int64_t(1) << 30), true) == R::Empty);
     }
     if (g_failed) {
         fprintf(stderr, "consensus_host_check: %d checks failed\n", g_failed);

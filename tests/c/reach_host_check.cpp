@@ -7,26 +7,8 @@
 // runs hand graphs with known answers, size sweeps across the word boundary against a plain boolean closure, and
 // every error case (outputs untouched).  The device call is linked but never made: its launches and the context
 // helpers are stubs here.
-#include <cstdarg>
+#include "host_check.h"
 
-#include "ovl_ctx.h"
-
-thread_local std::string g_err;
-
-int fail(const ovl_ctx*, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-int fail(const Dev*, int code, const char* fmt, ...) {
-    g_err = fmt;
-    return code;
-}
-void quiet(ovl_ctx*) {}
 extern "C" hipError_t ovl_launch_reach_fill(const OvlReachArgs*, hipStream_t) { return hipErrorNotSupported; }
 extern "C" hipError_t ovl_launch_reach_pivot(const OvlReachArgs*, int32_t, hipStream_t) { return hipErrorNotSupported; }
 extern "C" hipError_t ovl_launch_reach_update(const OvlReachArgs*, int32_t, int32_t, hipStream_t) {
@@ -35,15 +17,6 @@ extern "C" hipError_t ovl_launch_reach_update(const OvlReachArgs*, int32_t, int3
 extern "C" hipError_t ovl_launch_reach_mark(const OvlReachArgs*, int32_t, int32_t, hipStream_t) {
     return hipErrorNotSupported;
 }
-
-static int g_failed = 0;
-#define EXPECT(cond)                                                        \
-    do {                                                                    \
-        if (!(cond)) {                                                      \
-            fprintf(stderr, "%s:%d: %s failed\n", __FILE__, __LINE__, #cond); \
-            ++g_failed;                                                     \
-        }                                                                   \
-    } while (0)
 
 struct Graph {
     std::vector<int64_t> off;

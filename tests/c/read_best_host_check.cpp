@@ -7,26 +7,8 @@
 // runs hand cases with known answers, random reads and contigs against a plain full-table restatement of
 // aligners.py:85-202, and every error case (outputs untouched).  The device call is linked but never made: its
 // launches, the batched alignment and the context helpers are stubs here.
-#include <cstdarg>
+#include "host_check.h"
 
-#include "ovl_ctx.h"
-
-thread_local std::string g_err;
-
-int fail(const ovl_ctx*, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-int fail(const Dev*, int code, const char* fmt, ...) {
-    g_err = fmt;
-    return code;
-}
-void quiet(ovl_ctx*) {}
 extern "C" hipError_t ovl_launch_local_lane(const OvlLocalLaneArgs*, int32_t, int32_t, int32_t, hipStream_t) {
     return hipErrorNotSupported;
 }
@@ -38,57 +20,6 @@ extern "C" int ovl_local_align_batch(ovl_ctx*, const uint8_t*, const int64_t*, i
                                      const int32_t*, const int32_t*, int32_t, int32_t, int64_t, int32_t*, int32_t*,
                                      int32_t*, int32_t*, int32_t*, int8_t*, const int64_t*, int64_t*) {
     return OVL_E_UNSUPPORTED;
-}
-
-static int g_failed = 0;
-#define EXPECT(cond)                                                        \
-    do {                                                                    \
-        if (!(cond)) {                                                      \
-            fprintf(stderr, "%s:%d: %s failed\n", __FILE__, __LINE__, #cond); \
-            ++g_failed;                                                     \
-        }                                                                   \
-    } while (0)
-
-struct Seqs {
-    std::vector<uint8_t> bytes;
-    std::vector<int64_t> off{0};
-    void add(const std::string& s) {
-        bytes.insert(bytes.end(), s.begin(), s.end());
-        off.push_back((int64_t)bytes.size());
-    }
-    int32_t n() const { return (int32_t)off.size() - 1; }
-    std::string at(int32_t k) const { return std::string(bytes.begin() + off[k], bytes.begin() + off[k + 1]); }
-    const uint8_t* data() const { return bytes.empty() ? nullptr : bytes.data(); }
-};
-
-struct Triple {
-    int64_t score, start, end;
-};
-
-// aligners.py:85-167 on full tables
-static Triple local_plain(const std::string& q, const std::string& t, int64_t match, int64_t mismatch, int64_t indel) {
-    const size_t n = q.size(), m = t.size();
-    std::vector<std::vector<int64_t>> dp(n + 1, std::vector<int64_t>(m + 1, 0));
-    std::vector<std::vector<int>> tb(n + 1, std::vector<int>(m + 1, 0));
-    int64_t best = 0;
-    size_t bi = 0, bj = 0;
-    for (size_t i = 1; i <= n; ++i)
-        for (size_t j = 1; j <= m; ++j) {
-            const int64_t d = dp[i - 1][j - 1] + (q[i - 1] == t[j - 1] ? match : mismatch);
-            const int64_t u = dp[i - 1][j] + indel, l = dp[i][j - 1] + indel;
-            if (d >= u && d >= l && d >= 0) { dp[i][j] = d; tb[i][j] = 1; }
-            else if (u >= l && u >= 0) { dp[i][j] = u; tb[i][j] = 2; }
-            else if (l >= 0) { dp[i][j] = l; tb[i][j] = 3; }
-            if (dp[i][j] > best) { best = dp[i][j]; bi = i; bj = j; }
-        }
-    size_t i = bi, j = bj;
-    while (i > 0 && j > 0 && dp[i][j] > 0) {
-        if (tb[i][j] == 1) { --i; --j; }
-        else if (tb[i][j] == 2) --i;
-        else if (tb[i][j] == 3) --j;
-        else break;
-    }
-    return {best, (int64_t)j, (int64_t)bj};
 }
 
 // aligners.py:170-202

@@ -5,8 +5,9 @@ smaller shapes, against the rule restated over the oracle's aligned strings (tes
 The pileup kernel gives one wavefront one read and consumes its walk 64 ops at a time, carrying two prefix counts
 from chunk to chunk: the shapes here put walks of 63, 64, 65, 127, 128, 129 and 200 ops next to each other, runs of
 left and of up ops inside one chunk and across a chunk boundary, every window rule in one launch, many reads on the
-same columns, read counts around the wavefront boundary, several chunks of reads, and a read that leaves the batch
-kernel for the single-pair path.  One oracle restatement per scoring is computed once and shared.
+same columns, read counts around the wavefront boundary, several chunks of reads, a read that leaves the batch
+kernel for the single-pair path, and the two reads on either side of that boundary (1,024 and 1,025 bases) through
+both callers of the routing rule.  One oracle restatement per scoring is computed once and shared.
 """
 import random
 
@@ -200,6 +201,29 @@ def test_a_long_read_takes_the_single_pair_path(engine, pool):
     assert last["single_reads"] == 1 and last["batch_reads"] == 41
     assert dev["aln"][20, 0] > 10000 and dev["counts"][1000:, :4].sum() >= 1099 + 100 - 13
     assert last["ops"] == int(dev["counts"].sum()) + dev["n_other"]
+
+
+def test_the_strip_boundary_routes_alike_in_both_callers(engine):
+    """1,024 bases are the batch kernel's 16 strips, 1,025 one more: ovl_consensus and ovl_local_align_batch, which
+    share one routing rule, send the first read to the batch kernel and the second down the single-pair path."""
+    from ovlgraph.reads import read_genome_from_fasta
+    contig = read_genome_from_fasta()[3300:4400]
+    reads = []
+    for lo, n in ((30, 1024), (60, 1025)):
+        s = list(contig[lo:lo + n + 1])
+        for i in range(50, n, 101):
+            s[i] = "A" if s[i] != "A" else "C"
+        del s[700]
+        reads.append("".join(s))
+    assert [len(r) for r in reads] == [1024, 1025]
+    dev = check(engine, [contig], reads, [0, 0], READ_LENGTH, what="boundary")
+    last = engine.last_consensus()
+    assert last["batch_reads"] == 1 and last["single_reads"] == 1
+    assert dev["aln"][:, 0].min() > 9000
+    score = engine.local_align_batch(reads, contig, None, *SCORINGS[0])[0]
+    last = engine.last_local_batch()
+    assert last["batched"] == 1 and last["single"] == 1
+    assert score.tolist() == dev["aln"][:, 0].tolist()
 
 
 def test_polish_contigs_on_the_device_returns_the_true_sequences(engine):
