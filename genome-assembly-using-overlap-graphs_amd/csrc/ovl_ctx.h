@@ -60,6 +60,7 @@
 #include "ovl_resident.h"
 #include "ovl_worker.h"
 #include "ovl_digest.h"
+#include "ovl_score_range.h"
 
 #define OVL_API extern "C" __attribute__((visibility("default")))
 
@@ -173,6 +174,16 @@ constexpr size_t kExpandPart = size_t(1) << 14;
 
 struct ovl_ctx;
 
+// ovl_last_score_form: the form the first scoring launch of the last scoring call took (launch_score_chunk records
+// it while `open`, which the call's entry sets)
+struct ScoreForm {
+    bool open = false;
+    int32_t kernel = OVL_KERNEL_NONE, key64 = 0, wide = 0;
+    int32_t lane = 0, prof = 0, sfx = 0, ho = 0, h2 = 0;  // the lane-per-pair full DP and its arguments
+    int32_t band_form = -1, split = 0;                    // the band knob's form (-1: none) and two lanes per pair
+    int32_t rs_log2 = 0;                                  // the ungapped launch's rs_log2 (ungapped_rs_log2)
+};
+
 // Per-device state.
 struct Dev {
     ovl_ctx* owner = nullptr;
@@ -181,6 +192,7 @@ struct Dev {
     hipStream_t s_in = nullptr;    // host-array calls: the pair list's copies and decodes, beside the kernels
     int32_t cu_count = 256;
     Knobs k;
+    ScoreForm form;
     // resident reads
     int32_t n_reads = -1;
     int32_t lmax = 0;
@@ -367,8 +379,6 @@ inline void set_view(DevBuf& v, DevBuf& whole, size_t offset, size_t bytes) {
 
 template <typename T>
 T* as(DevBuf& b) { return reinterpret_cast<T*>(b.p); }
-
-inline int64_t iabs64(int64_t v) { return v < 0 ? -v : v; }
 
 // Restores the caller's current device when a public entry point returns.
 struct DeviceGuard {

@@ -140,7 +140,7 @@ OVL_API int ovl_read_best(ovl_ctx* ctx, const uint8_t* reads, const int64_t* r_o
         if (code[*p] < 0) code[*p] = n_codes++;
     for (const uint8_t* p = contigs + c_off[0]; p < contigs + c_off[C]; ++p)
         if (code[*p] < 0) code[*p] = n_codes++;
-    const bool lane_scoring = n_codes <= 255 && mismatch <= 0 && indel <= 0 && match < 65536;
+    const bool lane_scoring = read_best_lane_scoring_ok(n_codes, match, mismatch, indel);
     std::vector<int32_t> lane, other;  // the reads by path
     int64_t lane_max = 0;
     for (int32_t r = 0; r < n_reads; ++r) {

@@ -30,6 +30,7 @@
 #include <type_traits>
 
 #include "ovl_kernels.h"
+#include "ovl_score_range.h"
 
 namespace ovl {
 namespace {
@@ -1038,18 +1039,9 @@ extern "C" int32_t ovl_dp_lane_waves_per_simd(int32_t cw) { return cw == 32 ? 4 
 // the LDS hand-off (HO 2): rows rounded to 32, 4 bits per row, a dword per 8 rows, per wavefront of the block
 extern "C" int32_t ovl_dp_lane_lds_bytes(int32_t lcap) { return ((lcap + 31) & ~31) / 8 * 4 * 64 * 4; }
 
-// dp_lane_h2_kernel: a diagonal score's f16 encoding ends in a zero byte when its odd part is <= 7 (at most three
-// significant bits); the relative values stay below 65 * 15 + 128 < 2048 under HO 2's step bound
-static bool h2_byte_score(int64_t v) {
-    if (v == 0) return true;
-    uint64_t u = (uint64_t)(v < 0 ? -v : v);
-    while (!(u & 1)) u >>= 1;
-    return u <= 7 && (v < 0 ? -v : v) <= 2048;
-}
-
+// dp_lane_h2_kernel's scorings (ovl_score_range.h: both diagonal scores' f16 encodings end in a zero byte)
 extern "C" int32_t ovl_dp_lane_h2_ok(int64_t match, int64_t mismatch, int64_t indel) {
-    return indel <= 0 && h2_byte_score(match - 2 * indel) && h2_byte_score(mismatch - 2 * indel) &&
-                   std::max(match, mismatch) - 2 * indel <= 15 ? 1 : 0;
+    return dp_lane_h2_ok(match, mismatch, indel) ? 1 : 0;
 }
 
 // hand-off bytes dp_lane_h2_kernel needs in HBM

@@ -108,10 +108,7 @@ int32_t sw_walk_host(const std::vector<int8_t>& tb, int32_t m, int32_t bi, int32
     return j;
 }
 
-// The best-cell key of the local-alignment kernels: 24-bit score, 20-bit row and column
-inline bool local_limits_ok(int64_t n, int64_t m, int64_t match) {
-    return n <= 0xFFFFF && m <= 0xFFFFF && std::max<int64_t>(0, match) * std::min(n, m) < (int64_t(1) << 24);
-}
+// (the best-cell key limit, local_limits_ok: ovl_score_range.h)
 
 // The argument checks that every stage over a read set and a contig set shares, in the two places where they stand
 // in each stage's order: the counts first, and, after the stage's own pointer checks, the offsets and the bytes.
@@ -150,12 +147,7 @@ inline int64_t local_steps(int64_t m) { return (m + 126) / 64 * 64; }
 inline size_t local_table_bytes(int64_t n, int64_t m) {
     return (size_t)local_strips(n) * (size_t)local_steps(m) * 64;
 }
-// Cells beyond int32: sw_kernel's wide form, and never the batch kernel
-inline bool local_wide(int64_t n, int64_t m, int64_t match, int64_t mismatch, int64_t indel) {
-    const int64_t M = std::max(std::max(iabs64(match), iabs64(mismatch)), iabs64(indel));
-    const int64_t top = std::max<int64_t>(0, match) * std::min(n, m);
-    return M >= (int64_t(1) << 30) || top + M >= (int64_t(1) << 31);
-}
+// (cells beyond int32, local_wide: ovl_score_range.h -- sw_kernel's wide form, and never the batch kernel)
 
 // Where a query of n bases against a window of m goes: nowhere (Empty: every result is 0), through the batch kernel
 // with the others, or alone through sw_kernel (ovl_local_align) -- wide scoring, more strips than one wavefront

@@ -4,14 +4,7 @@
 
 namespace {
 
-// aligners.py:40: diag is taken whenever diag >= up and diag >= left.  Every dp
-// value is a sum of <= lmax diagonal terms when that always holds, so it does if
-// indel <= min(0, lmax*min(match,mismatch)) - max(0, lmax*max(match,mismatch)).
-bool gaps_cannot_win(int64_t match, int64_t mismatch, int64_t indel, int64_t lmax) {
-    const int64_t lo = std::min<int64_t>(0, lmax * std::min(match, mismatch));
-    const int64_t hi = std::max<int64_t>(0, lmax * std::max(match, mismatch));
-    return indel <= lo - hi;
-}
+// (the range rules -- gaps_cannot_win, the key, cell and hand-off widths -- are ovl_score_range.h's)
 
 int make_plan_full(const Dev* c, int32_t match, int32_t mismatch, int64_t indel, Plan* out);
 
@@ -48,25 +41,17 @@ int make_plan(const Dev* c, int32_t match, int32_t mismatch, int64_t indel, int3
 
 int make_plan_full(const Dev* c, int32_t match, int32_t mismatch, int64_t indel, Plan* out) {
     const int64_t L = std::max<int32_t>(c->lmax, 1);
-    const int64_t amax = std::max(iabs64(match), iabs64(mismatch));
     Plan p;
     // ungapped closed form: exact when gaps cannot win and no int32 store can wrap
-    if (c->wmax > 0 && gaps_cannot_win(match, mismatch, indel, L) && amax * L < (int64_t(1) << 31)) {
+    if (c->wmax > 0 && gaps_cannot_win(match, mismatch, indel, L) && ungapped_int32_ok(match, mismatch, L)) {
         p.kernel = OVL_KERNEL_UNGAPPED;
-        // 32-bit keys (score << 16) - j need |score| < 2^15 on both sides, and the
-        // folded form X * ((mismatch - match) << 16) + ... a 24-bit multiplier
-        const int64_t dms = (int64_t)mismatch - (int64_t)match;
-        // (the uniform sweep compares keys without their block constant: |score| + 32*amax
-        //  must stay below 2^15 as well)
-        p.key64 = !(amax * (2 * L + 32) < (1 << 15) && iabs64(dms) < 128 && iabs64(match) < 128);
+        p.key64 = !ungapped_key32_ok(match, mismatch, L);
     } else {
         if (c->lmax > kDpMaxLen)
             return fail(c, OVL_E_UNSUPPORTED, "gapped DP supports reads up to %d bases (longest is %d)", kDpMaxLen,
                         c->lmax);
         p.kernel = OVL_KERNEL_DP;
-        const int64_t M = std::max(amax, iabs64(indel));
-        // |dp| <= 2*lmax*M; one more term for the candidates: int32 is exact below 2^31
-        p.wide = !(indel > INT32_MIN && M < (int64_t(1) << 31) && (2 * L + 1) * M < (int64_t(1) << 31));
+        p.wide = !dp_int32_ok(match, mismatch, indel, L);
     }
     *out = p;
     return OVL_OK;
@@ -107,8 +92,8 @@ hipError_t scratch_release(Dev* c, hipStream_t s) {
 bool use_dp_lane(const Dev* c, int64_t match, int64_t mismatch, int64_t indel, int64_t n_pairs) {
     if (c->k.dp_lane == 0) return false;
     const int64_t L = std::max<int32_t>(c->lmax, 1);
-    const int64_t M = std::max(std::max(iabs64(match), iabs64(mismatch)), iabs64(indel));
-    if (L > kLaneMaxLen || (4 * L + 4) * M >= (int64_t(1) << 30) || c->codes_bytes + 64 >= (int64_t(1) << 32))
+    if (L > kLaneMaxLen || !dp_lane_int32_ok(match, mismatch, indel, L) ||
+        c->codes_bytes + 64 >= (int64_t(1) << 32))
         return false;
     return c->k.dp_lane == 1 || n_pairs >= kLaneMinPairs;
 }
@@ -161,6 +146,15 @@ int launch_score_chunk(Dev* c, const Plan& pl, const int32_t* d_a, const int32_t
                        int32_t match, int32_t mismatch, int64_t indel, int32_t* d_score, int32_t* d_end,
                        hipStream_t s) {
     if (n_pairs == 0) return OVL_OK;
+    // ovl_last_score_form: the call's first launch describes itself (a banded launch, not its seed's)
+    ScoreForm& f = c->form;
+    const bool rec = f.open;
+    if (rec) {
+        f = ScoreForm{};
+        f.kernel = pl.kernel;
+        f.key64 = pl.kernel == OVL_KERNEL_BANDED ? pl.seed_key64 : (pl.kernel == OVL_KERNEL_UNGAPPED && pl.key64);
+        f.wide = pl.kernel != OVL_KERNEL_UNGAPPED && pl.wide ? 1 : 0;
+    }
     const int32_t* seed_end = nullptr;
     if (pl.kernel == OVL_KERNEL_BANDED) {
         // seed j* into device scratch (the outputs may be host memory), then the banded DP reads it
@@ -198,6 +192,7 @@ int launch_score_chunk(Dev* c, const Plan& pl, const int32_t* d_a, const int32_t
         // uniform-length fast path (2 bit planes): pairs of two reads of length lmax;
         // uniform_kernel scores the other pairs through its LDS side ring
         g.lw = c->planes == 2 ? c->lmax : 0;
+        if (rec) f.rs_log2 = g.rs_log2;
         g.full = as<uint32_t>(c->full);
         // (timing: this launch records the chunk's kernel events itself, once; issue_chunk checks they were taken)
         g.ev_start = c->kev_start;
@@ -259,17 +254,11 @@ int launch_score_chunk(Dev* c, const Plan& pl, const int32_t* d_a, const int32_t
             k.cw = 32;
             k.slots = (int64_t)c->cu_count * 4 * ovl_dp_lane_waves_per_simd(k.cw);
             const int64_t L = std::max<int32_t>(c->lmax, 1);
-            const int64_t M = std::max(std::max(iabs64(match), iabs64(mismatch)), iabs64(indel));
-            const int64_t sma = (int64_t)match - 2 * indel, smm = (int64_t)mismatch - 2 * indel;
-            k.prof = c->k.lane_prof && c->planes == 2 && indel <= 0 && sma >= -128 && sma <= 127 && smm >= -128 &&
-                     smm <= 127;
-            k.ho = (4 * L + 4) * M < (int64_t(1) << 15) ? 1 : 0;
+            k.prof = c->k.lane_prof && c->planes == 2 && dp_lane_prof_ok(match, mismatch, indel);
+            k.ho = dp_lane_ho1_ok(match, mismatch, indel, L) ? 1 : 0;
             k.sfx = k.prof && c->k.lane_sfx && c->wmax > 0;
-            // column steps G[i][j] - G[i-1][j] lie in [0, max(match, mismatch) - 2*indel]: 4 bits in LDS
-            const int64_t step_max = std::max<int64_t>(match, mismatch) - 2 * indel;
-            if (k.sfx && indel <= 0 && std::max<int64_t>(match, mismatch) >= indel &&
-                step_max <= 15 && g.mcap <= 256)
-                k.ho = 2;
+            // 4-bit column steps in LDS
+            if (k.sfx && dp_lane_ho2_ok(match, mismatch, indel, g.mcap)) k.ho = 2;
             k.h2 = k.ho == 2 && c->k.lane_h2 && ovl_dp_lane_h2_ok(match, mismatch, indel);
             // hand-off columns in HBM: one per resident slot (HO 0 / 1), per tile for the h2 form's HBM variant --
             // which launches at most kH2Slice pairs at a time over one reused column buffer (lcap / 2 bytes per
@@ -303,23 +292,24 @@ int launch_score_chunk(Dev* c, const Plan& pl, const int32_t* d_a, const int32_t
                 HIPCHK(c, ovl_launch_dp_lane(&gs, &k, s));
             }
             HIPCHK(c, scratch_release(c, s));
+            if (rec) {
+                f.lane = 1;
+                f.prof = k.prof;
+                f.sfx = k.sfx;
+                f.ho = k.ho;
+                f.h2 = k.h2;
+            }
             return OVL_OK;
         }
         if (g.band >= 0) {
-            // "-inf" (kBandNeg) must stay below every value: |values| <= (2*lmax + 1) * M and the row
-            // form's scan adds up to 2*band*|indel|
-            const int64_t Mx = std::max(std::max(iabs64(match), iabs64(mismatch)), iabs64(indel));
             const int64_t L = std::max<int32_t>(c->lmax, 1);
-            const bool neg_ok = (4 * L + 2) * Mx < (int64_t(1) << 29);
+            const bool neg_ok = band_neg_ok(match, mismatch, indel, L);
             const int64_t lanes = 2 * (int64_t)g.band + 1;
             const bool diag_ok = neg_ok && ovl_band_diag_slots(g.band, c->lmax, nullptr) > 0;
             const bool rows_ok = neg_ok && lanes <= 192 && c->lmax <= 1024;
-            // lane per pair: byte scores (match/mismatch - 2*indel, -2*indel, -indel in int8), indel <= 0,
-            // <= 4 symbols, G = dp - indel*(i+j) in int32 with j down to -(2*lmax + band)
-            const int64_t sma = (int64_t)match - 2 * indel, smm = (int64_t)mismatch - 2 * indel;
-            auto i8 = [](int64_t v) { return v >= -128 && v <= 127; };
-            const bool lane_ok = c->planes == 2 && ovl_band_lane_ok(g.band) && indel <= 0 && i8(sma) &&
-                                 i8(smm) && i8(-2 * indel) && (6 * L + 2 * g.band + 8) * Mx < (int64_t(1) << 30) &&
+            // lane per pair: <= 4 symbols, byte scores and G in int32 (band_lane_scoring_ok)
+            const bool lane_ok = c->planes == 2 && ovl_band_lane_ok(g.band) &&
+                                 band_lane_scoring_ok(match, mismatch, indel, L, g.band) &&
                                  c->lmax <= kLaneMaxLen && c->codes_bytes + 64 < (int64_t(1) << 32);
             switch (c->k.band_form) {
                 case OVL_BAND_FORM_ROWS: g.band_form = rows_ok ? OVL_BAND_FORM_ROWS : OVL_BAND_FORM_STRIP; break;
@@ -337,6 +327,7 @@ int launch_score_chunk(Dev* c, const Plan& pl, const int32_t* d_a, const int32_t
                                       : (diag_ok ? OVL_BAND_FORM_DIAG : OVL_BAND_FORM_FAST);
                     break;
             }
+            if (rec) f.band_form = g.band_form;
             if (g.band_form == OVL_BAND_FORM_LANE) {
                 OvlLaneArgs k{};
                 k.sfx = c->k.lane_sfx && c->wmax > 0;
@@ -346,6 +337,10 @@ int launch_score_chunk(Dev* c, const Plan& pl, const int32_t* d_a, const int32_t
                 k.wsfx = c->wmax;
                 k.split = c->k.band_form == OVL_BAND_FORM_LANE2 ||
                           (c->k.band_form != OVL_BAND_FORM_LANE1 && g.band >= kBandLane2Min);
+                if (rec) {
+                    f.sfx = k.sfx;
+                    f.split = k.split;
+                }
                 HIPCHK(c, ovl_launch_band_lane(&g, &k, s));
                 HIPCHK(c, scratch_release(c, s));
                 return OVL_OK;
@@ -374,6 +369,8 @@ int launch_score(Dev* c, const Plan& pl, const int32_t* d_a, const int32_t* d_b,
 
 int check_scoring_args(ovl_ctx* c, int32_t match, int32_t mismatch, int64_t indel, int32_t band, Plan* p) {
     // every device holds the same read set, so device 0 plans for all
+    c->devs[0]->form = ScoreForm{};
+    c->devs[0]->form.open = true;
     return make_plan(c->devs[0], match, mismatch, indel, band, p);
 }
 
@@ -388,6 +385,25 @@ OVL_API int ovl_plan(const ovl_ctx* c, int32_t match, int32_t mismatch, int64_t 
     return OVL_OK;
 }
 
+OVL_API int ovl_last_score_form(const ovl_ctx* c, int32_t* kernel, int32_t* key64, int32_t* wide, int32_t* lane,
+                                int32_t* prof, int32_t* sfx, int32_t* ho, int32_t* h2, int32_t* band_form,
+                                int32_t* split, int32_t* rs_log2) {
+    if (!c) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
+    const ScoreForm& f = c->devs[0]->form;
+    if (kernel) *kernel = f.kernel;
+    if (key64) *key64 = f.key64;
+    if (wide) *wide = f.wide;
+    if (lane) *lane = f.lane;
+    if (prof) *prof = f.prof;
+    if (sfx) *sfx = f.sfx;
+    if (ho) *ho = f.ho;
+    if (h2) *h2 = f.h2;
+    if (band_form) *band_form = f.band_form;
+    if (split) *split = f.split;
+    if (rs_log2) *rs_log2 = f.rs_log2;
+    return OVL_OK;
+}
+
 // ----------------------------------------------------------------------------- scoring
 
 OVL_API int ovl_score_device(ovl_ctx* c, const int32_t* d_a, const int32_t* d_b, int64_t n_pairs, int32_t match,
@@ -399,6 +415,8 @@ OVL_API int ovl_score_device(ovl_ctx* c, const int32_t* d_a, const int32_t* d_b,
     if (n_pairs > 0 && (!d_a || !d_b || !d_score || !d_end)) return fail(c, OVL_E_ARG, "NULL device pointer");
     Dev* d = c->devs[0];
     Plan p;
+    d->form = ScoreForm{};
+    d->form.open = true;
     int rc = make_plan(d, match, mismatch, indel, band, &p);
     if (rc != OVL_OK) return rc;
     if (n_pairs > 0 && d->n_reads == 0) return fail(c, OVL_E_INDEX, "pairs given but the read set is empty");

@@ -26,6 +26,7 @@ ERRORS = {
     -5: "OVL_E_RANGE", -6: "OVL_E_STATE", -7: "OVL_E_INDEX", -8: "OVL_E_INTERNAL",
 }
 KERNELS = {0: "none", 1: "ungapped", 2: "dp", 3: "banded"}
+BAND_FORMS = {-1: "none", 0: "strip", 1: "rows", 2: "fast", 3: "diag", 4: "lane"}
 
 # name -> (restype, argtypes); mirrors include/ovl.h exactly
 _P = ctypes.c_void_p
@@ -58,6 +59,7 @@ SIGNATURES = {
     "ovl_set_reads": (ctypes.c_int, [_P, _P, _P, _i32]),
     "ovl_reads_info": (ctypes.c_int, [_P, _pi32, _pi32, _pi32, _pi64]),
     "ovl_plan": (ctypes.c_int, [_P, _i32, _i32, _i64, _i32, _pi32]),
+    "ovl_last_score_form": (ctypes.c_int, [_P] + [_pi32] * 11),
     "ovl_score_host": (ctypes.c_int, [_P, _P, _P, _i64, _i32, _i32, _i64, _i32, _P, _P]),
     "ovl_score_device": (ctypes.c_int, [_P, _P, _P, _i64, _i32, _i32, _i64, _i32, _P, _P, _P]),
     "ovl_check_device_errors": (ctypes.c_int, [_P]),

@@ -334,6 +334,22 @@ class OverlapEngine:
         check(self._L.ovl_plan(self._ctx, match, mismatch, indel, band, ctypes.byref(k)), self._ctx)
         return _lib.KERNELS[k.value]
 
+    def last_score_form(self) -> Dict[str, object]:
+        """The form the first scoring launch of the last scoring call took on this engine's first device
+        (ovl_last_score_form; host-array calls, ``score_tensors`` and ``launcher`` alike): ``kernel`` ("none" when
+        nothing was launched, else as ``plan``), ``key64`` (for a banded call, its seed's), ``wide``, ``lane`` (the
+        lane-per-pair full DP ran) with its arguments ``prof``, ``sfx``, ``ho`` (0 int32 / 1 int16 hand-off column,
+        2 four-bit steps in LDS) and ``h2`` (packed f16 cells), ``band_form`` ("none", "strip", "rows", "fast", "diag"
+        or "lane": the band form as launched), ``split`` (the band lane kernel's two lanes per pair) and ``rs_log2`` (an
+        ungapped launch: 0 in throughput mode)."""
+        names = ("kernel", "key64", "wide", "lane", "prof", "sfx", "ho", "h2", "band_form", "split", "rs_log2")
+        v = [ctypes.c_int32() for _ in names]
+        check(self._L.ovl_last_score_form(self._ctx, *[ctypes.byref(x) for x in v]), self._ctx)
+        form: Dict[str, object] = dict(zip(names, (x.value for x in v)))
+        form["kernel"] = _lib.KERNELS[form["kernel"]]
+        form["band_form"] = _lib.BAND_FORMS[form["band_form"]]
+        return form
+
     # ---------------------------------------------------------------- candidates
     def candidates(self, k: int = 5) -> Tuple[np.ndarray, np.ndarray]:
         """k-mer candidate pairs over the resident (distinct) reads, enumerated on the GPU.

@@ -160,6 +160,20 @@ int ovl_reads_info(const ovl_ctx* ctx, int32_t* n_reads, int32_t* lmax, int32_t*
 int ovl_plan(const ovl_ctx* ctx, int32_t match, int32_t mismatch, int64_t indel, int32_t band,
              int32_t* out_kernel);
 
+/* The form the first scoring launch of the last scoring call took on the context's first device (host-array
+ * calls, ovl_score_candidates*, ovl_score_device): kernel (OVL_KERNEL_*; OVL_KERNEL_NONE when nothing was
+ * launched), key64 (the ungapped kernel's 64-bit keys; for a banded call, its seed's), wide (cells beyond int32),
+ * lane (the lane-per-pair full DP ran) with its arguments prof (byte score profile), sfx (row symbols from the bit
+ * planes), ho (hand-off column: 0 int32, 1 int16, 2 four-bit steps in LDS) and h2 (two pairs per lane as packed f16
+ * cells), band_form (the band knob's form as launched: 0 strip, 1 rows, 2 fast, 3 diag, 4 lane;
+ * -1 without a band), split (its lane kernel's two lanes per pair) and rs_log2 (an ungapped launch: 0 in throughput
+ * mode; above 0 the uniform kernel's latency mode or the general kernel's lanes per pair).  Any pointer may be
+ * NULL.  Additions like this one leave OVL_ABI_VERSION as it is: the version changes when an existing signature
+ * does. */
+int ovl_last_score_form(const ovl_ctx* ctx, int32_t* kernel, int32_t* key64, int32_t* wide, int32_t* lane,
+                        int32_t* prof, int32_t* sfx, int32_t* ho, int32_t* h2, int32_t* band_form, int32_t* split,
+                        int32_t* rs_log2);
+
 /* Score against the resident reads; host pair/result arrays; synchronous.  Sharded over the
  * context's devices; chunked H2D / kernel / D2H pipeline per device.  A pair index outside
  * [0, n_reads) makes the call return OVL_E_INDEX (checked on the device, its results are -1). */
