@@ -236,3 +236,280 @@ extern "C" hipError_t ovl_shard_cut(const int64_t* cum, int64_t lo, int64_t hi, 
     ovl_cand::cut_kernel<<<1, 64, 0, stream>>>(cum, lo, hi, shards, cuts);
     return hipGetLastError();
 }
+
+// ----------------------------------------------------------------------------- seed candidates
+// The second candidate rule (include/ovl.h, ovl_seed_candidates):
+//
+//   Reads are the distinct reads in read_copies order, and k >= 1.  The prefix key of read b is b[:k]; a read
+//   shorter than k has no key and takes no part.  For each read a in order, for each offset o = 1, 2, ...,
+//   len(a) - k ascending, for each read b != a in read order whose prefix key equals a[o:o+k]: emit (a, b, o),
+//   unless (a, b) was already emitted at a smaller offset.
+//
+// Each b has exactly one prefix key, so two offsets of a with different k-mers have disjoint groups and two with
+// equal k-mers the same group: "already emitted" is "a's k-mer at o also occurs at an offset o' with 1 <= o' < o",
+// and such an offset emits nothing.  No sort of the output is needed.
+//
+// Device plan, the keys packed as key_kernel packs them, (k << 58) | codes:
+//   1. keys:   seed_key_kernel, one thread per read: its prefix key, or ~0 for a read shorter than k -- no k-mer
+//              key equals it (its length field is 63 > 29 >= k), and it sorts behind every group, so the sort's
+//              first n_long entries are exactly the reads with len >= k and only those are searched;
+//   2. sort:   the stable radix sort of (prefix key, read) of rule 1 (ovl_cand_sort);
+//   3. count:  seed_count_kernel, one wavefront per read a.  It forms the len(a) - k keys of a's offsets into LDS:
+//              lane j owns a run of ceil((len(a) - k) / 64) consecutive offsets, packs the first key and rolls the
+//              others ((key << bits | next symbol) & mask).  Then, 64 offsets at a time, a lane binary-searches its
+//              key's group [lo, hi) in the sorted keys, and the lanes that found one compare their key with the keys
+//              of all earlier offsets (one LDS broadcast read per earlier offset) and drop theirs if it occurred.
+//              The keys stay in LDS, not registers: an offset is compared with every earlier one of the read, not only
+//              with its own 64.  That comparison is (len - k)^2 / 64 LDS reads per read, below the len^2 cells that
+//              scoring one pair of such reads costs.  Count = group sizes, minus one where a is in the group (its
+//              own prefix key equals the k-mer);
+//   4. scan:   exclusive int64 prefix sum of the counts (ovl_cand_scan) -> output offsets;
+//   5. emit:   seed_emit_kernel, one wavefront per read, 64 offsets at a time: an inclusive scan of the 64 group
+//              sizes lays the groups' members end to end in the rule's order (offset ascending, then read order),
+//              and the wavefront walks them 64 members at a time -- a lane finds its member's offset by a six-step
+//              search of the scan -- drops b == a by ballot as emit_kernel does and writes a, b and o coalesced.
+//              A group's (lo, size) per offset comes from HBM, where the count pass left it (KEEP, the default), or
+//              is searched again (the keys formed again into LDS; OVL_SEED_GROUPS=search).  Measured, DESIGN.md §4.6a:
+//              PhiX N = 50,000, k = 12, 15.6 M pairs, the emit kernel takes 69 us from HBM against 294 us.
+namespace ovl_cand {
+
+__global__ __launch_bounds__(256) void seed_key_kernel(const uint8_t* __restrict__ codes, const int64_t* __restrict__ off,
+                                                       const int32_t* __restrict__ len, int32_t n_reads, int32_t k,
+                                                       int32_t bits, uint64_t* __restrict__ pre_key,
+                                                       int32_t* __restrict__ iota) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_reads;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        uint64_t key = ~0ull;
+        if (len[i] >= k) {
+            const uint8_t* r = codes + off[i];
+            uint64_t p = 0;
+            for (int q = 0; q < k; ++q) p = (p << bits) | r[q];
+            key = ((uint64_t)k << 58) | p;
+        }
+        pre_key[i] = key;
+        iota[i] = (int32_t)i;
+    }
+}
+
+// The keys of read r's offsets 1 .. n_off into this wavefront's LDS (keys[i] is offset i + 1's): lane j packs the
+// first key of its run and rolls the others.
+__device__ __forceinline__ void seed_wave_keys(const uint8_t* __restrict__ r, int32_t n_off, int32_t k, int32_t bits,
+                                               int lane, uint64_t* keys) {
+    const int32_t run = (n_off + 63) >> 6;
+    const int32_t i0 = lane * run;
+    const int32_t i1 = min(i0 + run, n_off);
+    if (i0 < i1) {
+        const uint64_t mask = (1ull << (k * bits)) - 1ull;  // k * bits <= 58
+        const uint64_t tag = (uint64_t)k << 58;
+        uint64_t p = 0;
+        for (int q = 0; q < k; ++q) p = (p << bits) | r[i0 + 1 + q];
+        keys[i0] = tag | p;
+        for (int32_t i = i0 + 1; i < i1; ++i) {
+            p = ((p << bits) | r[i + k]) & mask;  // offset i + 1's last symbol
+            keys[i] = tag | p;
+        }
+    }
+    // the other lanes' keys are read next: LDS writes of this wavefront retired, and no reordering across
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Offsets c0 + 1 .. c0 + 64 of a read, lane = offset - 1 - c0: the lane's key, and its group sorted[lo, lo + g) --
+// g = 0 past the read's offsets, without a group, and where the key occurred at an earlier offset of the read.
+__device__ __forceinline__ void seed_chunk_group(const uint64_t* __restrict__ sorted, int32_t n_long,
+                                                 const uint64_t* keys, int32_t n_off, int32_t c0, int lane,
+                                                 uint64_t& key, int32_t& lo, int32_t& g) {
+    const int32_t i = c0 + lane;
+    const bool valid = i < n_off;
+    key = valid ? keys[i] : 0ull;
+    lo = 0;
+    g = 0;
+    if (valid) {
+        lo = (int32_t)bound(sorted, n_long, key, false);
+        if (lo < n_long && sorted[lo] == key) {
+            int64_t a = lo + 1, b = n_long;  // upper bound within (lo, n_long)
+            while (a < b) {
+                const int64_t mid = (a + b) >> 1;
+                if (sorted[mid] <= key) a = mid + 1;
+                else b = mid;
+            }
+            g = (int32_t)a - lo;
+        }
+    }
+    if (__ballot(g > 0) != 0ull) {
+        const int32_t jend = min(c0 + 63, n_off - 1);  // the largest offset index of the chunk: j < i <= jend
+        bool dup = false;
+        for (int32_t j = 0; j < jend; ++j) dup |= (keys[j] == key) & (j < i);
+        if (dup) g = 0;
+    }
+}
+
+template <bool KEEP>
+__global__ __launch_bounds__(256) void seed_count_kernel(const uint8_t* __restrict__ codes, const int64_t* __restrict__ off,
+                                                         const int32_t* __restrict__ len, int32_t n_reads, int32_t k,
+                                                         int32_t bits, const uint64_t* __restrict__ sorted,
+                                                         int32_t n_long, const uint64_t* __restrict__ pre_key,
+                                                         int32_t max_off, int32_t* __restrict__ grp_lo,
+                                                         int32_t* __restrict__ grp_n, int64_t* __restrict__ cnt) {
+    extern __shared__ uint64_t seed_lds[];
+    const int lane = threadIdx.x & 63;
+    uint64_t* keys = seed_lds + (size_t)(threadIdx.x >> 6) * max_off;
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    for (int64_t a = wave; a < n_reads; a += n_waves) {
+        const int32_t n_off = min(len[a] - k, max_off);  // (max_off = lmax - k: never the smaller one)
+        int64_t total = 0;
+        if (n_off > 0) {
+            const int64_t base = off[a];
+            seed_wave_keys(codes + base, n_off, k, bits, lane, keys);
+            const uint64_t own = pre_key[a];
+            for (int32_t c0 = 0; c0 < n_off; c0 += 64) {
+                uint64_t key;
+                int32_t lo, g;
+                seed_chunk_group(sorted, n_long, keys, n_off, c0, lane, key, lo, g);
+                if (KEEP && c0 + lane < n_off) {
+                    grp_lo[base + c0 + lane] = lo;
+                    grp_n[base + c0 + lane] = g;
+                }
+                total += g - (g > 0 && key == own ? 1 : 0);
+            }
+            // the next read's keys overwrite these: this read's LDS reads are done first
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+        }
+#pragma unroll
+        for (int s = 32; s >= 1; s >>= 1) total += __shfl_xor(total, s, 64);
+        if (lane == 0) cnt[a] = total;
+    }
+}
+
+template <bool KEEP>
+__global__ __launch_bounds__(256) void seed_emit_kernel(const uint8_t* __restrict__ codes, const int64_t* __restrict__ off,
+                                                        const int32_t* __restrict__ len, int32_t n_reads, int32_t k,
+                                                        int32_t bits, const uint64_t* __restrict__ sorted,
+                                                        int32_t n_long, const int32_t* __restrict__ order,
+                                                        int32_t max_off, const int32_t* __restrict__ grp_lo,
+                                                        const int32_t* __restrict__ grp_n,
+                                                        const int64_t* __restrict__ cnt, const int64_t* __restrict__ offs,
+                                                        int32_t* __restrict__ out_a, int32_t* __restrict__ out_b,
+                                                        int32_t* __restrict__ out_o) {
+    extern __shared__ uint64_t seed_lds[];
+    const int lane = threadIdx.x & 63;
+    uint64_t* keys = seed_lds + (size_t)(threadIdx.x >> 6) * max_off;
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    for (int64_t a = wave; a < n_reads; a += n_waves) {
+        const int64_t mine = cnt[a];
+        if (mine == 0) continue;
+        const int32_t n_off = min(len[a] - k, max_off);
+        const int64_t base = off[a];
+        const int64_t out0 = offs[a], out1 = out0 + mine;  // this read's slots: nothing is written outside them
+        if (!KEEP) seed_wave_keys(codes + base, n_off, k, bits, lane, keys);
+        int64_t written = 0;
+        for (int32_t c0 = 0; c0 < n_off; c0 += 64) {
+            int32_t lo = 0, g = 0;
+            if (KEEP) {
+                if (c0 + lane < n_off) {
+                    lo = grp_lo[base + c0 + lane];
+                    g = grp_n[base + c0 + lane];
+                }
+            } else {
+                uint64_t key;
+                seed_chunk_group(sorted, n_long, keys, n_off, c0, lane, key, lo, g);
+            }
+            // the 64 groups' members end to end: lane l's are positions [P[l] - g[l], P[l])
+            int64_t P = g;
+#pragma unroll
+            for (int s = 1; s < 64; s <<= 1) {
+                const int64_t up = __shfl_up(P, s, 64);
+                if (lane >= s) P += up;
+            }
+            const int64_t T = __shfl(P, 63, 64);
+            for (int64_t t0 = 0; t0 < T; t0 += 64) {
+                const int64_t t = t0 + lane;
+                const bool valid = t < T;
+                int l = 0;  // the lanes whose P <= t: the first lane with P > t owns member t
+#pragma unroll
+                for (int s = 32; s >= 1; s >>= 1) {
+                    const int64_t pv = __shfl(P, l + s - 1, 64);
+                    if (pv <= t) l += s;
+                }
+                l = min(l, 63);
+                const int64_t pl = __shfl(P, l, 64);
+                const int32_t gl = __shfl(g, l, 64);
+                const int32_t ll = __shfl(lo, l, 64);
+                const int64_t pos = (int64_t)ll + (t - (pl - gl));
+                const bool in = valid && pos >= 0 && pos < n_long;
+                const int32_t b = in ? order[pos] : -1;
+                const bool keep = in && b != (int32_t)a;
+                const uint64_t m = __ballot(keep);
+                const int64_t slot = out0 + written + __popcll(m & ((1ull << lane) - 1ull));
+                if (keep && slot < out1) {
+                    out_a[slot] = (int32_t)a;
+                    out_b[slot] = b;
+                    out_o[slot] = c0 + l + 1;
+                }
+                written += __popcll(m);
+            }
+        }
+        if (!KEEP) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
+}
+
+}  // namespace ovl_cand
+
+extern "C" hipError_t ovl_seed_keys(const uint8_t* codes, const int64_t* off, const int32_t* len, int32_t n_reads,
+                                    int32_t k, int32_t bits, uint64_t* pre_key, int32_t* iota, hipStream_t stream) {
+    if (n_reads <= 0) return hipSuccess;
+    ovl_cand::seed_key_kernel<<<grid_for_threads(n_reads, 8192), 256, 0, stream>>>(codes, off, len, n_reads, k, bits,
+                                                                                   pre_key, iota);
+    return hipGetLastError();
+}
+
+// One wavefront per read; a block is 4 wavefronts while their keys (max_off each) fit 64 KiB of LDS, else one.
+static void seed_shape(int32_t n_reads, int32_t max_off, unsigned* grid, unsigned* block, size_t* lds) {
+    const int waves = max_off <= OVL_SEED_MAX_OFFSETS / 4 ? 4 : 1;
+    *block = 64u * waves;
+    *lds = (size_t)waves * (size_t)max_off * sizeof(uint64_t);
+    int64_t b = ((int64_t)n_reads + waves - 1) / waves;
+    if (b > 16384) b = 16384;
+    *grid = (unsigned)(b < 1 ? 1 : b);
+}
+
+extern "C" hipError_t ovl_seed_count(const OvlSeedArgs* s, int32_t keep, hipStream_t stream) {
+    if (s->n_reads <= 0 || s->max_off <= 0) return hipSuccess;
+    if (s->max_off > OVL_SEED_MAX_OFFSETS) return hipErrorInvalidValue;
+    unsigned grid, block;
+    size_t lds;
+    seed_shape(s->n_reads, s->max_off, &grid, &block, &lds);
+    if (keep)
+        ovl_cand::seed_count_kernel<true><<<grid, block, lds, stream>>>(s->codes, s->off, s->len, s->n_reads, s->k,
+                                                                        s->bits, s->sorted, s->n_long, s->pre_key,
+                                                                        s->max_off, s->grp_lo, s->grp_n, s->cnt);
+    else
+        ovl_cand::seed_count_kernel<false><<<grid, block, lds, stream>>>(s->codes, s->off, s->len, s->n_reads, s->k,
+                                                                         s->bits, s->sorted, s->n_long, s->pre_key,
+                                                                         s->max_off, s->grp_lo, s->grp_n, s->cnt);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t ovl_seed_emit(const OvlSeedArgs* s, int32_t keep, hipStream_t stream) {
+    if (s->n_reads <= 0 || s->max_off <= 0) return hipSuccess;
+    if (s->max_off > OVL_SEED_MAX_OFFSETS) return hipErrorInvalidValue;
+    unsigned grid, block;
+    size_t lds;
+    seed_shape(s->n_reads, s->max_off, &grid, &block, &lds);
+    if (keep)
+        ovl_cand::seed_emit_kernel<true><<<grid, block, 0, stream>>>(
+            s->codes, s->off, s->len, s->n_reads, s->k, s->bits, s->sorted, s->n_long, s->order, s->max_off, s->grp_lo,
+            s->grp_n, s->cnt, s->offs, s->out_a, s->out_b, s->out_o);
+    else
+        ovl_cand::seed_emit_kernel<false><<<grid, block, lds, stream>>>(
+            s->codes, s->off, s->len, s->n_reads, s->k, s->bits, s->sorted, s->n_long, s->order, s->max_off, s->grp_lo,
+            s->grp_n, s->cnt, s->offs, s->out_a, s->out_b, s->out_o);
+    return hipGetLastError();
+}

@@ -113,6 +113,7 @@ Knobs read_knobs() {
     }
     if (const char* e = getenv("OVL_LOCAL_BATCH_WAVES")) k.local_batch_waves = std::max(0, atoi(e));
     if (const char* e = getenv("OVL_TR_WINDOW")) k.tr_window = std::max(0, atoi(e));
+    if (const char* e = getenv("OVL_SEED_GROUPS")) k.seed_keep = strcmp(e, "search") != 0;
     if (const char* e = getenv("OVL_REACH_WINDOW")) k.reach_window = std::max(0, atoi(e));
     if (const char* e = getenv("OVL_READ_BEST_CHUNK")) k.read_best_chunk = std::max(0, atoi(e));
     if (const char* e = getenv("OVL_CONSENSUS_CHUNK")) k.consensus_chunk = std::max(0, atoi(e));
@@ -138,7 +139,7 @@ void destroy_dev(Dev* d) {
                       &d->lb_ctr, &d->lb_rows, &d->lb_slabs, &d->lb_wops, &d->lb_out, &d->lb_ops, &d->tr_off,
                       &d->tr_edge, &d->tr_order, &d->tr_ctr, &d->tr_out, &d->rc_off, &d->rc_head, &d->rc_order,
                       &d->rc_matrix, &d->rc_pivot, &d->rc_out, &d->rb_in, &d->rb_tile, &d->rb_res, &d->rb_bits, &d->cs_ref,
-                      &d->cs_counts, &d->cs_called, &d->cs_ctr, &d->cs_hits})
+                      &d->cs_counts, &d->cs_called, &d->cs_ctr, &d->cs_hits, &d->cand_o, &d->sd_glo, &d->sd_gn})
         release(*b);
     if (d->l_tb_host) (void)hipHostFree(d->l_tb_host);
     for (hipEvent_t e : d->lb_ev)
@@ -150,6 +151,8 @@ void destroy_dev(Dev* d) {
     for (hipEvent_t e : d->rb_ev)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : d->cs_ev)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : d->sd_ev)
         if (e) (void)hipEventDestroy(e);
     free_staging(d->st_in);
     free_staging(d->st_out);

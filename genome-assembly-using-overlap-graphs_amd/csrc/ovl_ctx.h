@@ -140,6 +140,10 @@ struct Knobs {
                                   // the tile budget allows; tests force several chunks)
     int32_t consensus_chunk = 0;  // OVL_CONSENSUS_CHUNK: reads per chunk of ovl_consensus (0: what the ops budget
                                   // allows; tests force several chunks)
+    int32_t seed_keep = 1;        // OVL_SEED_GROUPS env (keep|search): ovl_seed_candidates' emit pass takes every
+                                  // offset's group from HBM, where the count pass left it (default), or searches it
+                                  // again: PhiX N = 50,000, k = 12, the emit kernel 69 us against 294 us, the whole
+                                  // call 0.47 ms against 0.69 ms (profiles/seed_candidates.json; tests run both)
     int32_t reach_window = 0;     // OVL_REACH_WINDOW: columns (bits) of the reachability rows that ovl_reach_reduce's
                                   // marking holds in registers per pass (0: 16,384; tests force several passes)
     int32_t pack_direct_pct = 18; // OVL_PACK_DIRECT_PCT: packed calls into pinned arrays store this share of the
@@ -218,6 +222,11 @@ struct Dev {
     // device candidate enumeration (ovl_candidates): per-read keys / groups and the pair list
     DevBuf k_pre, k_suf, k_sorted, k_iota, k_order, k_lo, k_hi, k_cnt, k_offs, k_temp, cand_a, cand_b;
     int64_t cand_n = -1;  // -1: no candidate list for the resident reads
+    // seed candidates (ovl_seed_candidates): the offset of each pair of the list, every offset's group (count pass ->
+    // emit pass), and whether the resident list came from that rule
+    DevBuf cand_o, sd_glo, sd_gn;
+    bool cand_seed = false;
+    hipEvent_t sd_ev[6] = {};  // timing on: before the keys, after them, the sort, the count + scan; around the emit
     // heavy tiles of the candidate list (tiles holding side pairs, scheduled first: uniform_kernel), built on
     // the first throughput-mode launch over the list (ensure_heavy)
     DevBuf tile_flags, heavy_ids;
@@ -336,6 +345,7 @@ struct ovl_ctx {
     int64_t x_cs_batch = 0, x_cs_single = 0, x_cs_ops = 0;      // ovl_last_consensus
     int32_t x_cs_launches = 0;
     double x_cs_ms[3] = {0.0, 0.0, 0.0};                        // ovl_last_consensus_timing
+    double x_sd_ms[4] = {0.0, 0.0, 0.0, 0.0};                   // ovl_last_seed_timing
 };
 
 int fail(const ovl_ctx* c, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));

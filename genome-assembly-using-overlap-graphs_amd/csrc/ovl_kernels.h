@@ -151,6 +151,36 @@ extern "C" hipError_t ovl_cand_emit(const int32_t* order, const int64_t* lo, con
                                     int32_t n_reads, int32_t all_pairs, int32_t* out_a, int32_t* out_b,
                                     hipStream_t stream);
 
+// seed candidates (ovl_candidates.hip, ovl_seed_candidates): every k-mer of a read at offsets >= 1 looked up among
+// the prefix keys.  ovl_seed_keys writes the prefix keys (~0 for a read shorter than k) and the identity for
+// ovl_cand_sort; ovl_seed_count the per-read pair counts (and, keep != 0, every offset's group into grp_lo / grp_n,
+// indexed off[a] + offset - 1); ovl_seed_emit the list at offs (ovl_cand_scan of the counts), its groups taken from
+// grp_lo / grp_n (keep != 0) or searched again.  max_off = lmax - k, the most offsets a read has: a wavefront holds
+// that many keys in LDS, at most OVL_SEED_MAX_OFFSETS (64 KiB).
+#define OVL_SEED_MAX_OFFSETS 8192
+struct OvlSeedArgs {
+    const uint8_t* codes;
+    const int64_t* off;
+    const int32_t* len;
+    int32_t n_reads, k, bits;
+    const uint64_t* sorted;   // the sorted prefix keys, of which the first n_long are reads with len >= k
+    const int32_t* order;     // their reads
+    int32_t n_long;
+    const uint64_t* pre_key;  // per read
+    int32_t max_off;
+    int32_t* grp_lo;          // per base: the group of the offset's key (keep)
+    int32_t* grp_n;
+    int64_t* cnt;             // per read: its pairs
+    const int64_t* offs;      // per read: its first output slot
+    int32_t* out_a;
+    int32_t* out_b;
+    int32_t* out_o;
+};
+extern "C" hipError_t ovl_seed_keys(const uint8_t* codes, const int64_t* off, const int32_t* len, int32_t n_reads,
+                                    int32_t k, int32_t bits, uint64_t* pre_key, int32_t* iota, hipStream_t stream);
+extern "C" hipError_t ovl_seed_count(const OvlSeedArgs* s, int32_t keep, hipStream_t stream);
+extern "C" hipError_t ovl_seed_emit(const OvlSeedArgs* s, int32_t keep, hipStream_t stream);
+
 // local alignment (ovl_local.hip)
 // rowbuf: n_strips x (64 * n_chunks + 64) words {value, epoch}, n_chunks = (m + 126) / 64; tb (nullable):
 // n_strips x 64 * n_chunks x 64 bytes, [strip][tau][lane]

@@ -375,6 +375,35 @@ class OverlapEngine:
         check(self._L.ovl_candidates(self._ctx, int(k), ctypes.byref(n)), self._ctx)
         return int(n.value)
 
+    def enumerate_seed_candidates(self, k: int) -> int:
+        """Enumerate the seed candidate list on the device (ovl_seed_candidates): every k-mer of a read at offsets
+        >= 1 looked up among the reads' prefixes, the list and order of ``candidates.enumerate_seed_candidates``.
+        It becomes the resident candidate list (``candidates_copy``, ``score_candidates``, ...); returns its
+        length."""
+        n = ctypes.c_int64()
+        check(self._L.ovl_seed_candidates(self._ctx, int(k), ctypes.byref(n)), self._ctx)
+        return int(n.value)
+
+    def seed_offsets(self) -> np.ndarray:
+        """The offset of each pair of the resident seed candidate list (ovl_seed_offsets_copy); OVL_E_STATE when
+        the resident list did not come from ``enumerate_seed_candidates``."""
+        n = self.candidates_device()[2]  # (OVL_E_STATE without any list)
+        out = np.zeros(max(n, 1), dtype=np.int32)
+        check(self._L.ovl_seed_offsets_copy(self._ctx, _ptr(out)), self._ctx)
+        return out[:n]
+
+    def seed_candidates(self, k: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """``(a, b, offset)`` of the seed candidate list, enumerated on the GPU and kept resident."""
+        a, b = self.candidates_copy(self.enumerate_seed_candidates(k))
+        return a, b, self.seed_offsets()
+
+    def last_seed_timing(self) -> Dict[str, float]:
+        """Device times (ms) of the last ``enumerate_seed_candidates`` made with timing on
+        (ovl_last_seed_timing): keys_ms, sort_ms, count_ms (the count kernel and the scan), emit_ms."""
+        v = [ctypes.c_double() for _ in range(4)]
+        check(self._L.ovl_last_seed_timing(self._ctx, *[ctypes.byref(x) for x in v]), self._ctx)
+        return dict(zip(("keys_ms", "sort_ms", "count_ms", "emit_ms"), (x.value for x in v)))
+
     def candidates_device(self) -> Tuple[int, int, int]:
         """(device ptr of a_idx, device ptr of b_idx, n_pairs) of the resident candidate list."""
         pa, pb, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int64()

@@ -42,10 +42,21 @@ import networkx as nx
 import numpy as np
 
 from ._lib import OvlError
-from .candidates import dedup_reads, enumerate_candidates
+from .candidates import dedup_reads, enumerate_candidates, enumerate_seed_candidates
 from .engine import INDEL_DEFAULT, OverlapEngine, default_engine
 
 CANDIDATE_MODES = ("auto", "device", "host")
+# which k-mers select the candidate pairs (a, b): "suffix" -- a's last k bases equal b's first k, the reference's rule
+# (overlapGraphs.py:30-52) -- or "any": a k-mer of a at some offset >= 1 equals b's first k bases, the seed rule
+# (candidates.enumerate_seed_candidates)
+SEED_MODES = ("suffix", "any")
+
+
+def _check_seeds(seeds: str, k: int) -> None:
+    if seeds not in SEED_MODES:
+        raise ValueError(f"seeds must be one of {SEED_MODES}")
+    if seeds == "any" and k < 1:
+        raise ValueError('seeds="any" needs k >= 1 (every ordered pair is what seeds="suffix" with k=0 gives)')
 
 
 def _score(distinct: Sequence[str], a: np.ndarray, b: np.ndarray, engine: Optional[OverlapEngine],
@@ -113,9 +124,9 @@ def assemble_graph(distinct: Sequence[str], counts: Sequence[int], a, b, score, 
 
 
 def candidates_and_scores(distinct: Sequence[str], k: int, engine: Optional[OverlapEngine] = None, scorer=None,
-                          candidates: str = "auto", timing: Optional[dict] = None):
+                          candidates: str = "auto", timing: Optional[dict] = None, seeds: str = "suffix"):
     """Candidate pairs (overlapGraphs.py:30-52) and their (score, end) (:53), in reference order, as
-    int32 arrays.
+    int32 arrays.  ``seeds="any"`` takes the seed rule's pairs instead (``SEED_MODES``), in that rule's order.
 
     ``candidates``: "device" enumerates on the GPU (list kept resident and scored
     without a host round trip), "host" uses ``enumerate_candidates``, "auto" is
@@ -127,6 +138,9 @@ def candidates_and_scores(distinct: Sequence[str], k: int, engine: Optional[Over
     from .engine import encode_reads
     if candidates not in CANDIDATE_MODES:
         raise ValueError(f"candidates must be one of {CANDIDATE_MODES}")
+    _check_seeds(seeds, k)
+    if seeds == "any":
+        return _seed_candidates_and_scores(distinct, k, engine, scorer, candidates, timing)
     st = _Stages(timing)
     if scorer is not None or candidates == "host":
         a, b = enumerate_candidates(distinct, k)
@@ -149,6 +163,41 @@ def candidates_and_scores(distinct: Sequence[str], k: int, engine: Optional[Over
         sc, en = _score(distinct, a, b, eng, None, enc)
         st("score")
         return a, b, sc, en
+    st("enumerate")
+    a, b = eng.candidates_copy(n)
+    st("candidates_copy")
+    sc, en = eng.score_candidates(10, -1, INDEL_DEFAULT)
+    st("score")
+    return a, b, sc, en
+
+
+def _seed_candidates_and_scores(distinct, k, engine, scorer, candidates, timing):
+    """``candidates_and_scores`` under the seed rule, with the same routing: the host form for a ``scorer``, for
+    ``candidates="host"``, and under "auto" when the device refuses the keys (OVL_E_UNSUPPORTED).  "auto" has no
+    size below which it takes the host form: DESIGN.md §4.6a has the measurement."""
+    from .engine import encode_reads
+    st = _Stages(timing)
+
+    def on_host(eng, enc):
+        a, b, _offset = enumerate_seed_candidates(distinct, k)
+        st("enumerate_host")
+        sc, en = _score(distinct, a, b, eng, scorer, enc)
+        st("score")
+        return a, b, sc, en
+
+    if scorer is not None or candidates == "host":
+        return on_host(engine, None)
+    eng = engine or default_engine()
+    enc = encode_reads(distinct)
+    st("encode")
+    eng.set_reads(distinct, enc)
+    st("set_reads")
+    try:
+        n = eng.enumerate_seed_candidates(k)
+    except OvlError as e:
+        if e.code != -4 or candidates == "device":
+            raise
+        return on_host(eng, enc)
     st("enumerate")
     a, b = eng.candidates_copy(n)
     st("candidates_copy")
@@ -473,27 +522,33 @@ def engine_on(devices) -> OverlapEngine:
 
 
 def overlap_edges_k(reads, k=5, engine: Optional[OverlapEngine] = None, scorer=None,
-                    candidates: str = "auto", devices=None, timing: Optional[dict] = None) -> OverlapEdges:
+                    candidates: str = "auto", devices=None, timing: Optional[dict] = None,
+                    seeds: str = "suffix") -> OverlapEdges:
     """Scored k-mer candidates of ``construct_overlap_graph_nx_k`` as columns (no networkx).
     ``timing``: a dict that receives the stage times (s), dedup first (candidates_and_scores)."""
     assert k >= 0, "k-mer length must be non-negative"
+    _check_seeds(seeds, k)
     if engine is None and devices is not None:
         engine = engine_on(devices)
     st = _Stages(timing)
     distinct, counts = dedup_reads(reads)
     st("dedup")
-    a, b, sc, en = candidates_and_scores(distinct, k, engine, scorer, candidates, timing)
+    a, b, sc, en = candidates_and_scores(distinct, k, engine, scorer, candidates, timing, seeds)
     return OverlapEdges(distinct, counts, a, b, sc, en)
 
 
 def construct_overlap_graph_nx_k(reads, k=5, engine: Optional[OverlapEngine] = None, scorer=None,
-                                 candidates: str = "auto", devices=None):
+                                 candidates: str = "auto", devices=None, seeds: str = "suffix"):
     """Overlap graph over k-mer-filtered candidates (overlapGraphs.py:5-61).
+
+    ``seeds`` chooses the filter (``SEED_MODES``): "suffix" is the reference's -- a pair is scored when a's last k
+    bases equal b's first k -- and "any" scores a pair when any k-mer of a at an offset >= 1 equals b's first k
+    bases, so that an overlap of any length >= k reaches the scorer; its edges are inserted in that rule's order.
 
     ``devices`` ("all" or ordinals) scores on several GPUs from this one process: every
     device enumerates the same list, scores its Σ n·m-balanced shard and copies its
     results into its slice of the host result arrays."""
-    edges = overlap_edges_k(reads, k, engine, scorer, candidates, devices)
+    edges = overlap_edges_k(reads, k, engine, scorer, candidates, devices, seeds=seeds)
     return edges.to_digraph(), edges.read_copies()
 
 
@@ -700,17 +755,19 @@ def create_contig(start_read, dag, visited, topo_order):
 
 
 def assemble_contigs_using_overlap_graphs(reads, k=5, params=None, engine: Optional[OverlapEngine] = None,
-                                          scorer=None):
+                                          scorer=None, seeds: str = "suffix", candidates: str = "auto"):
     """overlapGraphs.py:151-193: overlap graph (GPU candidates + scoring), cycle removal (native
     replay), topological order, greedy contig walks -- the same contigs in the same order.
     ``params`` (the reference's experiment dict) only feeds the progress lines; ``scorer`` is the
-    graph builders' hook for (score, end) from another backend."""
+    graph builders' hook for (score, end) from another backend; ``seeds`` and ``candidates`` are
+    ``construct_overlap_graph_nx_k``'s (with ``seeds="any"`` the graph, and so the contigs, are not the reference's)."""
     def say(step):
         if params is not None:
             print(f"{step} for experiment_name={params['experiment_name']} - N={params['N']}, l={params['l']}, "
                   f"p={params['error_prob']}, k={params['k']}, num_iteration={params['num_iteration']}...")
     say("Constructing overlap graph")
-    overlap_graph, read_copies = construct_overlap_graph_nx_k(reads, k=k, engine=engine, scorer=scorer)
+    overlap_graph, read_copies = construct_overlap_graph_nx_k(reads, k=k, engine=engine, scorer=scorer,
+                                                              candidates=candidates, seeds=seeds)
     say("Removing cycles from graph")
     dag = remove_cycles_from_graph(overlap_graph)
     topo_with_copies = {node: i for i, node in enumerate(nx.topological_sort(dag))}

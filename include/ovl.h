@@ -215,6 +215,38 @@ int ovl_align_one(ovl_ctx* ctx, int32_t a, int32_t b, int32_t match, int32_t mis
  */
 int ovl_candidates(ovl_ctx* ctx, int32_t k, int64_t* out_n_pairs);
 
+/*
+ * Seed candidates: the second candidate rule, every k-mer of a read looked up among the reads' prefixes.
+ *
+ *   Reads are the distinct reads in read_copies order, and k >= 1.  The prefix key of read b is b[:k]; a read
+ *   shorter than k has no key and takes no part.  For each read a in order, for each offset o = 1, 2, ...,
+ *   len(a) - k ascending, for each read b != a in read order whose prefix key equals a[o:o+k]: emit (a, b, o),
+ *   unless (a, b) was already emitted at a smaller offset.
+ *
+ * Each b has one prefix key, so offsets of a with different k-mers have disjoint groups and offsets with equal
+ * k-mers the same group: an offset whose k-mer occurs at an earlier offset >= 1 of a emits nothing.  Offset 0 is
+ * left out: reads sharing their first k bases start at the same place.  For reads longer than k the list of
+ * ovl_candidates at the same k is a subset of this one up to order (its hit is o = len(a) - k).
+ *
+ * The list becomes the context's candidate list exactly as after ovl_candidates -- enumerated on every device,
+ * replaced by the next ovl_candidates, ovl_seed_candidates or ovl_set_reads -- so ovl_candidates_copy,
+ * ovl_candidates_device, ovl_score_candidates(_range) and ovl_candidates_shards work on it unchanged;
+ * *out_n_pairs receives its length.  Every argument is checked before anything runs, and a failed check leaves the
+ * previous list as it was: OVL_E_ARG for k < 1 or a null pointer, OVL_E_STATE without resident reads,
+ * OVL_E_UNSUPPORTED when k * (bits per symbol: 2, 4 or 8) > 58, when a read is longer than k + 8192, or (after the
+ * count pass, the previous list still intact) when the list would hold 2^31 pairs or more.
+ */
+int ovl_seed_candidates(ovl_ctx* ctx, int32_t k, int64_t* out_n_pairs);
+
+/* The offset o of each pair of the list of ovl_seed_candidates (as many entries as the list has pairs);
+ * OVL_E_STATE when the context's candidate list did not come from ovl_seed_candidates. */
+int ovl_seed_offsets_copy(ovl_ctx* ctx, int32_t* out_offset);
+
+/* With ovl_set_timing on, the device time (ms, HIP events on the context's first device) of the last
+ * ovl_seed_candidates: the key kernel, the sort, the count kernel with the scan, the emit kernel.  Each may be
+ * NULL; zeros when timing was off. */
+int ovl_last_seed_timing(const ovl_ctx* ctx, double* keys_ms, double* sort_ms, double* count_ms, double* emit_ms);
+
 /* Copy the context's candidate list to host arrays of *out_n_pairs entries each. */
 int ovl_candidates_copy(ovl_ctx* ctx, int32_t* a_idx, int32_t* b_idx);
 
