@@ -2,7 +2,7 @@
 // per-device state, and the functions that cross the host files ovl_ctx.cpp (contexts, devices, pinned memory),
 // ovl_plan.cpp (planner, kernel launch), ovl_pipeline.cpp (host-array pipeline), ovl_reads.cpp (read upload),
 // ovl_cand.cpp (candidate lists, resident grid), ovl_local_api.cpp (single alignments), ovl_depth_api.cpp (read
-// depth), ovl_consensus_api.cpp (read pileup and consensus) and the graph stages ovl_reduce_api.cpp /
+// depth), ovl_consensus_api.cpp (read pileup and consensus), ovl_layout_api.cpp (best-successor layout) and the graph stages ovl_reduce_api.cpp /
 // ovl_reach_api.cpp.  What the local-alignment stages share on the host is in ovl_local_host.h.
 //
 // A context (ovl_ctx) drives one or more HIP devices from one host thread.  Each
@@ -146,6 +146,9 @@ struct Knobs {
                                   // call 0.47 ms against 0.69 ms (profiles/seed_candidates.json; tests run both)
     int32_t reach_window = 0;     // OVL_REACH_WINDOW: columns (bits) of the reachability rows that ovl_reach_reduce's
                                   // marking holds in registers per pass (0: 16,384; tests force several passes)
+    int32_t layout_runs = 1;      // OVL_LAYOUT_LINK env (runs|plain): the layout's link kernel reduces runs of equal a
+                                  // inside the wavefront before its atomics (default), or issues one atomic per
+                                  // eligible pair (the measurement: DESIGN.md 4.15; tests run both)
     int32_t pack_direct_pct = 18; // OVL_PACK_DIRECT_PCT: packed calls into pinned arrays store this share of the
                                   // pairs (the last chunk) as int32 straight into them, over the link while the
                                   // host expands the packed chunks (tools/pack_ab.py, target point, six
@@ -258,6 +261,11 @@ struct Dev {
     // the counters {n_other, n_changed, bad ops}, and the flat count indices of the single-pair reads' votes
     DevBuf cs_ref, cs_counts, cs_called, cs_ctr, cs_hits;
     hipEvent_t cs_ev[4] = {};  // timing on: a chunk's start, after its alignment launch, after its pileup; the vote
+    // layout (ovl_layout_api.cpp): the call's inputs (ovl_layout: lengths, offsets, bytes and the four columns;
+    // ovl_layout_candidates: the score and end columns and the code table), the per-read block (WorkPlan), the
+    // contigs' bytes and the scan's scratch
+    DevBuf ly_in, ly_work, ly_bases, ly_temp;
+    hipEvent_t ly_ev[5] = {};  // timing on: before and after the scoring launches, the link kernel, the forest, the spelling
     // host-array pipeline: events per slot and pinned staging (slots x cap pairs x {a, b} / {score, end})
     hipEvent_t ev_k[kSlots] = {};
     int32_t* st_in = nullptr;
@@ -304,6 +312,7 @@ struct HostReads {
     std::vector<int32_t> len;
     std::vector<uint32_t> full;
     uint8_t lut[256];
+    uint8_t inv[256];              // code -> byte (the layout spells contigs from the resident codes)
     const uint8_t* src = nullptr;  // the caller's bytes, then (stage_reads) their pinned copy
     int64_t total = 0;
     bool packed2 = false;          // every byte is A, C, G or T: the stage holds them 2-bit packed (o_pk)
@@ -346,6 +355,9 @@ struct ovl_ctx {
     int32_t x_cs_launches = 0;
     double x_cs_ms[3] = {0.0, 0.0, 0.0};                        // ovl_last_consensus_timing
     double x_sd_ms[4] = {0.0, 0.0, 0.0, 0.0};                   // ovl_last_seed_timing
+    int64_t x_ly_links = 0, x_ly_cycles = 0, x_ly_on_path = 0;  // ovl_last_layout
+    int32_t x_ly_levels = 0;
+    double x_ly_ms[4] = {0.0, 0.0, 0.0, 0.0};                   // ovl_last_layout_timing
 };
 
 int fail(const ovl_ctx* c, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));

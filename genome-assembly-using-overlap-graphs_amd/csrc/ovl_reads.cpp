@@ -86,9 +86,13 @@ int stage_reads(ovl_ctx* c, ReadStage& st, HostReads& h) {
         if (!h.packed2) host_copy(st.p + st.o_raw, h.src, (size_t)h.total);
     }
     memset(h.lut, 0, sizeof(h.lut));
+    memset(h.inv, 0, sizeof(h.inv));
     int k = 0;
     for (int v = 0; v < 256; ++v)
-        if (present[v]) h.lut[v] = (uint8_t)k++;
+        if (present[v]) {
+            h.inv[k] = (uint8_t)v;
+            h.lut[v] = (uint8_t)k++;
+        }
     h.planes = k <= 4 ? 2 : (k <= 16 ? 4 : 8);
     // bit-plane layouts: W = ceil(lmax/32) words of 32 bases, rows padded to 16 bytes
     h.wmax = 0;

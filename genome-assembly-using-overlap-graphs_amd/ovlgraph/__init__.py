@@ -14,7 +14,8 @@ from .engine import INDEL_DEFAULT, OverlapEngine, default_engine, encode_reads, 
 
 __all__ = ["OvlError", "OverlapEngine", "default_engine", "encode_reads", "score_reads", "INDEL_DEFAULT",
            "transitive_reduction", "assemble_contigs_string", "transitive_reduction2", "find_unitigs",
-           "assemble_contigs", "pileup", "polish_contigs"]
+           "assemble_contigs", "pileup", "polish_contigs", "best_successor_layout", "layout_loop",
+           "assemble_contigs_best_successor"]
 
 
 def __getattr__(name):
@@ -27,4 +28,10 @@ def __getattr__(name):
     if name in ("pileup", "polish_contigs"):
         from . import consensus
         return getattr(consensus, name)
+    # the best-successor layout's entry points.  The function layout.layout is best_successor_layout here: the name
+    # ovlgraph.layout is the submodule's, as the import system binds it, whatever was imported first
+    if name in ("best_successor_layout", "layout_loop", "assemble_contigs_best_successor"):
+        from .layout import assemble_contigs_best_successor, layout as best_successor_layout, layout_loop
+        return {"best_successor_layout": best_successor_layout, "layout_loop": layout_loop,
+                "assemble_contigs_best_successor": assemble_contigs_best_successor}[name]
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -4,7 +4,8 @@ The library is built in-tree by ``csrc/Makefile`` (``__graft_entry__.build()``)
 into ``genome-assembly-using-overlap-graphs_amd/build/libovl.so``.  There is no
 CPU fallback: if the library is missing or no GPU is visible the engine
 raises ``OvlError`` (the host forms -- ``ovl_remove_cycles``, ``ovl_transitive_reduce_host``,
-``ovl_reach_reduce_host``, ``ovl_read_best_host``, ``ovl_consensus_host`` -- need neither a context nor a GPU).  ctypes
+``ovl_reach_reduce_host``, ``ovl_read_best_host``, ``ovl_consensus_host``, ``ovl_layout_host`` -- need neither a
+context nor a GPU).  ctypes
 releases the GIL for the duration of each call.
 """
 from __future__ import annotations
@@ -101,6 +102,14 @@ SIGNATURES = {
     "ovl_last_consensus": (ctypes.c_int, [_P, _pi64, _pi64, _pi64, _pi32]),
     "ovl_last_consensus_timing": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double),
                                                  ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
+    "ovl_layout_host": (ctypes.c_int, [_P, _P, _i32, _P, _P, _P, _P, _i64, _i32, _i32, _P, _P, _P, _P, _P, _P, _P,
+                                       _pi32]),
+    "ovl_layout": (ctypes.c_int, [_P, _P, _P, _i32, _P, _P, _P, _P, _i64, _i32, _i32, _P, _P, _P, _P, _P, _P, _P,
+                                  _pi32]),
+    "ovl_layout_candidates": (ctypes.c_int, [_P, _i32, _i32, _i64, _i32, _i32, _i32, _P, _P, _P, _P, _P, _P, _P,
+                                             _pi32]),
+    "ovl_last_layout": (ctypes.c_int, [_P, _pi64, _pi64, _pi32, _pi64]),
+    "ovl_last_layout_timing": (ctypes.c_int, [_P] + [ctypes.POINTER(ctypes.c_double)] * 4),
 }
 
 

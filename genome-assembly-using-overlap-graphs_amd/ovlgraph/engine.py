@@ -198,6 +198,52 @@ def consensus_host(reads, contigs, place, read_length: int, match: int = 10, mis
     return _consensus_result(R, total, cnt, called, aln, n_changed, n_other)
 
 
+def _layout_outputs(n: int, total: int):
+    """The arrays that receive a layout: succ, link, contig, offset (int32 per read), on_path (uint8 per read), the
+    contigs' bytes (at most the reads' bytes) and their offsets (n + 1 int64)."""
+    outs = [np.zeros(max(n, 1), dtype=np.int32) for _ in range(4)]
+    return outs, np.zeros(max(n, 1), dtype=np.uint8), np.zeros(max(total, 1), dtype=np.uint8), \
+        np.zeros(n + 1, dtype=np.int64)
+
+
+def _layout_columns(n: int, a, b, score, end):
+    cols = [np.ascontiguousarray(x, dtype=np.int32) for x in (a, b, score, end)]
+    if any(x.ndim != 1 or x.shape != cols[0].shape for x in cols):
+        raise OvlError(-1, "layout: a, b, score and end must be 1-D arrays of equal length")
+    return cols
+
+
+def _layout_result(n: int, outs, on_path, bases, c_off, n_contigs: int, stats) -> Dict[str, object]:
+    res: Dict[str, object] = dict(zip(("succ", "link", "contig", "offset"), (o[:n] for o in outs)))
+    res["on_path"] = on_path[:n]
+    res["c_off"] = c_off[: n_contigs + 1]
+    res["bases"] = bases[: int(c_off[n_contigs])]
+    res["n_contigs"] = n_contigs
+    res.update(stats)
+    return res
+
+
+def last_layout_host() -> Dict[str, int]:
+    """{links, cycles, levels, on_path_reads} of this thread's last ``layout_host`` (ovl_last_layout without a
+    context)."""
+    li, cy, pa, lv = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32()
+    check(_lib.load().ovl_last_layout(None, ctypes.byref(li), ctypes.byref(cy), ctypes.byref(lv), ctypes.byref(pa)))
+    return {"links": li.value, "cycles": cy.value, "levels": lv.value, "on_path_reads": pa.value}
+
+
+def layout_host(reads, a, b, score, end, min_score: int = 1, min_overlap: int = 1, encoded=None) -> Dict[str, object]:
+    """``OverlapEngine.layout`` on one host thread (ovl_layout_host): no context, no GPU."""
+    buf, offs = encoded if encoded is not None else encode_reads(reads)
+    n = offs.shape[0] - 1
+    cols = _layout_columns(n, a, b, score, end)
+    outs, on_path, bases, c_off = _layout_outputs(n, int(offs[-1] - offs[0]))
+    nc = ctypes.c_int32(0)
+    check(_lib.load().ovl_layout_host(_ptr(buf), _ptr(offs), n, *[_ptr(x) for x in cols], cols[0].shape[0],
+                                      int(min_score), int(min_overlap), *[_ptr(o) for o in outs], _ptr(on_path),
+                                      _ptr(bases), _ptr(c_off), ctypes.byref(nc)))
+    return _layout_result(n, outs, on_path, bases, c_off, nc.value, last_layout_host())
+
+
 def host_pool() -> Dict[str, int]:
     """The host thread pool's plan, recounted now (ovl_host_pool): {threads, sharers, cpus, packed}."""
     v = [ctypes.c_int32() for _ in range(4)]
@@ -598,6 +644,47 @@ class OverlapEngine:
         check(self._L.ovl_last_consensus_timing(self._ctx, *[ctypes.byref(x) for x in t]), self._ctx)
         return {"batch_reads": a.value, "single_reads": b.value, "ops": o.value, "launches": n.value,
                 "align_ms": t[0].value, "pileup_ms": t[1].value, "vote_ms": t[2].value}
+
+    def layout(self, reads, a, b, score, end, min_score: int = 1, min_overlap: int = 1,
+               encoded=None) -> Dict[str, object]:
+        """The best-successor layout of scored pairs (ovl_layout; the rule: ``ovlgraph.layout``): ``succ``, ``link``,
+        ``contig``, ``offset`` (int32 per read), ``on_path`` (uint8 per read), ``bases`` (the contigs' bytes) with
+        ``c_off`` and ``n_contigs``, and the counts of ``last_layout``."""
+        buf, offs = encoded if encoded is not None else encode_reads(reads)
+        n = offs.shape[0] - 1
+        cols = _layout_columns(n, a, b, score, end)
+        outs, on_path, bases, c_off = _layout_outputs(n, int(offs[-1] - offs[0]))
+        nc = ctypes.c_int32(0)
+        check(self._L.ovl_layout(self._ctx, _ptr(buf), _ptr(offs), n, *[_ptr(x) for x in cols], cols[0].shape[0],
+                                 int(min_score), int(min_overlap), *[_ptr(o) for o in outs], _ptr(on_path),
+                                 _ptr(bases), _ptr(c_off), ctypes.byref(nc)), self._ctx)
+        return _layout_result(n, outs, on_path, bases, c_off, nc.value, self.last_layout())
+
+    def layout_candidates(self, match: int = 10, mismatch: int = -1, indel: int = INDEL_DEFAULT, band: int = -1,
+                          min_score: int = 1, min_overlap: int = 1) -> Dict[str, object]:
+        """``layout`` of the resident candidate list on the resident reads (ovl_layout_candidates): the list is scored
+        into device columns and laid out there; only the outputs come back, and the list stays as it was."""
+        i = self.info()
+        n = max(i["n_reads"], 0)
+        # (the contigs hold at most the reads' bytes, which n * lmax bounds)
+        outs, on_path, bases, c_off = _layout_outputs(n, n * i["lmax"])
+        nc = ctypes.c_int32(0)
+        check(self._L.ovl_layout_candidates(self._ctx, int(match), int(mismatch), int(indel), int(band),
+                                            int(min_score), int(min_overlap), *[_ptr(o) for o in outs], _ptr(on_path),
+                                            _ptr(bases), _ptr(c_off), ctypes.byref(nc)), self._ctx)
+        return _layout_result(n, outs, on_path, bases, c_off, nc.value, self.last_layout())
+
+    def last_layout(self) -> Dict[str, float]:
+        """{links, cycles, levels, on_path_reads} of the last ``layout`` / ``layout_candidates`` (ovl_last_layout): the
+        links of the forest after the cuts, the cycles cut, the doubling levels and the reads on contig paths; with
+        timing on also {score_ms, link_ms, forest_ms, spell_ms} (ovl_last_layout_timing)."""
+        li, cy, pa, lv = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32()
+        check(self._L.ovl_last_layout(self._ctx, ctypes.byref(li), ctypes.byref(cy), ctypes.byref(lv),
+                                      ctypes.byref(pa)), self._ctx)
+        t = [ctypes.c_double() for _ in range(4)]
+        check(self._L.ovl_last_layout_timing(self._ctx, *[ctypes.byref(x) for x in t]), self._ctx)
+        return {"links": li.value, "cycles": cy.value, "levels": lv.value, "on_path_reads": pa.value,
+                "score_ms": t[0].value, "link_ms": t[1].value, "forest_ms": t[2].value, "spell_ms": t[3].value}
 
     # ---------------------------------------------------------------- graph stages
     def transitive_reduce(self, off, heads, weights) -> np.ndarray:

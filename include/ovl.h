@@ -485,6 +485,72 @@ int ovl_last_consensus(const ovl_ctx* ctx, int64_t* batch_reads, int64_t* single
                        int32_t* launches);
 int ovl_last_consensus_timing(const ovl_ctx* ctx, double* align_ms, double* pileup_ms, double* vote_ms);
 
+/*
+ * Best-successor layout: contigs straight from the score columns, without a graph object.
+ *
+ *   Inputs: n reads with lengths len[r]; E pairs (a[p], b[p], score[p], end[p]) in list order; min_score and
+ *   min_overlap.
+ *   1. Eligible.  Pair p is eligible iff a[p] != b[p], score[p] >= min_score and min_overlap <= end[p] < len[b[p]].
+ *      A link that adds no base is no link.
+ *   2. Link.  link[a] is the eligible pair of a with the greatest score; ties go to the smallest p.
+ *      succ[a] = b[link[a]].  A read without an eligible pair has link = succ = -1.
+ *   3. Cycles.  succ is a functional graph.  Every cycle is cut at its pair with the least score; ties go to the
+ *      greatest p.  The source of that pair gets link = succ = -1.  What remains is a forest of in-trees, each with
+ *      one root (succ = -1).
+ *   4. Span.  tail[root] = 0; otherwise tail[a] = tail[succ[a]] + len[succ[a]] - end[link[a]].
+ *      span[a] = len[a] + tail[a] is the length of the contig spelled from a.
+ *   5. Contigs.  One contig per root, in ascending root index.  Its head is the read of the tree with the greatest
+ *      span; ties go to the smallest read index.  The contig is the head followed, along succ, by
+ *      read[succ][end[link]:] (the reference's own concatenation, create_contig).  Its length is span[head].
+ *   6. Placement.  Every read r gets contig[r], its tree's contig; offset[r] = span[head] - span[r], which for a read
+ *      on the head's path is where its first base lies; and on_path[r].
+ *   Everything is integer and independent of pair order, except the tie rules, which name p.
+ *
+ * The rule works on the reads it is given (the distinct reads of a read set: copies do not multiply contigs).
+ * Outputs, each of which may be NULL: succ, link, contig, offset (n_reads int32 each), on_path (n_reads bytes, 0 or
+ * 1), bases (the contigs' bytes one after the other: at most sum len bytes, since every read contributes at most its
+ * length) and c_off (n_reads + 1 int64, of which *n_contigs + 1 are written: contig c is bases[c_off[c] ..
+ * c_off[c+1])).  *n_contigs is always written.  No two-call protocol is needed.
+ * Every argument is checked before anything is launched or written: OVL_E_ARG for null pointers (n_contigs; offsets
+ * with reads; a column with pairs; seqs with bases to spell), negative counts, offsets that decrease and
+ * min_overlap < 1; OVL_E_UNSUPPORTED for n_pairs >= 2^31 or sum len >= 2^31, and from the device forms when the
+ * columns and tables do not fit the device's free memory; OVL_E_INDEX for a pair index outside [0, n_reads).
+ *
+ * ovl_layout_host: the rule on one host thread, with no context and no GPU.
+ * ovl_layout: uploads the reads and the columns and runs the kernels of ovl_layout.hip on the context's first
+ *   device: one lane per pair reduces the key (score biased by 2^31) << 32 | ~p into best[a] (runs of equal a inside
+ *   a wavefront first, one 64-bit atomic max per run; an ungrouped list is as correct); pointer doubling over succ
+ *   (ceil(log2 n) levels) finds every read's root or a node on a cycle, the minimum key around a cycle names the one
+ *   link to cut, and the doubling is redone only when a cycle was found; tail is the same doubling with a sum; the
+ *   head per root is a 64-bit atomic max of span << 32 | ~r; the head's path is marked from the highest level down
+ *   through the kept jump tables; a wavefront per on-path read copies its successor's new bases.
+ *   Device memory: 16 bytes per pair (the four columns) and 66 + 4 * (ceil(log2 n) + 1) bytes per read (the jump
+ *   tables are (levels + 1) * n * 4 of them), plus the reads (sum len + 12 per read) and the contigs (sum len).
+ * ovl_layout_candidates: the same on the resident reads and the resident candidate list (ovl_candidates or
+ *   ovl_seed_candidates): the list is scored into device columns by the launches of ovl_score_device (same
+ *   scoring arguments and limits) and the same kernels run on them; only the outputs cross the link, and the list
+ *   stays as it was.  8 bytes per pair for the two columns beside the list's own 8, the per-read bytes as above.
+ *   OVL_E_STATE without resident reads or without a candidate list.  A list whose columns do not fit the device is
+ *   refused (OVL_E_UNSUPPORTED): it is not scored in chunks.
+ * ovl_last_layout: of the last ovl_layout / ovl_layout_candidates of the context -- or, with ctx NULL, of the calling
+ *   thread's last ovl_layout_host -- the links of the forest (after the cuts), the cycles cut, the doubling levels
+ *   (0 from the host form, which walks) and the reads on contig paths.  ovl_last_layout_timing (timing on): device
+ *   time in ms of the scoring launches (0 for ovl_layout), the link kernel, the forest kernels and the spelling.
+ */
+int ovl_layout_host(const uint8_t* seqs, const int64_t* offsets, int32_t n_reads, const int32_t* a, const int32_t* b,
+                    const int32_t* score, const int32_t* end, int64_t n_pairs, int32_t min_score, int32_t min_overlap,
+                    int32_t* succ, int32_t* link, int32_t* contig, int32_t* offset, uint8_t* on_path, uint8_t* bases,
+                    int64_t* c_off, int32_t* n_contigs);
+int ovl_layout(ovl_ctx* ctx, const uint8_t* seqs, const int64_t* offsets, int32_t n_reads, const int32_t* a,
+               const int32_t* b, const int32_t* score, const int32_t* end, int64_t n_pairs, int32_t min_score,
+               int32_t min_overlap, int32_t* succ, int32_t* link, int32_t* contig, int32_t* offset, uint8_t* on_path,
+               uint8_t* bases, int64_t* c_off, int32_t* n_contigs);
+int ovl_layout_candidates(ovl_ctx* ctx, int32_t match, int32_t mismatch, int64_t indel, int32_t band,
+                          int32_t min_score, int32_t min_overlap, int32_t* succ, int32_t* link, int32_t* contig,
+                          int32_t* offset, uint8_t* on_path, uint8_t* bases, int64_t* c_off, int32_t* n_contigs);
+int ovl_last_layout(const ovl_ctx* ctx, int64_t* links, int64_t* cycles, int32_t* levels, int64_t* on_path_reads);
+int ovl_last_layout_timing(const ovl_ctx* ctx, double* score_ms, double* link_ms, double* forest_ms, double* spell_ms);
+
 #ifdef __cplusplus
 }
 #endif

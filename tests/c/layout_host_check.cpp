@@ -1,0 +1,216 @@
+// layout_host_check.cpp — the host code of csrc/ovl_layout_api.cpp (the argument checks and ovl_layout_host) as a
+// stand-alone program, for a sanitizer build on a machine without a GPU:
+//
+//     make -C genome-assembly-using-overlap-graphs_amd/csrc layout-host-check
+//
+// compiles this file and ovl_layout_api.cpp with -fsanitize=address,undefined (host side) and runs the result.  It
+// runs hand cases with known answers -- a cycle with a tail running into it, a tied cycle, a star, a chain, reads
+// without pairs, no reads at all -- every output in exactly-sized buffers, with and without the optional outputs,
+// and every error case (outputs untouched).  The device calls are linked but never made: their launches, the scoring
+// entry points and the context helpers are stubs here.
+#include "host_check.h"
+#include "ovl_layout.h"
+
+extern "C" hipError_t ovl_launch_layout_link(const OvlLayoutArgs*, int32_t, hipStream_t) { return hipErrorNotSupported; }
+extern "C" hipError_t ovl_launch_layout_double(const OvlLayoutArgs*, int32_t, hipStream_t) {
+    return hipErrorNotSupported;
+}
+extern "C" hipError_t ovl_launch_layout_cut(const OvlLayoutArgs*, hipStream_t) { return hipErrorNotSupported; }
+extern "C" hipError_t ovl_layout_scan_bytes(int32_t, size_t*) { return hipErrorNotSupported; }
+extern "C" hipError_t ovl_launch_layout_place(const OvlLayoutArgs*, void*, size_t, hipStream_t) {
+    return hipErrorNotSupported;
+}
+extern "C" hipError_t ovl_launch_layout_spell(const OvlLayoutArgs*, int32_t, hipStream_t) {
+    return hipErrorNotSupported;
+}
+int launch_score(Dev*, const Plan&, const int32_t*, const int32_t*, int64_t, int32_t, int32_t, int64_t, int32_t*,
+                 int32_t*, hipStream_t) {
+    return OVL_E_UNSUPPORTED;
+}
+int check_scoring_args(ovl_ctx*, int32_t, int32_t, int64_t, int32_t, Plan*) { return OVL_E_UNSUPPORTED; }
+
+struct Pairs {
+    std::vector<int32_t> a, b, score, end;
+    void add(int32_t x, int32_t y, int32_t s, int32_t e) {
+        a.push_back(x);
+        b.push_back(y);
+        score.push_back(s);
+        end.push_back(e);
+    }
+    int64_t n() const { return (int64_t)a.size(); }
+};
+
+// every output in a buffer of exactly its size (the sanitizer sees a byte too many)
+struct Out {
+    std::vector<int32_t> succ, link, contig, offset;
+    std::vector<uint8_t> on_path, bases;
+    std::vector<int64_t> c_off;
+    int32_t n_contigs = -7;
+    Out(const Seqs& rd)
+        : succ((size_t)rd.n(), 77), link((size_t)rd.n(), 77), contig((size_t)rd.n(), 77), offset((size_t)rd.n(), 77),
+          on_path((size_t)rd.n(), 77), bases((size_t)rd.total(), 77), c_off((size_t)rd.n() + 1, 77) {}
+    bool untouched() const {
+        auto all77 = [](const auto& v) { return std::all_of(v.begin(), v.end(), [](auto x) { return x == 77; }); };
+        return all77(succ) && all77(link) && all77(contig) && all77(offset) && all77(on_path) && all77(bases) &&
+               all77(c_off) && n_contigs == -7;
+    }
+    std::vector<std::string> contigs() const {
+        std::vector<std::string> v;
+        for (int32_t k = 0; k < n_contigs; ++k) v.emplace_back(bases.begin() + c_off[k], bases.begin() + c_off[k + 1]);
+        return v;
+    }
+};
+
+static int run(const Seqs& rd, const Pairs& p, int32_t min_score, int32_t min_overlap, Out& o) {
+    return ovl_layout_host(rd.data(), rd.off.data(), rd.n(), p.a.data(), p.b.data(), p.score.data(), p.end.data(),
+                           p.n(), min_score, min_overlap, o.succ.data(), o.link.data(), o.contig.data(),
+                           o.offset.data(), o.on_path.data(), o.bases.data(), o.c_off.data(), &o.n_contigs);
+}
+
+static void expect_stats(int64_t links, int64_t cycles, int64_t on_path) {
+    int64_t l = -1, c = -1, p = -1;
+    int32_t lv = -1;
+    EXPECT(ovl_last_layout(nullptr, &l, &c, &lv, &p) == OVL_OK);
+    EXPECT(l == links && c == cycles && p == on_path && lv == 0);
+}
+
+int main() {
+    {  // a 3-cycle (weakest link: read 1's) with a tail of two reads running into it at read 2
+        Seqs rd;
+        for (const char* s : {"AAAACC", "CCGGGG", "GGTTTT", "ACGTAA", "TTACGT"}) rd.add(s);
+        Pairs p;
+        p.add(0, 1, 40, 2);
+        p.add(1, 2, 5, 2);
+        p.add(2, 0, 30, 2);
+        p.add(4, 3, 20, 4);
+        p.add(3, 2, 20, 1);
+        p.add(3, 3, 99, 2);  // a == b: not eligible
+        Out o(rd);
+        EXPECT(run(rd, p, 1, 1, o) == OVL_OK);
+        EXPECT((o.succ == std::vector<int32_t>{1, -1, 0, 2, 3}));
+        EXPECT((o.link == std::vector<int32_t>{0, -1, 2, 4, 3}));
+        EXPECT(o.n_contigs == 1 && (o.contig == std::vector<int32_t>{0, 0, 0, 0, 0}));
+        EXPECT((o.on_path == std::vector<uint8_t>{1, 1, 1, 1, 1}));
+        // TTACGT + AA + GTTTT + AACC + GGGG
+        EXPECT((o.contigs() == std::vector<std::string>{"TTACGTAAGTTTTAACCGGGG"}));
+        EXPECT((o.offset == std::vector<int32_t>{11, 15, 7, 2, 0}));
+        EXPECT(o.c_off[0] == 0 && o.c_off[1] == 21);
+        expect_stats(4, 1, 5);
+        // without the optional outputs (and then without seqs)
+        int32_t nc = -1;
+        EXPECT(ovl_layout_host(rd.data(), rd.off.data(), rd.n(), p.a.data(), p.b.data(), p.score.data(), p.end.data(),
+                               p.n(), 1, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &nc) ==
+               OVL_OK);
+        EXPECT(nc == 1);
+        nc = -1;
+        EXPECT(ovl_layout_host(nullptr, rd.off.data(), rd.n(), p.a.data(), p.b.data(), p.score.data(), p.end.data(),
+                               p.n(), 1, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &nc) ==
+               OVL_OK);
+        EXPECT(nc == 1);
+        // a bound that leaves read 1's link out from the start: no cycle to cut
+        Out q(rd);
+        EXPECT(run(rd, p, 6, 1, q) == OVL_OK);
+        EXPECT(q.succ == o.succ && q.contigs() == o.contigs());
+        expect_stats(4, 0, 5);
+    }
+    {  // a cycle whose least score is tied: the greatest p is cut
+        Seqs rd;
+        for (const char* s : {"ACGT", "CGTA", "GTAC", "TACG"}) rd.add(s);
+        Pairs p;
+        for (int32_t i = 0; i < 4; ++i) p.add(i, (i + 1) % 4, 25, 3);
+        Out o(rd);
+        EXPECT(run(rd, p, 1, 1, o) == OVL_OK);
+        EXPECT((o.succ == std::vector<int32_t>{1, 2, 3, -1}));
+        EXPECT((o.contigs() == std::vector<std::string>{"ACGTACG"}));
+        expect_stats(3, 1, 4);
+    }
+    {  // a star: 40 reads into read 40; the one read with a base more heads the contig, the others hang off it
+        Seqs rd;
+        for (int32_t i = 0; i < 40; ++i) rd.add(i == 7 ? "ACGTACGTA" : "ACGTACGT");
+        rd.add("GTGTGTGT");
+        Pairs p;
+        for (int32_t i = 0; i < 40; ++i) p.add(i, 40, 10 + i, 2);
+        Out o(rd);
+        EXPECT(run(rd, p, 1, 1, o) == OVL_OK);
+        EXPECT(o.n_contigs == 1 && o.on_path[7] == 1 && o.on_path[0] == 0 && o.on_path[40] == 1);
+        EXPECT((o.contigs() == std::vector<std::string>{"ACGTACGTAGTGTGT"}));
+        EXPECT(o.offset[7] == 0 && o.offset[0] == 1 && o.offset[40] == 7);
+        expect_stats(40, 0, 2);
+    }
+    {  // reads without pairs: one contig per read, in read order; an end equal to len(b) is no link
+        Seqs rd;
+        for (const char* s : {"ACGT", "", "TTTTT"}) rd.add(s);
+        Pairs none;
+        Out o(rd);
+        EXPECT(ovl_layout_host(rd.data(), rd.off.data(), rd.n(), nullptr, nullptr, nullptr, nullptr, 0, 1, 1,
+                               o.succ.data(), o.link.data(), o.contig.data(), o.offset.data(), o.on_path.data(),
+                               o.bases.data(), o.c_off.data(), &o.n_contigs) == OVL_OK);
+        EXPECT((o.contigs() == std::vector<std::string>{"ACGT", "", "TTTTT"}));
+        EXPECT((o.contig == std::vector<int32_t>{0, 1, 2}) && (o.succ == std::vector<int32_t>{-1, -1, -1}));
+        Pairs p;
+        p.add(0, 2, 50, 5);
+        p.add(2, 1, 50, 0);
+        Out q(rd);
+        EXPECT(run(rd, p, 1, 1, q) == OVL_OK);
+        EXPECT(q.contigs() == o.contigs());
+        expect_stats(0, 0, 3);
+    }
+    {  // no reads at all
+        int64_t c_off[1] = {77};
+        int32_t nc = -1;
+        EXPECT(ovl_layout_host(nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, 1, 1, nullptr, nullptr,
+                               nullptr, nullptr, nullptr, nullptr, c_off, &nc) == OVL_OK);
+        EXPECT(nc == 0 && c_off[0] == 0);
+        expect_stats(0, 0, 0);
+    }
+    {  // error cases: the code, and the outputs untouched
+        Seqs rd;
+        for (const char* s : {"ACGTAC", "GTACGT", "ACGTTT"}) rd.add(s);
+        Pairs p;
+        p.add(0, 1, 30, 2);
+        p.add(1, 2, 30, 2);
+        auto call = [&](const uint8_t* seqs, const int64_t* off, int32_t n, const Pairs& q, int64_t np, int32_t mo,
+                        bool with_nc, int want) {
+            Out o(rd);
+            EXPECT(ovl_layout_host(seqs, off, n, q.a.data(), q.b.data(), q.score.data(), q.end.data(), np, 1, mo,
+                                   o.succ.data(), o.link.data(), o.contig.data(), o.offset.data(), o.on_path.data(),
+                                   o.bases.data(), o.c_off.data(), with_nc ? &o.n_contigs : nullptr) == want);
+            EXPECT(o.untouched());
+            EXPECT(!g_err.empty());
+        };
+        const std::vector<int64_t> down = {0, 6, 4, 18}, huge = {0, 6, 12, int64_t(1) << 31};
+        call(rd.data(), rd.off.data(), 3, p, p.n(), 1, false, OVL_E_ARG);
+        call(rd.data(), nullptr, 3, p, p.n(), 1, true, OVL_E_ARG);
+        call(nullptr, rd.off.data(), 3, p, p.n(), 1, true, OVL_E_ARG);
+        call(rd.data(), rd.off.data(), -1, p, p.n(), 1, true, OVL_E_ARG);
+        call(rd.data(), rd.off.data(), 3, p, -1, 1, true, OVL_E_ARG);
+        call(rd.data(), rd.off.data(), 3, p, p.n(), 0, true, OVL_E_ARG);
+        call(rd.data(), down.data(), 3, p, p.n(), 1, true, OVL_E_ARG);
+        call(rd.data(), rd.off.data(), 3, p, int64_t(1) << 31, 1, true, OVL_E_UNSUPPORTED);
+        call(rd.data(), huge.data(), 3, p, p.n(), 1, true, OVL_E_UNSUPPORTED);
+        Pairs bad = p;
+        bad.b[1] = 3;
+        call(rd.data(), rd.off.data(), 3, bad, bad.n(), 1, true, OVL_E_INDEX);
+        bad.b[1] = 2;
+        bad.a[0] = -1;
+        call(rd.data(), rd.off.data(), 3, bad, bad.n(), 1, true, OVL_E_INDEX);
+        Pairs holes = p;
+        Out o(rd);
+        EXPECT(ovl_layout_host(rd.data(), rd.off.data(), 3, holes.a.data(), nullptr, holes.score.data(),
+                               holes.end.data(), 2, 1, 1, o.succ.data(), nullptr, nullptr, nullptr, nullptr, nullptr,
+                               nullptr, &o.n_contigs) == OVL_E_ARG);
+        EXPECT(o.untouched());
+        int32_t nc = -7;
+        EXPECT(ovl_layout(nullptr, rd.data(), rd.off.data(), 3, p.a.data(), p.b.data(), p.score.data(), p.end.data(),
+                          2, 1, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &nc) == OVL_E_ARG);
+        EXPECT(ovl_layout_candidates(nullptr, 10, -1, -1, -1, 1, 1, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                     nullptr, nullptr, &nc) == OVL_E_ARG);
+        EXPECT(nc == -7 && ovl_last_layout_timing(nullptr, nullptr, nullptr, nullptr, nullptr) == OVL_E_ARG);
+    }
+    if (g_failed) {
+        fprintf(stderr, "layout_host_check: %d expectation(s) failed\n", g_failed);
+        return 1;
+    }
+    printf("layout_host_check: ok\n");
+    return 0;
+}
