@@ -118,6 +118,8 @@ Knobs read_knobs() {
     if (const char* e = getenv("OVL_READ_BEST_CHUNK")) k.read_best_chunk = std::max(0, atoi(e));
     if (const char* e = getenv("OVL_CONSENSUS_CHUNK")) k.consensus_chunk = std::max(0, atoi(e));
     if (const char* e = getenv("OVL_LAYOUT_LINK")) k.layout_runs = strcmp(e, "plain") != 0;
+    if (const char* e = getenv("OVL_SPECTRUM_VOTE")) k.spec_ballot = strcmp(e, "ballot") == 0;
+    if (const char* e = getenv("OVL_SPECTRUM_BINS")) k.spec_bins = std::min(std::max(atoi(e), 4), 1024);
     if (const char* e = getenv("OVL_PIPE_CHUNK")) {
         const long long v = atoll(e);
         if (v >= 64) k.pipe_chunk = v;
@@ -141,7 +143,7 @@ void destroy_dev(Dev* d) {
                       &d->tr_edge, &d->tr_order, &d->tr_ctr, &d->tr_out, &d->rc_off, &d->rc_head, &d->rc_order,
                       &d->rc_matrix, &d->rc_pivot, &d->rc_out, &d->rb_in, &d->rb_tile, &d->rb_res, &d->rb_bits, &d->cs_ref,
                       &d->cs_counts, &d->cs_called, &d->cs_ctr, &d->cs_hits, &d->cand_o, &d->sd_glo, &d->sd_gn, &d->ly_in,
-                      &d->ly_work, &d->ly_bases, &d->ly_temp})
+                      &d->ly_work, &d->ly_bases, &d->ly_temp, &d->sp_in, &d->sp_work})
         release(*b);
     if (d->l_tb_host) (void)hipHostFree(d->l_tb_host);
     for (hipEvent_t e : d->lb_ev)
@@ -157,6 +159,8 @@ void destroy_dev(Dev* d) {
     for (hipEvent_t e : d->sd_ev)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : d->ly_ev)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : d->sp_ev)
         if (e) (void)hipEventDestroy(e);
     free_staging(d->st_in);
     free_staging(d->st_out);

@@ -2,7 +2,8 @@
 // per-device state, and the functions that cross the host files ovl_ctx.cpp (contexts, devices, pinned memory),
 // ovl_plan.cpp (planner, kernel launch), ovl_pipeline.cpp (host-array pipeline), ovl_reads.cpp (read upload),
 // ovl_cand.cpp (candidate lists, resident grid), ovl_local_api.cpp (single alignments), ovl_depth_api.cpp (read
-// depth), ovl_consensus_api.cpp (read pileup and consensus), ovl_layout_api.cpp (best-successor layout) and the graph stages ovl_reduce_api.cpp /
+// depth), ovl_consensus_api.cpp (read pileup and consensus), ovl_layout_api.cpp (best-successor layout),
+// ovl_spectrum_api.cpp (k-mer spectrum read correction) and the graph stages ovl_reduce_api.cpp /
 // ovl_reach_api.cpp.  What the local-alignment stages share on the host is in ovl_local_host.h.
 //
 // A context (ovl_ctx) drives one or more HIP devices from one host thread.  Each
@@ -149,6 +150,13 @@ struct Knobs {
     int32_t layout_runs = 1;      // OVL_LAYOUT_LINK env (runs|plain): the layout's link kernel reduces runs of equal a
                                   // inside the wavefront before its atomics (default), or issues one atomic per
                                   // eligible pair (the measurement: DESIGN.md 4.15; tests run both)
+    int32_t spec_bins = 0;        // OVL_SPECTRUM_BINS: bins of the device histogram that ovl_correct_reads takes its
+                                  // threshold from (0: 1,024, the most; at least 4).  A first valley past the exact
+                                  // bins is taken from the counts themselves (tests reach that with 4 bins)
+    int32_t spec_ballot = 0;      // OVL_SPECTRUM_VOTE env (atomic|ballot): ovl_correct_reads' correction pass counts a
+                                  // solid work item with one LDS atomic (default) or by ballot, one add per segment:
+                                  // PhiX N = 50,000, k = 12, the pass 0.617 ms against 0.613 ms, inside the spreads
+                                  // (profiles/spectrum.json; tests run both)
     int32_t pack_direct_pct = 18; // OVL_PACK_DIRECT_PCT: packed calls into pinned arrays store this share of the
                                   // pairs (the last chunk) as int32 straight into them, over the link while the
                                   // host expands the packed chunks (tools/pack_ab.py, target point, six
@@ -266,6 +274,10 @@ struct Dev {
     // contigs' bytes and the scan's scratch
     DevBuf ly_in, ly_work, ly_bases, ly_temp;
     hipEvent_t ly_ev[5] = {};  // timing on: before and after the scoring launches, the link kernel, the forest, the spelling
+    // read correction (ovl_spectrum_api.cpp): the call's upload (offsets, window offsets, bytes) and its tables
+    // (WorkPlan: keys, sorted keys, head flags and their scan, run starts, counts, histogram, counters, outputs)
+    DevBuf sp_in, sp_work;
+    hipEvent_t sp_ev[6] = {};  // timing on: before the keys, after them, the sort, the count pass; around the correction
     // host-array pipeline: events per slot and pinned staging (slots x cap pairs x {a, b} / {score, end})
     hipEvent_t ev_k[kSlots] = {};
     int32_t* st_in = nullptr;
@@ -358,6 +370,7 @@ struct ovl_ctx {
     int64_t x_ly_links = 0, x_ly_cycles = 0, x_ly_on_path = 0;  // ovl_last_layout
     int32_t x_ly_levels = 0;
     double x_ly_ms[4] = {0.0, 0.0, 0.0, 0.0};                   // ovl_last_layout_timing
+    double x_sp_ms[4] = {0.0, 0.0, 0.0, 0.0};                   // ovl_last_correct_timing
 };
 
 int fail(const ovl_ctx* c, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));

@@ -15,7 +15,7 @@ from .engine import INDEL_DEFAULT, OverlapEngine, default_engine, encode_reads, 
 __all__ = ["OvlError", "OverlapEngine", "default_engine", "encode_reads", "score_reads", "INDEL_DEFAULT",
            "transitive_reduction", "assemble_contigs_string", "transitive_reduction2", "find_unitigs",
            "assemble_contigs", "pileup", "polish_contigs", "best_successor_layout", "layout_loop",
-           "assemble_contigs_best_successor"]
+           "assemble_contigs_best_successor", "kmer_spectrum", "solid_threshold", "correct_reads"]
 
 
 def __getattr__(name):
@@ -34,4 +34,7 @@ def __getattr__(name):
         from .layout import assemble_contigs_best_successor, layout as best_successor_layout, layout_loop
         return {"best_successor_layout": best_successor_layout, "layout_loop": layout_loop,
                 "assemble_contigs_best_successor": assemble_contigs_best_successor}[name]
+    if name in ("kmer_spectrum", "solid_threshold", "correct_reads"):
+        from . import correct
+        return getattr(correct, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -4,7 +4,8 @@ The library is built in-tree by ``csrc/Makefile`` (``__graft_entry__.build()``)
 into ``genome-assembly-using-overlap-graphs_amd/build/libovl.so``.  There is no
 CPU fallback: if the library is missing or no GPU is visible the engine
 raises ``OvlError`` (the host forms -- ``ovl_remove_cycles``, ``ovl_transitive_reduce_host``,
-``ovl_reach_reduce_host``, ``ovl_read_best_host``, ``ovl_consensus_host``, ``ovl_layout_host`` -- need neither a
+``ovl_reach_reduce_host``, ``ovl_read_best_host``, ``ovl_consensus_host``, ``ovl_layout_host``, ``ovl_kmer_spectrum_host``,
+``ovl_correct_reads_host`` -- need neither a
 context nor a GPU).  ctypes
 releases the GIL for the duration of each call.
 """
@@ -110,6 +111,11 @@ SIGNATURES = {
                                              _pi32]),
     "ovl_last_layout": (ctypes.c_int, [_P, _pi64, _pi64, _pi32, _pi64]),
     "ovl_last_layout_timing": (ctypes.c_int, [_P] + [ctypes.POINTER(ctypes.c_double)] * 4),
+    "ovl_kmer_spectrum_host": (ctypes.c_int, [_P, _P, _i32, _i32, _P, _P, _i64, _pi64]),
+    "ovl_correct_reads_host": (ctypes.c_int, [_P, _P, _i32, _i32, _i32, _P, _P, _P]),
+    "ovl_kmer_spectrum": (ctypes.c_int, [_P, _P, _P, _i32, _i32, _P, _P, _i64, _pi64]),
+    "ovl_correct_reads": (ctypes.c_int, [_P, _P, _P, _i32, _i32, _i32, _P, _P, _P]),
+    "ovl_last_correct_timing": (ctypes.c_int, [_P] + [ctypes.POINTER(ctypes.c_double)] * 4),
 }
 
 

@@ -244,6 +244,47 @@ def layout_host(reads, a, b, score, end, min_score: int = 1, min_overlap: int = 
     return _layout_result(n, outs, on_path, bases, c_off, nc.value, last_layout_host())
 
 
+CORRECT_STATS = ("kmers", "distinct", "solid", "untrusted", "changed", "ties", "threshold", "windows")
+
+
+def _spectrum_call(fn, ctx_args, buf, offs, k: int, err_ctx=None):
+    """The two-call protocol of ovl_kmer_spectrum(_host): size the arrays, then fill them."""
+    n = offs.shape[0] - 1
+    nd = ctypes.c_int64(0)
+    rc = fn(*ctx_args, _ptr(buf), _ptr(offs), n, int(k), None, None, 0, ctypes.byref(nd))
+    if rc not in (0, -5):
+        check(rc, err_ctx)
+    keys = np.zeros(max(nd.value, 1), dtype=np.uint64)
+    counts = np.zeros(max(nd.value, 1), dtype=np.int32)
+    if nd.value > 0:
+        check(fn(*ctx_args, _ptr(buf), _ptr(offs), n, int(k), _ptr(keys), _ptr(counts), nd.value, ctypes.byref(nd)),
+              err_ctx)
+    return keys[: nd.value], counts[: nd.value]
+
+
+def _correct_call(fn, ctx_args, buf, offs, k: int, min_count: int, err_ctx=None):
+    """ovl_correct_reads(_host): (the corrected bytes, the changed bases per read, the stats as a dict)."""
+    n = offs.shape[0] - 1
+    out = np.zeros(max(buf.shape[0], 1), dtype=np.uint8)
+    changed = np.zeros(max(n, 1), dtype=np.int32)
+    stats = np.zeros(8, dtype=np.int64)
+    check(fn(*ctx_args, _ptr(buf), _ptr(offs), n, int(k), int(min_count), _ptr(out), _ptr(changed), _ptr(stats)),
+          err_ctx)
+    return out[: int(offs[-1])], changed[:n], dict(zip(CORRECT_STATS, (int(v) for v in stats)))
+
+
+def kmer_spectrum_host(reads, k: int, encoded=None):
+    """``OverlapEngine.kmer_spectrum`` on one host thread (ovl_kmer_spectrum_host): no context, no GPU."""
+    buf, offs = encoded if encoded is not None else encode_reads(reads)
+    return _spectrum_call(_lib.load().ovl_kmer_spectrum_host, (), buf, offs, k)
+
+
+def correct_reads_host(reads, k: int, min_count: int = 0, encoded=None):
+    """``OverlapEngine.correct_reads`` on one host thread (ovl_correct_reads_host): no context, no GPU."""
+    buf, offs = encoded if encoded is not None else encode_reads(reads)
+    return _correct_call(_lib.load().ovl_correct_reads_host, (), buf, offs, k, min_count)
+
+
 def host_pool() -> Dict[str, int]:
     """The host thread pool's plan, recounted now (ovl_host_pool): {threads, sharers, cpus, packed}."""
     v = [ctypes.c_int32() for _ in range(4)]
@@ -685,6 +726,26 @@ class OverlapEngine:
         check(self._L.ovl_last_layout_timing(self._ctx, *[ctypes.byref(x) for x in t]), self._ctx)
         return {"links": li.value, "cycles": cy.value, "levels": lv.value, "on_path_reads": pa.value,
                 "score_ms": t[0].value, "link_ms": t[1].value, "forest_ms": t[2].value, "spell_ms": t[3].value}
+
+    def kmer_spectrum(self, reads, k: int, encoded=None):
+        """The k-mer spectrum of ``reads`` (ovl_kmer_spectrum; the rule: ``ovlgraph.correct``): the distinct keys
+        ascending (uint64) and their counts (int32)."""
+        buf, offs = encoded if encoded is not None else encode_reads(reads)
+        return _spectrum_call(self._L.ovl_kmer_spectrum, (self._ctx,), buf, offs, k, self._ctx)
+
+    def correct_reads(self, reads, k: int, min_count: int = 0, encoded=None):
+        """One round of k-mer spectrum correction (ovl_correct_reads): the corrected bytes in the layout of
+        ``encode_reads``, the changed bases per read (int32) and the stats ``engine.CORRECT_STATS`` as a dict.
+        ``min_count`` 0 takes the threshold rule."""
+        buf, offs = encoded if encoded is not None else encode_reads(reads)
+        return _correct_call(self._L.ovl_correct_reads, (self._ctx,), buf, offs, k, min_count, self._ctx)
+
+    def last_correct(self) -> Dict[str, float]:
+        """With timing on, {keys_ms, sort_ms, count_ms, correct_ms} of the last ``kmer_spectrum`` / ``correct_reads``
+        (ovl_last_correct_timing); zeros with timing off."""
+        t = [ctypes.c_double() for _ in range(4)]
+        check(self._L.ovl_last_correct_timing(self._ctx, *[ctypes.byref(x) for x in t]), self._ctx)
+        return {"keys_ms": t[0].value, "sort_ms": t[1].value, "count_ms": t[2].value, "correct_ms": t[3].value}
 
     # ---------------------------------------------------------------- graph stages
     def transitive_reduce(self, off, heads, weights) -> np.ndarray:

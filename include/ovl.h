@@ -551,6 +551,62 @@ int ovl_layout_candidates(ovl_ctx* ctx, int32_t match, int32_t mismatch, int64_t
 int ovl_last_layout(const ovl_ctx* ctx, int64_t* links, int64_t* cycles, int32_t* levels, int64_t* on_path_reads);
 int ovl_last_layout_timing(const ovl_ctx* ctx, double* score_ms, double* link_ms, double* forest_ms, double* spell_ms);
 
+/*
+ * k-mer spectrum read correction: the reads corrected against their own k-mer spectrum, before anything is scored.
+ *
+ *   Codes, keys and windows.  Codes are A = 0, C = 1, G = 2, T = 3, taken from the bytes ACGT; any other byte has no
+ *   code.  k is in [1, 31].  The key of a window r[o:o+k] whose bytes all have codes is
+ *   sum_j code(r[o+j]) << 2(k-1-j), a uint64 below 2^62, so key order is the k-mers' order as byte strings.  A window
+ *   that holds a byte without a code has no key, and so has every window of a read shorter than k.
+ *   Spectrum.  The distinct keys over all windows of all reads (reads counted as given, duplicates included) in
+ *   ascending order, each with its number of occurrences as an int32.
+ *   Threshold.  h[c] = the number of distinct keys with count c.  solid_threshold is the smallest c >= 1 with
+ *   c >= max count or h[c+1] >= h[c] (the first valley of the histogram).  A key is solid when its count is >=
+ *   min_count; a window without a key is never solid.
+ *   Correction, one round.  Every decision reads the original reads only, so reads and positions are independent of
+ *   each other and of the order in which they are handled.  For a read r of length L >= k and a position i the
+ *   covering windows are the offsets o in [max(0, i-k+1), min(i, L-k)].  Position i is trusted when at least one
+ *   covering window is solid, and stays.  An untrusted position whose byte has no code stays.  Otherwise, for each of
+ *   the three other bases x, s(x) is the number of covering windows that are solid after r[i] alone is replaced by x;
+ *   if the largest s(x) is >= 1 and strictly greater than the other two, r[i] becomes that x; on a tie, or when all
+ *   are 0, r[i] stays.  Reads shorter than k are returned as they are.  Lengths never change.
+ *
+ * Read r is seqs[offsets[r] .. offsets[r+1]).  Every argument is checked before anything runs or is written:
+ * OVL_E_ARG for null pointers (offsets; seqs with bytes to read; out_n_distinct; the output arrays with a capacity > 0;
+ * out_stats; out_changed with reads; out_seqs with bytes), n_reads < 0, capacity < 0, min_count < 0, k outside [1, 31]
+ * and offsets that decrease.
+ *
+ * ovl_kmer_spectrum: the spectrum into out_keys / out_counts (capacity entries each); *out_n_distinct receives the
+ *   number of distinct keys.  With capacity too small it writes nothing but *out_n_distinct and returns OVL_E_RANGE,
+ *   so a caller can size the buffers (capacity 0, both arrays NULL) and call again.
+ * ovl_correct_reads: one round.  min_count >= 1, or 0 for the threshold rule.  out_seqs receives the corrected bytes in
+ *   the input's layout (read r at out_seqs[offsets[r] ..); bytes outside [offsets[0], offsets[n_reads]) are not
+ *   touched; it may be seqs itself: the decisions are made from keys formed before anything is written), out_changed the changed bases per read, and out_stats eight
+ *   int64: {0 k-mers (windows with a key), 1 distinct keys, 2 solid windows, 3 untrusted positions, 4 changed bases,
+ *   5 ties (untrusted positions whose largest s(x) is >= 1 and not alone), 6 the threshold used, 7 windows}.
+ * The device forms run the kernels of ovl_spectrum.hip on the context's first device: a key pass (one wavefront per
+ *   read, keys rolled), hipcub's radix sort over 2k + 1 bits (a window without a key is ~0 and sorts last), head flags,
+ *   a scan and a scatter of (key, run length), then the correction pass over the spectrum in device memory.  Device
+ *   memory: 40 bytes per window, the reads twice and 20 bytes per read.  Limits: reads of up to k + 8,191 bases (64 KiB
+ *   of keys in LDS) and fewer than 2^31 windows; beyond either OVL_E_UNSUPPORTED, naming the read; the same when the
+ *   tables do not fit the device's free memory.
+ * ovl_kmer_spectrum_host / ovl_correct_reads_host: the rule on one host thread, with no context, no GPU and no limit
+ *   on the reads (OVL_E_UNSUPPORTED only when one key occurs 2^31 times or more).
+ * ovl_last_correct_timing (timing on): device time in ms of the key pass, the sort, the count pass (head flags, scan,
+ *   scatter, run lengths; the host's wait for the number of distinct keys lies inside it) and the correction pass (0
+ *   after ovl_kmer_spectrum) of the context's last call.
+ */
+int ovl_kmer_spectrum_host(const uint8_t* seqs, const int64_t* offsets, int32_t n_reads, int32_t k, uint64_t* out_keys,
+                           int32_t* out_counts, int64_t capacity, int64_t* out_n_distinct);
+int ovl_correct_reads_host(const uint8_t* seqs, const int64_t* offsets, int32_t n_reads, int32_t k, int32_t min_count,
+                           uint8_t* out_seqs, int32_t* out_changed, int64_t* out_stats);
+int ovl_kmer_spectrum(ovl_ctx* ctx, const uint8_t* seqs, const int64_t* offsets, int32_t n_reads, int32_t k,
+                      uint64_t* out_keys, int32_t* out_counts, int64_t capacity, int64_t* out_n_distinct);
+int ovl_correct_reads(ovl_ctx* ctx, const uint8_t* seqs, const int64_t* offsets, int32_t n_reads, int32_t k,
+                      int32_t min_count, uint8_t* out_seqs, int32_t* out_changed, int64_t* out_stats);
+int ovl_last_correct_timing(const ovl_ctx* ctx, double* keys_ms, double* sort_ms, double* count_ms,
+                            double* correct_ms);
+
 #ifdef __cplusplus
 }
 #endif
