@@ -3,14 +3,13 @@
 // piled up into six vote channels per contig base, and every base with enough votes is called by majority.  The host
 // form (ovl_consensus_host, over ovl_local_host.h's fill and walk) and the device call (ovl_consensus: the batch
 // kernel's walks stay in device memory and ovl_consensus.hip piles them up and votes there).  The pileup routine and
-// the vote rule below are the one statement both forms share.
+// the vote rule (ovl_consensus_rule.h) are the one statement both forms share.
+#include "ovl_consensus_rule.h"
 #include "ovl_local_host.h"
 
 namespace {
 
 constexpr int64_t kOpsBudget = int64_t(256) << 20;  // the walks of one chunk of reads (bytes of Dev::lb_ops)
-
-inline int32_t channel(uint8_t b) { return b == 'A' ? 0 : (b == 'C' ? 1 : (b == 'G' ? 2 : (b == 'T' ? 3 : -1))); }
 
 template <typename C>
 int check_consensus(const C* c, const uint8_t* reads, const int64_t* r_off, int32_t n_reads, const uint8_t* contigs,
@@ -40,43 +39,6 @@ int check_consensus(const C* c, const uint8_t* reads, const int64_t* r_off, int3
                         "consensus, read %d: lengths < 2^20 and match * min(n, m) < 2^24 required", r);
     }
     return OVL_OK;
-}
-
-// The pileup of one walk from cell (bi, bj): every op votes at the contig base of its cell's column (DP column j is
-// base col0 + j - 1) -- a diag in the channel of the read's byte (none for a byte outside ACGT: counted and
-// returned), a left in channel 4 (gap), an up in channel 5 (ins: the column at the left of the inserted base).
-// vote(k) receives the flat index k = base * 6 + channel.
-template <typename Vote>
-int64_t pile_ops(const int8_t* ops, int64_t cnt, const uint8_t* q, int32_t bi, int32_t bj, int64_t col0, Vote&& vote) {
-    int64_t other = 0;
-    int32_t i = bi, j = bj;
-    for (int64_t t = 0; t < cnt; ++t) {
-        const int64_t at = (col0 + j - 1) * 6;
-        if (ops[t] == 1) {
-            const int32_t ch = channel(q[i - 1]);
-            if (ch >= 0) vote(at + ch);
-            else ++other;
-            --i;
-            --j;
-        } else if (ops[t] == 2) {
-            vote(at + 5);
-            --i;
-        } else {
-            vote(at + 4);
-            --j;
-        }
-    }
-    return other;
-}
-
-// The call per contig base: with fewer than min_depth base votes it keeps its byte; else the largest of A, C, G, T
-// wins, a tie going to the contig's own byte when it is among the tied and else to the first in that order.
-inline uint8_t call_base(const int32_t* v, uint8_t own, int32_t min_depth) {
-    if ((int64_t)v[0] + v[1] + v[2] + v[3] < min_depth) return own;
-    const int32_t top = std::max(std::max(v[0], v[1]), std::max(v[2], v[3]));
-    const int32_t oc = channel(own);
-    if (oc >= 0 && v[oc] == top) return own;
-    return v[0] == top ? 'A' : (v[1] == top ? 'C' : (v[2] == top ? 'G' : 'T'));
 }
 
 void zero_aln(int32_t* aln, int32_t n_reads) {

@@ -143,7 +143,7 @@ void destroy_dev(Dev* d) {
                       &d->tr_edge, &d->tr_order, &d->tr_ctr, &d->tr_out, &d->rc_off, &d->rc_head, &d->rc_order,
                       &d->rc_matrix, &d->rc_pivot, &d->rc_out, &d->rb_in, &d->rb_tile, &d->rb_res, &d->rb_bits, &d->cs_ref,
                       &d->cs_counts, &d->cs_called, &d->cs_ctr, &d->cs_hits, &d->cand_o, &d->sd_glo, &d->sd_gn, &d->ly_in,
-                      &d->ly_work, &d->ly_bases, &d->ly_temp, &d->sp_in, &d->sp_work})
+                      &d->ly_work, &d->ly_bases, &d->ly_temp, &d->sp_in, &d->sp_work, &d->pl_in, &d->pl_slab, &d->pl_aln})
         release(*b);
     if (d->l_tb_host) (void)hipHostFree(d->l_tb_host);
     for (hipEvent_t e : d->lb_ev)
@@ -155,6 +155,8 @@ void destroy_dev(Dev* d) {
     for (hipEvent_t e : d->rb_ev)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : d->cs_ev)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : d->pl_ev)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : d->sd_ev)
         if (e) (void)hipEventDestroy(e);

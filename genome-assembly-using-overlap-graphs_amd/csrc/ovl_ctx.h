@@ -2,7 +2,8 @@
 // per-device state, and the functions that cross the host files ovl_ctx.cpp (contexts, devices, pinned memory),
 // ovl_plan.cpp (planner, kernel launch), ovl_pipeline.cpp (host-array pipeline), ovl_reads.cpp (read upload),
 // ovl_cand.cpp (candidate lists, resident grid), ovl_local_api.cpp (single alignments), ovl_depth_api.cpp (read
-// depth), ovl_consensus_api.cpp (read pileup and consensus), ovl_layout_api.cpp (best-successor layout),
+// depth), ovl_consensus_api.cpp (read pileup and consensus), ovl_consensus_placed_api.cpp (consensus at the layout's
+// placement), ovl_layout_api.cpp (best-successor layout),
 // ovl_spectrum_api.cpp (k-mer spectrum read correction) and the graph stages ovl_reduce_api.cpp /
 // ovl_reach_api.cpp.  What the local-alignment stages share on the host is in ovl_local_host.h.
 //
@@ -269,6 +270,10 @@ struct Dev {
     // the counters {n_other, n_changed, bad ops}, and the flat count indices of the single-pair reads' votes
     DevBuf cs_ref, cs_counts, cs_called, cs_ctr, cs_hits;
     hipEvent_t cs_ev[4] = {};  // timing on: a chunk's start, after its alignment launch, after its pileup; the vote
+    // placed consensus (ovl_consensus_placed_api.cpp; it shares cs_ref, cs_counts, cs_called and cs_ctr): the upload
+    // block (items, the reads' bytes), a chunk's code words ([row][lane]) and three int32 per read
+    DevBuf pl_in, pl_slab, pl_aln;
+    hipEvent_t pl_ev[3] = {};  // timing on: a round's start, after its band launches, after its vote
     // layout (ovl_layout_api.cpp): the call's inputs (ovl_layout: lengths, offsets, bytes and the four columns;
     // ovl_layout_candidates: the score and end columns and the code table), the per-read block (WorkPlan), the
     // contigs' bytes and the scan's scratch
@@ -366,6 +371,9 @@ struct ovl_ctx {
     int64_t x_cs_batch = 0, x_cs_single = 0, x_cs_ops = 0;      // ovl_last_consensus
     int32_t x_cs_launches = 0;
     double x_cs_ms[3] = {0.0, 0.0, 0.0};                        // ovl_last_consensus_timing
+    int64_t x_pl_voted = 0, x_pl_windowless = 0, x_pl_ops = 0;  // ovl_last_consensus_placed
+    int32_t x_pl_launches = 0, x_pl_rounds = 0;
+    double x_pl_ms[2] = {0.0, 0.0};                             // ovl_last_consensus_placed_timing
     double x_sd_ms[4] = {0.0, 0.0, 0.0, 0.0};                   // ovl_last_seed_timing
     int64_t x_ly_links = 0, x_ly_cycles = 0, x_ly_on_path = 0;  // ovl_last_layout
     int32_t x_ly_levels = 0;

@@ -282,6 +282,34 @@ extern "C" hipError_t ovl_launch_consensus_vote(const uint8_t* ref, const int32_
                                                 int32_t min_depth, uint8_t* called, unsigned long long* ctr,
                                                 hipStream_t stream);
 
+// placed consensus (ovl_consensus_placed.hip): one lane per item, an item being a read that has a window on its
+// contig (include/ovl.h, ovl_consensus_placed: the rule).  Lane g of the launch takes items[g]: its bytes are
+// q[q_off .. q_off + L), its window is ref[col0 .. col0 + w), whose first base is column lo of its contig, and d is
+// its placement's diagonal (offset - lo).  The lane fills the 2 * slack + 1 diagonals of the band row by row in
+// registers, writes each row's codes (2 bits per diagonal) as one 64-bit word to slab[(row - 1) * pitch + g]
+// (pitch >= n_items, rows up to the longest item of the launch), and, when its best score reaches min_vote_score,
+// walks its own words back and adds `weight` per op to counts[(col0 + column) * 6 + channel] and writes
+// aln[3 * read ..] = (score, lo + stop column, lo + best column).  ctr[0] += weight per diag op whose byte is none of
+// ACGT, ctr[3] += the items that voted, ctr[4] += their ops.  The scores are int32: the caller clamps negative ones
+// at -2^30 and keeps max(0, scores) * (L + w) below 2^30.
+struct OvlPlacedItem {
+    int64_t q_off;
+    int32_t L, w, d, col0, lo, weight, read, pad;
+};
+struct OvlPlacedArgs {
+    const OvlPlacedItem* items;
+    const uint8_t* q;
+    const uint8_t* ref;
+    unsigned long long* slab;
+    int32_t n_items, pitch;
+    int32_t slack, match, mismatch, indel, min_vote_score;
+    int32_t* counts;
+    int32_t* aln;
+    unsigned long long* ctr;
+};
+constexpr int32_t kPlacedMaxSlack = 15;  // 31 diagonals: 62 bits of codes per row
+extern "C" hipError_t ovl_launch_consensus_placed(const OvlPlacedArgs* a, hipStream_t stream);
+
 // transitive reduction of an overlap graph (ovl_reduce.hip): `blocks` persistent workgroups of kReduceThreads take
 // order[0 .. n_order) -- the nodes with out-edges, heaviest first by two-hop work -- from *counter (zeroed by the
 // caller).  edge[e] = {head, weight} of CSR edge e (heads validated in [0, n_nodes), |weight| < 2^30); a window of

@@ -14,7 +14,7 @@ from .engine import INDEL_DEFAULT, OverlapEngine, default_engine, encode_reads, 
 
 __all__ = ["OvlError", "OverlapEngine", "default_engine", "encode_reads", "score_reads", "INDEL_DEFAULT",
            "transitive_reduction", "assemble_contigs_string", "transitive_reduction2", "find_unitigs",
-           "assemble_contigs", "pileup", "polish_contigs", "best_successor_layout", "layout_loop",
+           "assemble_contigs", "pileup", "polish_contigs", "pileup_placed", "best_successor_layout", "layout_loop",
            "assemble_contigs_best_successor", "kmer_spectrum", "solid_threshold", "correct_reads"]
 
 
@@ -25,7 +25,7 @@ def __getattr__(name):
                 "assemble_contigs"):
         from . import overlapGraphs
         return getattr(overlapGraphs, name)
-    if name in ("pileup", "polish_contigs"):
+    if name in ("pileup", "polish_contigs", "pileup_placed", "pileup_placed_loop"):
         from . import consensus
         return getattr(consensus, name)
     # the best-successor layout's entry points.  The function layout.layout is best_successor_layout here: the name

@@ -198,6 +198,39 @@ def consensus_host(reads, contigs, place, read_length: int, match: int = 10, mis
     return _consensus_result(R, total, cnt, called, aln, n_changed, n_other)
 
 
+def _placed_call(fn, head, reads, contigs, contig, offset, slack, weights, rounds, min_depth, min_vote_score, match,
+                 mismatch, indel, counts):
+    """One call of ovl_consensus_placed / ovl_consensus_placed_host (``head``: the arguments before ``reads``)."""
+    R, C, buf, r_off, c_off, contig, total, cnt, called, aln = _consensus_arrays(reads, contigs, contig, counts)
+    offset = np.ascontiguousarray(offset, dtype=np.int32)
+    if offset.shape != (R,):
+        raise OvlError(-1, "offset must hold one int32 per read")
+    if weights is not None:
+        weights = np.ascontiguousarray(weights, dtype=np.int32)
+        if weights.shape != (R,):
+            raise OvlError(-1, "weights must hold one int32 per read")
+    n_changed, n_other, total_changed = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+    rounds_done = ctypes.c_int32(0)
+    rc = fn(*head, _ptr(buf), _ptr(r_off), R, _ptr(weights) if weights is not None else None, _ptr(buf), _ptr(c_off),
+            C, _ptr(contig), _ptr(offset), int(slack), int(match), int(mismatch), int(indel), int(min_vote_score),
+            int(min_depth), int(rounds), _ptr(cnt) if counts else None, _ptr(called), ctypes.byref(n_changed),
+            ctypes.byref(n_other), ctypes.byref(total_changed), ctypes.byref(rounds_done), _ptr(aln))
+    check(rc, head[0] if head else None)
+    res = _consensus_result(R, total, cnt, called, aln, n_changed, n_other)
+    res["total_changed"] = int(total_changed.value)
+    res["rounds"] = int(rounds_done.value)
+    return res
+
+
+def consensus_placed_host(reads, contigs, contig, offset, slack: int = 8, weights=None, rounds: int = 1,
+                          min_depth: int = 3, min_vote_score: int = 1, match: int = 10, mismatch: int = -1,
+                          indel: int = -1, counts: bool = True) -> Dict[str, object]:
+    """``OverlapEngine.consensus_placed`` on one host thread (ovl_consensus_placed_host): no context, no GPU, any
+    slack."""
+    return _placed_call(_lib.load().ovl_consensus_placed_host, (), reads, contigs, contig, offset, slack, weights,
+                        rounds, min_depth, min_vote_score, match, mismatch, indel, counts)
+
+
 def _layout_outputs(n: int, total: int):
     """The arrays that receive a layout: succ, link, contig, offset (int32 per read), on_path (uint8 per read), the
     contigs' bytes (at most the reads' bytes) and their offsets (n + 1 int64)."""
@@ -685,6 +718,30 @@ class OverlapEngine:
         check(self._L.ovl_last_consensus_timing(self._ctx, *[ctypes.byref(x) for x in t]), self._ctx)
         return {"batch_reads": a.value, "single_reads": b.value, "ops": o.value, "launches": n.value,
                 "align_ms": t[0].value, "pileup_ms": t[1].value, "vote_ms": t[2].value}
+
+    def consensus_placed(self, reads, contigs, contig, offset, slack: int = 8, weights=None, rounds: int = 1,
+                         min_depth: int = 3, min_vote_score: int = 1, match: int = 10, mismatch: int = -1,
+                         indel: int = -1, counts: bool = True) -> Dict[str, object]:
+        """Placed consensus (ovl_consensus_placed; the rule: include/ovl.h and ``consensus.pileup_placed_loop``): read
+        r votes with ``weights[r]`` (None: 1) on contig position ``contig[r]`` (-1: no vote), aligned inside the band of
+        ``slack`` diagonals around its placement ``offset[r]``, for up to ``rounds`` rounds on the device.  Returns
+        what ``consensus`` returns, of the last round, plus ``total_changed`` and ``rounds``."""
+        return _placed_call(self._L.ovl_consensus_placed, (self._ctx,), reads, contigs, contig, offset, slack, weights,
+                            rounds, min_depth, min_vote_score, match, mismatch, indel, counts)
+
+    def last_consensus_placed(self) -> Dict[str, float]:
+        """{voted_reads, windowless_reads, ops, launches, rounds} of the last ``consensus_placed``
+        (ovl_last_consensus_placed): the reads that voted in the last round, the placed reads without a window, the
+        ops of the last round's walks, the band kernel's launches and the rounds; with timing on also {band_ms,
+        vote_ms} over all rounds (ovl_last_consensus_placed_timing)."""
+        a, b, o = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        n, r = ctypes.c_int32(), ctypes.c_int32()
+        check(self._L.ovl_last_consensus_placed(self._ctx, ctypes.byref(a), ctypes.byref(b), ctypes.byref(o),
+                                                ctypes.byref(n), ctypes.byref(r)), self._ctx)
+        t = [ctypes.c_double() for _ in range(2)]
+        check(self._L.ovl_last_consensus_placed_timing(self._ctx, *[ctypes.byref(x) for x in t]), self._ctx)
+        return {"voted_reads": a.value, "windowless_reads": b.value, "ops": o.value, "launches": n.value,
+                "rounds": r.value, "band_ms": t[0].value, "vote_ms": t[1].value}
 
     def layout(self, reads, a, b, score, end, min_score: int = 1, min_overlap: int = 1,
                encoded=None) -> Dict[str, object]:

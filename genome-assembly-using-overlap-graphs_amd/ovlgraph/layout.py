@@ -154,7 +154,8 @@ def layout(reads: Sequence[str], a, b, score, end, min_score: int = 1, min_overl
 def assemble_contigs_best_successor(reads: Sequence[str], k: int = 12, seeds: str = "any", min_score: int = 1,
                                     min_overlap: int = 1, min_contig_length: int = 0, engine=None, scorer=None,
                                     candidates: str = "auto", timing: Optional[dict] = None,
-                                    layout_out: Optional[dict] = None) -> List[str]:
+                                    layout_out: Optional[dict] = None, polish: int = 0, slack: int = 8,
+                                    min_depth: int = 3) -> List[str]:
     """Contigs of ``reads`` by the best-successor layout of their candidate pairs (``seeds``: the candidate rule,
     ``overlapGraphs.SEED_MODES``), scored as the reference scores (match 10, mismatch -1, no gaps).
 
@@ -164,7 +165,13 @@ def assemble_contigs_best_successor(reads: Sequence[str], k: int = 12, seeds: st
     device's (OVL_E_UNSUPPORTED): the host list, its scores (through ``scorer`` or the engine), then ``layout``.
     ``min_contig_length`` drops shorter contigs (the contigs that grow from a truncated read at the genome's end are
     about one read long).  ``layout_out`` receives the placement arrays, the counts and, under ``"reads"``, the
-    distinct reads they index; ``timing`` the stage times in seconds."""
+    distinct reads they index; ``timing`` the stage times in seconds.
+
+    ``polish=R > 0`` polishes the contigs for up to R rounds of ``consensus.pileup_placed`` at the layout's own
+    placement (band half-width ``slack``, a base called from ``min_depth`` votes), every distinct read voting with its
+    copy count, before ``min_contig_length`` filters.  ``layout_out`` then also receives ``"copies"``, ``"polished"``
+    (the contigs returned, unfiltered; ``"contigs"`` stays the layout's) and ``"pileup"``, and ``timing`` a
+    ``"polish"`` stage.  With ``polish=0`` nothing of this happens."""
     from . import overlapGraphs as og
     from .candidates import dedup_reads
     from .engine import INDEL_DEFAULT, default_engine, encode_reads
@@ -172,7 +179,9 @@ def assemble_contigs_best_successor(reads: Sequence[str], k: int = 12, seeds: st
         raise ValueError(f"candidates must be one of {og.CANDIDATE_MODES}")
     og._check_seeds(seeds, k)
     st = og._Stages(timing)
-    distinct, _counts = dedup_reads(reads)
+    if polish < 0:
+        raise ValueError("polish must be >= 0")
+    distinct, copies = dedup_reads(reads)
     _check_text(distinct)
     st("dedup")
     res = None
@@ -203,4 +212,13 @@ def assemble_contigs_best_successor(reads: Sequence[str], k: int = 12, seeds: st
         layout_out.update({key: res[key] for key in _ARRAYS + ("links", "cycles", "levels", "on_path_reads")})
         layout_out["contigs"] = list(res["contigs"])
         layout_out["reads"] = distinct
-    return [c for c in res["contigs"] if len(c) >= min_contig_length]
+    contigs = res["contigs"]
+    if polish > 0:
+        from .consensus import pileup_placed
+        pile = pileup_placed(contigs, distinct, res["contig"], res["offset"], slack, copies, polish, min_depth,
+                             engine=engine)
+        contigs = list(pile.called)
+        st("polish")
+        if layout_out is not None:
+            layout_out.update({"copies": copies, "polished": contigs, "pileup": pile})
+    return [c for c in contigs if len(c) >= min_contig_length]

@@ -486,6 +486,70 @@ int ovl_last_consensus(const ovl_ctx* ctx, int64_t* batch_reads, int64_t* single
 int ovl_last_consensus_timing(const ovl_ctx* ctx, double* align_ms, double* pileup_ms, double* vote_ms);
 
 /*
+ * Placed consensus: every read votes on its contig where a layout placed it (ovl_layout's contig[r] and offset[r]),
+ * aligned only inside a band around the diagonal the placement names, with a weight (a distinct read's copy count),
+ * for up to `rounds` rounds.
+ *
+ *   Inputs: reads (reads, r_off) and weight[r] (NULL: 1 for every read); contigs (contigs, c_off; a repeated contig is
+ *   a separate position); contig[r] in [-1, n_contigs), -1 meaning no vote; offset[r], any int32; slack >= 0, match,
+ *   mismatch, indel, min_vote_score >= 1, min_depth >= 1, rounds >= 1.
+ *   A read r of length L > 0 with weight > 0, placed on contig c of length m, votes only if it passes every step:
+ *   1. Window.  In int64, lo = max(0, offset - slack) and hi = min(m, offset + L + slack).  If hi <= lo the read casts
+ *      no vote.  Otherwise t = contig[lo:hi), w = hi - lo, d = offset - lo.
+ *   2. Band.  DP cell (i, j), 1 <= i <= L, 1 <= j <= w, is in the band iff |(j - i) - d| <= slack.  Row 0, column 0
+ *      and every cell outside the band hold value 0 and code 0.
+ *   3. Fill.  Every in-band cell is filled by local alignment's statement (aligners.py:106-137): dg, u and l from the
+ *      three neighbours' values, an out-of-band neighbour counting as 0.  If dg >= u && dg >= l && dg >= 0 the cell
+ *      takes diag (code 1); else if u >= l && u >= 0, up (code 2); else if l >= 0, left (code 3); else its value is 0.
+ *      The code is stored only when the value is > 0.  The statement is total for any indel.
+ *   4. Best cell.  The first strict maximum over the in-band cells in row-major order.  A best score below
+ *      min_vote_score casts no vote and leaves the read's aln at zeros.
+ *   5. Walk.  From the best cell along the codes (aligners.py:139-161); it stops at code 0.
+ *   6. Votes.  The ops vote as in ovl_consensus, on the contig's own columns (lo + window column): diag in channel A,
+ *      C, G or T by the read's byte, left in gap, up in ins at the column at the left of the inserted base; a byte
+ *      outside ACGT on a diagonal goes to *n_other.  Every +1 is +weight[r], n_other included.  aln[r] is (score,
+ *      lo + the column where the walk stops, lo + the best cell's column).
+ *   7. Call.  Every base is called as in ovl_consensus (min_depth, majority, ties to the contig's own byte).
+ *   8. Rounds.  Round k + 1 runs on the contigs as round k called them (lengths never change, so the placement stays
+ *      valid); the loop stops after a round that changed nothing, or after `rounds` rounds.  counts, *n_changed,
+ *      *n_other and aln are the last round's; called is the contigs after the last round; *total_changed counts the
+ *      bases of called that differ from the input contigs; *rounds_done is the number of rounds that ran.
+ *   With slack >= max(L, m), weight NULL, min_vote_score 1 and one round this is ovl_consensus with place = contig and
+ *   read_length 0; `rounds` = R equals R calls with rounds = 1, each fed the call before's called bytes.
+ *
+ * counts and aln may be NULL.  Every argument is checked before anything is launched or written: OVL_E_ARG for null
+ * pointers, negative counts, slack or weights, min_vote_score, min_depth or rounds below 1, and offsets that decrease;
+ * OVL_E_INDEX for contig[r] outside [-1, n_contigs); OVL_E_UNSUPPORTED when the sum of weight * length over the placed
+ * reads reaches 2^31 (below it no channel can overflow), when the contigs together reach 2^31 bases, and for a placed
+ * read beyond ovl_local_align's limits (lengths < 2^20, match * min(L, m) < 2^24).  The device form also returns
+ * OVL_E_UNSUPPORTED for slack > 15 and for a placed read with max(0, match, mismatch, indel) * (L + w) >= 2^30 (its
+ * cells are int32); the host form takes any slack and scoring.
+ * ovl_consensus_placed (the context's first device): one lane per read fills the band row by row in registers (9, 17
+ * or 31 diagonals for slack <= 4, 8, 15), keeps a row's codes as one 64-bit word in device memory, walks its own
+ * words back and adds its weight per op; ovl_consensus's vote kernel calls the bases, and between rounds the called
+ * bytes become the contigs on the device: only the counters cross the link.  The call uploads its reads.  Reads are
+ * taken in chunks under a 256 MiB budget of code words (OVL_CONSENSUS_CHUNK caps the reads per chunk, for tests).
+ * ovl_last_consensus_placed: of the last ovl_consensus_placed, the reads that voted in the last round, the placed
+ * reads without a window, the ops of the last round's walks, the band kernel's launches and the rounds that ran.
+ * ovl_last_consensus_placed_timing (timing on): the band kernel's and the vote kernel's time over all rounds, in ms.
+ */
+int ovl_consensus_placed(ovl_ctx* ctx, const uint8_t* reads, const int64_t* r_off, int32_t n_reads,
+                         const int32_t* weight, const uint8_t* contigs, const int64_t* c_off, int32_t n_contigs,
+                         const int32_t* contig, const int32_t* offset, int32_t slack, int32_t match, int32_t mismatch,
+                         int64_t indel, int32_t min_vote_score, int32_t min_depth, int32_t rounds, int32_t* counts,
+                         uint8_t* called, int64_t* n_changed, int64_t* n_other, int64_t* total_changed,
+                         int32_t* rounds_done, int32_t* aln);
+int ovl_consensus_placed_host(const uint8_t* reads, const int64_t* r_off, int32_t n_reads, const int32_t* weight,
+                              const uint8_t* contigs, const int64_t* c_off, int32_t n_contigs, const int32_t* contig,
+                              const int32_t* offset, int32_t slack, int32_t match, int32_t mismatch, int64_t indel,
+                              int32_t min_vote_score, int32_t min_depth, int32_t rounds, int32_t* counts,
+                              uint8_t* called, int64_t* n_changed, int64_t* n_other, int64_t* total_changed,
+                              int32_t* rounds_done, int32_t* aln);
+int ovl_last_consensus_placed(const ovl_ctx* ctx, int64_t* voted_reads, int64_t* windowless_reads, int64_t* ops,
+                              int32_t* launches, int32_t* rounds);
+int ovl_last_consensus_placed_timing(const ovl_ctx* ctx, double* band_ms, double* vote_ms);
+
+/*
  * Best-successor layout: contigs straight from the score columns, without a graph object.
  *
  *   Inputs: n reads with lengths len[r]; E pairs (a[p], b[p], score[p], end[p]) in list order; min_score and
