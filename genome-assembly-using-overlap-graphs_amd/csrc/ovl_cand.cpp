@@ -4,37 +4,91 @@
 
 namespace {
 
-// Keys, sort, per-read groups and their offsets; the list length comes back in d->cand_tail.
-int cand_count(Dev* c, int32_t k) {
+// The resident list's consumers are sized for fewer than 2^31 pairs (device_cuts' cost sums, the tile ids of
+// ensure_heavy); a seed list can pass that where the reference's rule would not.
+constexpr int64_t kSeedMaxPairs = (int64_t(1) << 31) - 1;
+
+// What ovl_seed_candidates' rule adds to an enumeration (null: ovl_candidates' rule)
+struct SeedRule {
+    int32_t n_long, max_off;
+    bool timing;
+};
+
+OvlSeedArgs seed_args(Dev* c, int32_t k, const SeedRule& r) {
+    OvlSeedArgs s{};
+    s.codes = as<uint8_t>(c->codes);
+    s.off = as<int64_t>(c->off);
+    s.len = as<int32_t>(c->len);
+    s.n_reads = c->n_reads;
+    s.k = k;
+    s.bits = c->planes;  // symbol codes are dense: < 2^planes
+    s.sorted = as<uint64_t>(c->k_sorted);
+    s.order = as<int32_t>(c->k_order);
+    s.n_long = r.n_long;
+    s.pre_key = as<uint64_t>(c->k_pre);
+    s.max_off = r.max_off;
+    s.grp_lo = as<int32_t>(c->sd.glo);
+    s.grp_n = as<int32_t>(c->sd.gn);
+    s.cnt = as<int64_t>(c->k_cnt);
+    s.offs = as<int64_t>(c->k_offs);
+    s.out_a = as<int32_t>(c->cand_a);
+    s.out_b = as<int32_t>(c->cand_b);
+    s.out_o = as<int32_t>(c->sd.offs);
+    return s;
+}
+
+// The first half of an enumeration by either rule: keys, sort, per-read counts and their offsets; the list length
+// comes back in c->cand_tail.  ovl_candidates' rule (seed null) drops the resident list first and, at k = 0, needs no
+// keys; the seed rule works in scratch only (the resident list is untouched) and marks its phases for timing.
+int enum_count(Dev* c, int32_t k, const SeedRule* seed) {
     HIPCHK(c, hipSetDevice(c->device));
-    c->cand_n = -1;
-    c->heavy_for = -1;
+    if (!seed) {
+        c->cand_n = -1;
+        c->heavy_for = -1;
+    }
     const int32_t n = c->n_reads;
     const size_t nr = (size_t)std::max(n, 1);
-    const int all = k == 0 ? 1 : 0;
-    const int32_t bits = c->planes;  // symbol codes are dense: < 2^planes
+    const bool keyed = seed || k != 0;
     hipStream_t s = c->stream;
-    HIPCHK(c, ensure(c->k_lo, nr * sizeof(int64_t)));
-    HIPCHK(c, ensure(c->k_hi, nr * sizeof(int64_t)));
-    HIPCHK(c, ensure(c->k_cnt, nr * sizeof(int64_t)));
-    HIPCHK(c, ensure(c->k_offs, nr * sizeof(int64_t)));
+    for (DevBuf* b : {&c->k_cnt, &c->k_offs}) HIPCHK(c, ensure(*b, nr * sizeof(int64_t)));
+    if (!seed)
+        for (DevBuf* b : {&c->k_lo, &c->k_hi}) HIPCHK(c, ensure(*b, nr * sizeof(int64_t)));
+    if (keyed) {
+        for (DevBuf* b : {&c->k_pre, &c->k_sorted}) HIPCHK(c, ensure(*b, nr * sizeof(uint64_t)));
+        for (DevBuf* b : {&c->k_iota, &c->k_order}) HIPCHK(c, ensure(*b, nr * sizeof(int32_t)));
+        if (!seed) HIPCHK(c, ensure(c->k_suf, nr * sizeof(uint64_t)));
+    }
+    if (seed && c->k.seed_keep)
+        for (DevBuf* b : {&c->sd.glo, &c->sd.gn})
+            HIPCHK(c, ensure(*b, (size_t)std::max<int64_t>(c->codes_bytes, 1) * sizeof(int32_t)));
     size_t temp = 0;
     HIPCHK(c, ovl_cand_temp_bytes(n, &temp));
     HIPCHK(c, ensure(c->k_temp, temp));
-    if (!all) {
-        HIPCHK(c, ensure(c->k_pre, nr * sizeof(uint64_t)));
-        HIPCHK(c, ensure(c->k_suf, nr * sizeof(uint64_t)));
-        HIPCHK(c, ensure(c->k_sorted, nr * sizeof(uint64_t)));
-        HIPCHK(c, ensure(c->k_iota, nr * sizeof(int32_t)));
-        HIPCHK(c, ensure(c->k_order, nr * sizeof(int32_t)));
-        HIPCHK(c, ovl_cand_keys(as<uint8_t>(c->codes), as<int64_t>(c->off), as<int32_t>(c->len), n, k, bits,
+    StageTimer<6>& t = c->sd.timer;
+    HIPCHK(c, t.arm(seed && seed->timing));
+    HIPCHK(c, t.mark(0, s));
+    if (seed)
+        HIPCHK(c, ovl_seed_keys(as<uint8_t>(c->codes), as<int64_t>(c->off), as<int32_t>(c->len), n, k, c->planes,
+                                as<uint64_t>(c->k_pre), as<int32_t>(c->k_iota), s));
+    else if (keyed)
+        HIPCHK(c, ovl_cand_keys(as<uint8_t>(c->codes), as<int64_t>(c->off), as<int32_t>(c->len), n, k, c->planes,
                                 as<uint64_t>(c->k_pre), as<uint64_t>(c->k_suf), as<int32_t>(c->k_iota), s));
+    HIPCHK(c, t.mark(1, s));
+    if (keyed)
         HIPCHK(c, ovl_cand_sort(c->k_temp.p, c->k_temp.bytes, as<uint64_t>(c->k_pre), as<uint64_t>(c->k_sorted),
                                 as<int32_t>(c->k_iota), as<int32_t>(c->k_order), n, s));
+    HIPCHK(c, t.mark(2, s));
+    if (!seed) {
+        HIPCHK(c, ovl_cand_count(as<uint64_t>(c->k_sorted), as<uint64_t>(c->k_pre), as<uint64_t>(c->k_suf), n,
+                                 keyed ? 0 : 1, as<int64_t>(c->k_lo), as<int64_t>(c->k_hi), as<int64_t>(c->k_cnt), s));
+    } else if (seed->max_off > 0) {
+        const OvlSeedArgs a = seed_args(c, k, *seed);
+        HIPCHK(c, ovl_seed_count(&a, c->k.seed_keep, s));
+    } else if (n > 0) {  // no read is longer than k
+        HIPCHK(c, hipMemsetAsync(c->k_cnt.p, 0, (size_t)n * sizeof(int64_t), s));
     }
-    HIPCHK(c, ovl_cand_count(as<uint64_t>(c->k_sorted), as<uint64_t>(c->k_pre), as<uint64_t>(c->k_suf), n, all,
-                             as<int64_t>(c->k_lo), as<int64_t>(c->k_hi), as<int64_t>(c->k_cnt), s));
     HIPCHK(c, ovl_cand_scan(c->k_temp.p, c->k_temp.bytes, as<int64_t>(c->k_cnt), as<int64_t>(c->k_offs), n, s));
+    HIPCHK(c, t.mark(3, s));
     c->cand_tail[0] = c->cand_tail[1] = 0;
     if (n > 0) {
         HIPCHK(c, hipMemcpyAsync(&c->cand_tail[0], as<int64_t>(c->k_offs) + (n - 1), sizeof(int64_t),
@@ -57,6 +111,18 @@ int cand_emit(Dev* c, int32_t k) {
     return OVL_OK;
 }
 
+int seed_emit(Dev* c, int32_t k, const SeedRule& r, int64_t total) {
+    HIPCHK(c, hipSetDevice(c->device));
+    c->cand_n = -1;  // from here the previous list is gone
+    c->heavy_for = -1;
+    for (DevBuf* b : {&c->cand_a, &c->cand_b, &c->sd.offs}) HIPCHK(c, ensure(*b, (size_t)total * sizeof(int32_t)));
+    const OvlSeedArgs a = seed_args(c, k, r);
+    HIPCHK(c, c->sd.timer.mark(4, c->stream));
+    if (total > 0) HIPCHK(c, ovl_seed_emit(&a, c->k.seed_keep, c->stream));
+    HIPCHK(c, c->sd.timer.mark(5, c->stream));
+    return OVL_OK;
+}
+
 }  // namespace
 
 OVL_API int ovl_candidates(ovl_ctx* ctx, int32_t k, int64_t* out_n_pairs) {
@@ -76,21 +142,11 @@ OVL_API int ovl_candidates(ovl_ctx* ctx, int32_t k, int64_t* out_n_pairs) {
     // phases overlap across devices
     int rc = OVL_OK;
     for (Dev* d : ctx->devs)
-        if ((rc = cand_count(d, k)) != OVL_OK) break;
-    for (Dev* d : ctx->devs) {
-        (void)hipSetDevice(d->device);
-        hipError_t e = hipStreamSynchronize(d->stream);
-        if (rc == OVL_OK && e != hipSuccess) rc = fail(ctx, OVL_E_HIP, "ovl_candidates: %s", hipGetErrorString(e));
-    }
-    if (rc != OVL_OK) return rc;
+        if ((rc = enum_count(d, k, nullptr)) != OVL_OK) break;
+    if ((rc = sync_devices(ctx, rc, "ovl_candidates")) != OVL_OK) return rc;
     for (Dev* d : ctx->devs)
         if ((rc = cand_emit(d, k)) != OVL_OK) break;
-    for (Dev* d : ctx->devs) {
-        (void)hipSetDevice(d->device);
-        hipError_t e = hipStreamSynchronize(d->stream);
-        if (rc == OVL_OK && e != hipSuccess) rc = fail(ctx, OVL_E_HIP, "ovl_candidates: %s", hipGetErrorString(e));
-    }
-    if (rc != OVL_OK) return rc;
+    if ((rc = sync_devices(ctx, rc, "ovl_candidates")) != OVL_OK) return rc;
     const int64_t total = d0->cand_tail[0] + d0->cand_tail[1];
     for (Dev* d : ctx->devs) {
         d->cand_n = total;
@@ -100,102 +156,6 @@ OVL_API int ovl_candidates(ovl_ctx* ctx, int32_t k, int64_t* out_n_pairs) {
     *out_n_pairs = total;
     return OVL_OK;
 }
-
-// ----------------------------------------------------------------------------- seed candidates
-namespace {
-
-// The resident list's consumers are sized for fewer than 2^31 pairs (device_cuts' cost sums, the tile ids of
-// ensure_heavy); a seed list can pass that where the reference's rule would not.
-constexpr int64_t kSeedMaxPairs = (int64_t(1) << 31) - 1;
-
-OvlSeedArgs seed_args(Dev* c, int32_t k, int32_t n_long, int32_t max_off) {
-    OvlSeedArgs s{};
-    s.codes = as<uint8_t>(c->codes);
-    s.off = as<int64_t>(c->off);
-    s.len = as<int32_t>(c->len);
-    s.n_reads = c->n_reads;
-    s.k = k;
-    s.bits = c->planes;  // symbol codes are dense: < 2^planes
-    s.sorted = as<uint64_t>(c->k_sorted);
-    s.order = as<int32_t>(c->k_order);
-    s.n_long = n_long;
-    s.pre_key = as<uint64_t>(c->k_pre);
-    s.max_off = max_off;
-    s.grp_lo = as<int32_t>(c->sd_glo);
-    s.grp_n = as<int32_t>(c->sd_gn);
-    s.cnt = as<int64_t>(c->k_cnt);
-    s.offs = as<int64_t>(c->k_offs);
-    s.out_a = as<int32_t>(c->cand_a);
-    s.out_b = as<int32_t>(c->cand_b);
-    s.out_o = as<int32_t>(c->cand_o);
-    return s;
-}
-
-// Keys, sort, per-read counts and their offsets, in scratch only (the resident list is untouched); the list length
-// comes back in d->cand_tail.
-int seed_count(Dev* c, int32_t k, int32_t n_long, int32_t max_off, bool timing) {
-    HIPCHK(c, hipSetDevice(c->device));
-    const int32_t n = c->n_reads;
-    const size_t nr = (size_t)std::max(n, 1);
-    hipStream_t s = c->stream;
-    for (DevBuf* b : {&c->k_pre, &c->k_sorted}) HIPCHK(c, ensure(*b, nr * sizeof(uint64_t)));
-    for (DevBuf* b : {&c->k_iota, &c->k_order}) HIPCHK(c, ensure(*b, nr * sizeof(int32_t)));
-    for (DevBuf* b : {&c->k_cnt, &c->k_offs}) HIPCHK(c, ensure(*b, nr * sizeof(int64_t)));
-    if (c->k.seed_keep)
-        for (DevBuf* b : {&c->sd_glo, &c->sd_gn})
-            HIPCHK(c, ensure(*b, (size_t)std::max<int64_t>(c->codes_bytes, 1) * sizeof(int32_t)));
-    size_t temp = 0;
-    HIPCHK(c, ovl_cand_temp_bytes(n, &temp));
-    HIPCHK(c, ensure(c->k_temp, temp));
-    if (timing) {
-        HIPCHK(c, ensure_events(c->sd_ev));
-        HIPCHK(c, hipEventRecord(c->sd_ev[0], s));
-    }
-    HIPCHK(c, ovl_seed_keys(as<uint8_t>(c->codes), as<int64_t>(c->off), as<int32_t>(c->len), n, k, c->planes,
-                            as<uint64_t>(c->k_pre), as<int32_t>(c->k_iota), s));
-    if (timing) HIPCHK(c, hipEventRecord(c->sd_ev[1], s));
-    HIPCHK(c, ovl_cand_sort(c->k_temp.p, c->k_temp.bytes, as<uint64_t>(c->k_pre), as<uint64_t>(c->k_sorted),
-                            as<int32_t>(c->k_iota), as<int32_t>(c->k_order), n, s));
-    if (timing) HIPCHK(c, hipEventRecord(c->sd_ev[2], s));
-    const OvlSeedArgs a = seed_args(c, k, n_long, max_off);
-    if (max_off > 0) HIPCHK(c, ovl_seed_count(&a, c->k.seed_keep, s));
-    else if (n > 0)  // no read is longer than k
-        HIPCHK(c, hipMemsetAsync(c->k_cnt.p, 0, (size_t)n * sizeof(int64_t), s));
-    HIPCHK(c, ovl_cand_scan(c->k_temp.p, c->k_temp.bytes, as<int64_t>(c->k_cnt), as<int64_t>(c->k_offs), n, s));
-    if (timing) HIPCHK(c, hipEventRecord(c->sd_ev[3], s));
-    c->cand_tail[0] = c->cand_tail[1] = 0;
-    if (n > 0) {
-        HIPCHK(c, hipMemcpyAsync(&c->cand_tail[0], as<int64_t>(c->k_offs) + (n - 1), sizeof(int64_t),
-                                 hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipMemcpyAsync(&c->cand_tail[1], as<int64_t>(c->k_cnt) + (n - 1), sizeof(int64_t),
-                                 hipMemcpyDeviceToHost, s));
-    }
-    return OVL_OK;
-}
-
-int seed_emit(Dev* c, int32_t k, int32_t n_long, int32_t max_off, int64_t total, bool timing) {
-    HIPCHK(c, hipSetDevice(c->device));
-    c->cand_n = -1;  // from here the previous list is gone
-    c->heavy_for = -1;
-    for (DevBuf* b : {&c->cand_a, &c->cand_b, &c->cand_o}) HIPCHK(c, ensure(*b, (size_t)total * sizeof(int32_t)));
-    const OvlSeedArgs a = seed_args(c, k, n_long, max_off);
-    if (timing) HIPCHK(c, hipEventRecord(c->sd_ev[4], c->stream));
-    if (total > 0) HIPCHK(c, ovl_seed_emit(&a, c->k.seed_keep, c->stream));
-    if (timing) HIPCHK(c, hipEventRecord(c->sd_ev[5], c->stream));
-    return OVL_OK;
-}
-
-int seed_sync(ovl_ctx* ctx, int rc) {
-    for (Dev* d : ctx->devs) {
-        (void)hipSetDevice(d->device);
-        hipError_t e = hipStreamSynchronize(d->stream);
-        if (rc == OVL_OK && e != hipSuccess)
-            rc = fail(ctx, OVL_E_HIP, "ovl_seed_candidates: %s", hipGetErrorString(e));
-    }
-    return rc;
-}
-
-}  // namespace
 
 OVL_API int ovl_seed_candidates(ovl_ctx* ctx, int32_t k, int64_t* out_n_pairs) {
     if (!ctx) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
@@ -207,38 +167,29 @@ OVL_API int ovl_seed_candidates(ovl_ctx* ctx, int32_t k, int64_t* out_n_pairs) {
     if ((int64_t)k * bits > 58)
         return fail(ctx, OVL_E_UNSUPPORTED, "k=%d with %d-bit symbols does not fit a 64-bit key (k * bits <= 58)", k,
                     bits);
-    const int32_t max_off = std::max(d0->lmax - k, 0);
-    if (max_off > OVL_SEED_MAX_OFFSETS)
+    SeedRule rule{0, std::max(d0->lmax - k, 0), ctx->timing != 0};
+    if (rule.max_off > OVL_SEED_MAX_OFFSETS)
         return fail(ctx, OVL_E_UNSUPPORTED, "seed candidates take reads of up to k + %d bases (longest is %d)",
                     OVL_SEED_MAX_OFFSETS, d0->lmax);
-    int32_t n_long = 0;
-    for (int32_t l : ctx->h_len) n_long += l >= k ? 1 : 0;
+    for (int32_t l : ctx->h_len) rule.n_long += l >= k ? 1 : 0;
     quiet(ctx);
     DeviceGuard guard;
     CpuShare::get().refresh();
-    const bool timing = ctx->timing != 0;
     // every device enumerates the same list from its own copy of the reads, as in ovl_candidates
     int rc = OVL_OK;
     for (Dev* d : ctx->devs)
-        if ((rc = seed_count(d, k, n_long, max_off, timing)) != OVL_OK) break;
-    rc = seed_sync(ctx, rc);
-    if (rc != OVL_OK) return rc;
+        if ((rc = enum_count(d, k, &rule)) != OVL_OK) break;
+    if ((rc = sync_devices(ctx, rc, "ovl_seed_candidates")) != OVL_OK) return rc;
     const int64_t total = d0->cand_tail[0] + d0->cand_tail[1];
     if (total > kSeedMaxPairs)
         return fail(ctx, OVL_E_UNSUPPORTED, "seed candidates: %lld pairs, the resident list holds up to %lld",
                     (long long)total, (long long)kSeedMaxPairs);
     for (Dev* d : ctx->devs)
-        if ((rc = seed_emit(d, k, n_long, max_off, total, timing)) != OVL_OK) break;
-    rc = seed_sync(ctx, rc);
-    if (rc != OVL_OK) return rc;
-    for (int i = 0; i < 4; ++i) ctx->x_sd_ms[i] = 0.0;
-    if (timing)
-        for (int i = 0; i < 4; ++i) {
-            float ms = 0.0f;
-            (void)hipSetDevice(d0->device);
-            const int e0 = i < 3 ? i : 4;  // keys, sort, count + scan; the emit has its own start
-            if (hipEventElapsedTime(&ms, d0->sd_ev[e0], d0->sd_ev[e0 + 1]) == hipSuccess) ctx->x_sd_ms[i] = ms;
-        }
+        if ((rc = seed_emit(d, k, rule, total)) != OVL_OK) break;
+    if ((rc = sync_devices(ctx, rc, "ovl_seed_candidates")) != OVL_OK) return rc;
+    if (rule.timing) (void)hipSetDevice(d0->device);
+    for (int i = 0; i < 4; ++i)  // keys, sort, count + scan; the emit has its own start
+        d0->sd.last.ms[i] = d0->sd.timer.ms(i < 3 ? i : 4, i < 3 ? i + 1 : 5);
     for (Dev* d : ctx->devs) {
         d->cand_n = total;
         d->cand_seed = true;
@@ -257,7 +208,7 @@ OVL_API int ovl_seed_offsets_copy(ovl_ctx* ctx, int32_t* out_offset) {
     if (!out_offset) return fail(c, OVL_E_ARG, "NULL host pointer");
     DeviceGuard guard;
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(out_offset, c->cand_o.p, (size_t)c->cand_n * sizeof(int32_t), hipMemcpyDeviceToHost,
+    HIPCHK(c, hipMemcpyAsync(out_offset, c->sd.offs.p, (size_t)c->cand_n * sizeof(int32_t), hipMemcpyDeviceToHost,
                              c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return OVL_OK;
@@ -266,10 +217,11 @@ OVL_API int ovl_seed_offsets_copy(ovl_ctx* ctx, int32_t* out_offset) {
 OVL_API int ovl_last_seed_timing(const ovl_ctx* ctx, double* keys_ms, double* sort_ms, double* count_ms,
                                  double* emit_ms) {
     if (!ctx) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
-    if (keys_ms) *keys_ms = ctx->x_sd_ms[0];
-    if (sort_ms) *sort_ms = ctx->x_sd_ms[1];
-    if (count_ms) *count_ms = ctx->x_sd_ms[2];
-    if (emit_ms) *emit_ms = ctx->x_sd_ms[3];
+    const double* ms = ctx->devs[0]->sd.last.ms;
+    if (keys_ms) *keys_ms = ms[0];
+    if (sort_ms) *sort_ms = ms[1];
+    if (count_ms) *count_ms = ms[2];
+    if (emit_ms) *emit_ms = ms[3];
     return OVL_OK;
 }
 

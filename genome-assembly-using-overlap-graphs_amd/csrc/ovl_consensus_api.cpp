@@ -9,7 +9,7 @@
 
 namespace {
 
-constexpr int64_t kOpsBudget = int64_t(256) << 20;  // the walks of one chunk of reads (bytes of Dev::lb_ops)
+constexpr int64_t kOpsBudget = int64_t(256) << 20;  // the walks of one chunk of reads (bytes of Dev::lb.ops)
 
 template <typename C>
 int check_consensus(const C* c, const uint8_t* reads, const int64_t* r_off, int32_t n_reads, const uint8_t* contigs,
@@ -104,33 +104,30 @@ OVL_API int ovl_consensus(ovl_ctx* ctx, const uint8_t* reads, const int64_t* r_o
                           int32_t read_length, int32_t match, int32_t mismatch, int64_t indel, int32_t min_depth,
                           int32_t* counts, uint8_t* called, int64_t* n_changed, int64_t* n_other, int32_t* aln) {
     if (!ctx) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
-    quiet(ctx);
-    Dev* c = ctx->devs[0];
-    DeviceGuard guard;
-    const auto t_call = std::chrono::steady_clock::now();
+    StageCall call(ctx);
+    Dev* c = call.dev;
     int64_t total = 0;
     const int rc = check_consensus(c, reads, r_off, n_reads, contigs, c_off, n_contigs, place, read_length, match,
                                    min_depth, called, n_changed, n_other, &total);
     if (rc != OVL_OK) return rc;
     zero_aln(aln, n_reads);
     *n_changed = *n_other = 0;
-    ctx->x_cs_batch = ctx->x_cs_single = ctx->x_cs_ops = 0;
-    ctx->x_cs_launches = 0;
-    ctx->x_cs_ms[0] = ctx->x_cs_ms[1] = ctx->x_cs_ms[2] = 0.0;
-    ctx->t_kernel_ms = ctx->t_call_ms = 0.0;
+    call.begin();
+    c->cs.last = {};
+    ConsensusState::Last& last = c->cs.last;
     if (total == 0) return OVL_OK;  // no base to vote on, and every window is empty
     const uint8_t* ref = contigs + c_off[0];
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    HIPCHK(c, ensure(c->cs_ref, (size_t)total));
-    HIPCHK(c, ensure(c->cs_counts, sizeof(int32_t) * 6 * (size_t)total));
-    HIPCHK(c, ensure(c->cs_called, (size_t)total));
-    HIPCHK(c, ensure(c->cs_ctr, 32));
-    HIPCHK(c, hipMemcpyAsync(c->cs_ref.p, ref, (size_t)total, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemsetAsync(c->cs_counts.p, 0, sizeof(int32_t) * 6 * (size_t)total, s));
-    HIPCHK(c, hipMemsetAsync(c->cs_ctr.p, 0, 32, s));
-    if (ctx->timing) HIPCHK(c, ensure_events(c->cs_ev));
-    unsigned long long* d_ctr = as<unsigned long long>(c->cs_ctr);  // {n_other, n_changed, bad ops}, pileup's counter
+    HIPCHK(c, ensure(c->cs.ref, (size_t)total));
+    HIPCHK(c, ensure(c->cs.counts, sizeof(int32_t) * 6 * (size_t)total));
+    HIPCHK(c, ensure(c->cs.called, (size_t)total));
+    HIPCHK(c, ensure(c->cs.ctr, 32));
+    HIPCHK(c, hipMemcpyAsync(c->cs.ref.p, ref, (size_t)total, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemsetAsync(c->cs.counts.p, 0, sizeof(int32_t) * 6 * (size_t)total, s));
+    HIPCHK(c, hipMemsetAsync(c->cs.ctr.p, 0, 32, s));
+    HIPCHK(c, c->cs.timer.arm(ctx->timing));
+    unsigned long long* d_ctr = as<unsigned long long>(c->cs.ctr);  // {n_other, n_changed, bad ops}, pileup's counter
     uint32_t* d_take = reinterpret_cast<uint32_t*>(d_ctr + 3);
 
     int64_t host_other = 0;
@@ -165,44 +162,39 @@ OVL_API int ovl_consensus(ovl_ctx* ctx, const uint8_t* reads, const int64_t* r_o
         }
         if (!batch.empty()) {
             LocalBatchRun run;
-            if (ctx->timing) HIPCHK(c, hipEventRecord(c->cs_ev[0], s));
+            HIPCHK(c, c->cs.timer.mark(0, s));
             const int rl = local_batch_launch(ctx, c, reads, r_off, batch, nullptr, (int32_t)total,
-                                              as<uint8_t>(c->cs_ref), true, match, mismatch, (int32_t)indel, &run);
+                                              as<uint8_t>(c->cs.ref), true, match, mismatch, (int32_t)indel, &run);
             if (rl != OVL_OK) return rl;
-            if (ctx->timing) HIPCHK(c, hipEventRecord(c->cs_ev[1], s));
+            HIPCHK(c, c->cs.timer.mark(1, s));
             HIPCHK(c, hipMemsetAsync(d_take, 0, sizeof(uint32_t), s));
             OvlPileupArgs p{};
-            p.items = as<OvlLocalBatchItem>(c->lb_in);
-            p.q = as<uint8_t>(c->lb_in) + run.o_q;
-            p.out = as<OvlLocalBatchRecord>(c->lb_out);
-            p.ops = as<int8_t>(c->lb_ops);
+            p.items = as<OvlLocalBatchItem>(c->lb.in);
+            p.q = as<uint8_t>(c->lb.in) + run.o_q;
+            p.out = as<OvlLocalBatchRecord>(c->lb.out);
+            p.ops = as<int8_t>(c->lb.ops);
             p.n_items = run.nb;
             p.counter = d_take;
-            p.counts = as<int32_t>(c->cs_counts);
+            p.counts = as<int32_t>(c->cs.counts);
             p.ctr = d_ctr;
             const int32_t waves = (int32_t)std::min<int64_t>(run.nb, (int64_t)c->cu_count * 16);
             HIPCHK(c, ovl_launch_consensus_pileup(&p, waves, s));
-            if (ctx->timing) HIPCHK(c, hipEventRecord(c->cs_ev[2], s));
+            HIPCHK(c, c->cs.timer.mark(2, s));
             // the records come back (score and columns for aln, the op counts); the ops stay where they are
             res.resize((size_t)run.nb);
             unsigned long long lb_ctr[2] = {0, 0};
-            HIPCHK(c, hipMemcpyAsync(res.data(), c->lb_out.p, res.size() * sizeof(res[0]), hipMemcpyDeviceToHost, s));
-            HIPCHK(c, hipMemcpyAsync(lb_ctr, c->lb_ctr.p, sizeof(lb_ctr), hipMemcpyDeviceToHost, s));
+            HIPCHK(c, hipMemcpyAsync(res.data(), c->lb.out.p, res.size() * sizeof(res[0]), hipMemcpyDeviceToHost, s));
+            HIPCHK(c, hipMemcpyAsync(lb_ctr, c->lb.ctr.p, sizeof(lb_ctr), hipMemcpyDeviceToHost, s));
             HIPCHK(c, hipStreamSynchronize(s));
             if (lb_ctr[1] > (unsigned long long)run.nm_sum)
                 return fail(c, OVL_E_INTERNAL, "consensus: %llu ops for a capacity of %lld", lb_ctr[1],
                             (long long)run.nm_sum);
-            if (ctx->timing) {
-                float ms = 0.f;
-                HIPCHK(c, hipEventElapsedTime(&ms, c->cs_ev[0], c->cs_ev[1]));
-                ctx->x_cs_ms[0] += ms;
-                HIPCHK(c, hipEventElapsedTime(&ms, c->cs_ev[1], c->cs_ev[2]));
-                ctx->x_cs_ms[1] += ms;
-            }
+            last.ms[0] += c->cs.timer.ms(0, 1);
+            last.ms[1] += c->cs.timer.ms(1, 2);
             for (int32_t b = 0; b < run.nb; ++b) {
                 const int32_t r = batch[(size_t)b].k, f = place[r];
                 const OvlLocalBatchRecord& o = res[(size_t)b];
-                ctx->x_cs_ops += o.n_ops;
+                last.ops += o.n_ops;
                 if (aln && o.score > 0) {
                     const int32_t lo = batch[(size_t)b].lo - (int32_t)(c_off[f] - c_off[0]);  // in the contig
                     aln[3 * (int64_t)r] = o.score;
@@ -210,8 +202,8 @@ OVL_API int ovl_consensus(ovl_ctx* ctx, const uint8_t* reads, const int64_t* r_o
                     aln[3 * (int64_t)r + 2] = lo + o.end_j;
                 }
             }
-            ctx->x_cs_batch += run.nb;
-            ++ctx->x_cs_launches;
+            last.batch += run.nb;
+            ++last.launches;
         }
         // the reads the batch kernel does not take: one by one, their walks piled up by the host form's routine
         for (int32_t r : single) {
@@ -226,66 +218,62 @@ OVL_API int ovl_consensus(ovl_ctx* ctx, const uint8_t* reads, const int64_t* r_o
             if (sc <= 0) continue;
             host_other += pile_ops(ops.data(), n_ops, reads + r_off[r], ei, ej, (c_off[f] - c_off[0]) + w.lo,
                                    [&](int64_t k) { hits.push_back(k); });
-            ctx->x_cs_ops += n_ops;
+            last.ops += n_ops;
             if (aln) {
                 aln[3 * (int64_t)r] = sc;
                 aln[3 * (int64_t)r + 1] = w.lo + sj;
                 aln[3 * (int64_t)r + 2] = w.lo + ej;
             }
         }
-        ctx->x_cs_single += (int64_t)single.size();
+        last.single += (int64_t)single.size();
         if (!hits.empty()) {
             HIPCHK(c, hipSetDevice(c->device));
-            HIPCHK(c, ensure(c->cs_hits, sizeof(int64_t) * hits.size()));
-            HIPCHK(c, hipMemcpyAsync(c->cs_hits.p, hits.data(), sizeof(int64_t) * hits.size(), hipMemcpyHostToDevice,
+            HIPCHK(c, ensure(c->cs.hits, sizeof(int64_t) * hits.size()));
+            HIPCHK(c, hipMemcpyAsync(c->cs.hits.p, hits.data(), sizeof(int64_t) * hits.size(), hipMemcpyHostToDevice,
                                      s));
-            HIPCHK(c, ovl_launch_consensus_add(as<int64_t>(c->cs_hits), (int64_t)hits.size(),
-                                               as<int32_t>(c->cs_counts), s));
+            HIPCHK(c, ovl_launch_consensus_add(as<int64_t>(c->cs.hits), (int64_t)hits.size(),
+                                               as<int32_t>(c->cs.counts), s));
             HIPCHK(c, hipStreamSynchronize(s));  // `hits` is refilled by the next chunk
         }
         r0 = r1;
     }
 
     HIPCHK(c, hipSetDevice(c->device));
-    if (ctx->timing) HIPCHK(c, hipEventRecord(c->cs_ev[0], s));
-    HIPCHK(c, ovl_launch_consensus_vote(as<uint8_t>(c->cs_ref), as<int32_t>(c->cs_counts), total, min_depth,
-                                        as<uint8_t>(c->cs_called), d_ctr, s));
-    if (ctx->timing) HIPCHK(c, hipEventRecord(c->cs_ev[3], s));
+    HIPCHK(c, c->cs.timer.mark(0, s));
+    HIPCHK(c, ovl_launch_consensus_vote(as<uint8_t>(c->cs.ref), as<int32_t>(c->cs.counts), total, min_depth,
+                                        as<uint8_t>(c->cs.called), d_ctr, s));
+    HIPCHK(c, c->cs.timer.mark(3, s));
     unsigned long long ctr[3] = {0, 0, 0};
-    HIPCHK(c, hipMemcpyAsync(called, c->cs_called.p, (size_t)total, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(called, c->cs.called.p, (size_t)total, hipMemcpyDeviceToHost, s));
     if (counts)
-        HIPCHK(c, hipMemcpyAsync(counts, c->cs_counts.p, sizeof(int32_t) * 6 * (size_t)total, hipMemcpyDeviceToHost,
+        HIPCHK(c, hipMemcpyAsync(counts, c->cs.counts.p, sizeof(int32_t) * 6 * (size_t)total, hipMemcpyDeviceToHost,
                                  s));
-    HIPCHK(c, hipMemcpyAsync(ctr, c->cs_ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(ctr, c->cs.ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
-    if (ctx->timing) {
-        float ms = 0.f;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->cs_ev[0], c->cs_ev[3]));
-        ctx->x_cs_ms[2] = ms;
-    }
+    last.ms[2] = c->cs.timer.ms(0, 3);
     if (ctr[2])
         return fail(c, OVL_E_INTERNAL, "consensus: %llu ops of the walks fell outside their alignments", ctr[2]);
     *n_other = (int64_t)ctr[0] + host_other;
     *n_changed = (int64_t)ctr[1];
-    ctx->t_kernel_ms = ctx->x_cs_ms[0] + ctx->x_cs_ms[1] + ctx->x_cs_ms[2];
-    ctx->t_call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
-    return OVL_OK;
+    return call.done(last.ms[0] + last.ms[1] + last.ms[2]);
 }
 
 OVL_API int ovl_last_consensus(const ovl_ctx* ctx, int64_t* batch_reads, int64_t* single_reads, int64_t* ops,
                                int32_t* launches) {
     if (!ctx) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
-    if (batch_reads) *batch_reads = ctx->x_cs_batch;
-    if (single_reads) *single_reads = ctx->x_cs_single;
-    if (ops) *ops = ctx->x_cs_ops;
-    if (launches) *launches = ctx->x_cs_launches;
+    const ConsensusState::Last& l = ctx->devs[0]->cs.last;
+    if (batch_reads) *batch_reads = l.batch;
+    if (single_reads) *single_reads = l.single;
+    if (ops) *ops = l.ops;
+    if (launches) *launches = l.launches;
     return OVL_OK;
 }
 
 OVL_API int ovl_last_consensus_timing(const ovl_ctx* ctx, double* align_ms, double* pileup_ms, double* vote_ms) {
     if (!ctx) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
-    if (align_ms) *align_ms = ctx->x_cs_ms[0];
-    if (pileup_ms) *pileup_ms = ctx->x_cs_ms[1];
-    if (vote_ms) *vote_ms = ctx->x_cs_ms[2];
+    const double* ms = ctx->devs[0]->cs.last.ms;
+    if (align_ms) *align_ms = ms[0];
+    if (pileup_ms) *pileup_ms = ms[1];
+    if (vote_ms) *vote_ms = ms[2];
     return OVL_OK;
 }

@@ -10,7 +10,7 @@
 
 namespace {
 
-constexpr int64_t kSlabBudget = int64_t(256) << 20;  // a chunk's code words (bytes of Dev::pl_slab)
+constexpr int64_t kSlabBudget = int64_t(256) << 20;  // a chunk's code words (bytes of Dev::pl.slab)
 
 // The window of a placement (rule 1), in int64: no vote when it is empty
 struct PlacedWindow {
@@ -199,10 +199,8 @@ OVL_API int ovl_consensus_placed(ovl_ctx* ctx, const uint8_t* reads, const int64
                                  int64_t* n_changed, int64_t* n_other, int64_t* total_changed, int32_t* rounds_done,
                                  int32_t* aln) {
     if (!ctx) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
-    quiet(ctx);
-    Dev* c = ctx->devs[0];
-    DeviceGuard guard;
-    const auto t_call = std::chrono::steady_clock::now();
+    StageCall call(ctx);
+    Dev* c = call.dev;
     int64_t total = 0;
     const int rc = check_placed(c, true, reads, r_off, n_reads, weight, contigs, c_off, n_contigs, contig, offset,
                                 slack, match, mismatch, indel, min_vote_score, min_depth, rounds, called, n_changed,
@@ -211,11 +209,10 @@ OVL_API int ovl_consensus_placed(ovl_ctx* ctx, const uint8_t* reads, const int64
     if (aln) std::fill(aln, aln + (int64_t)n_reads * 3, 0);
     *n_changed = *n_other = *total_changed = 0;
     *rounds_done = 1;
-    ctx->x_pl_voted = ctx->x_pl_windowless = ctx->x_pl_ops = 0;
-    ctx->x_pl_launches = 0;
-    ctx->x_pl_rounds = 1;
-    ctx->x_pl_ms[0] = ctx->x_pl_ms[1] = 0.0;
-    ctx->t_kernel_ms = ctx->t_call_ms = 0.0;
+    call.begin();
+    c->pl.last = {};
+    PlacedState::Last& last = c->pl.last;
+    last.rounds = 1;
     if (total == 0) return OVL_OK;  // no base to vote on, and every window is empty
 
     // the reads that have a window: one item each, in read order
@@ -227,7 +224,7 @@ OVL_API int ovl_consensus_placed(ovl_ctx* ctx, const uint8_t* reads, const int64
             if (f < 0 || L == 0 || wt == 0) continue;
             const PlacedWindow pw = placed_window(L, c_off[f + 1] - c_off[f], offset[r], slack);
             if (pw.w == 0) {
-                ++ctx->x_pl_windowless;
+                ++last.windowless;
                 continue;
             }
             items.push_back({r_off[r] - r_off[0], (int32_t)L, (int32_t)pw.w, (int32_t)pw.d,
@@ -261,26 +258,26 @@ OVL_API int ovl_consensus_placed(ovl_ctx* ctx, const uint8_t* reads, const int64
     const size_t o_q = items.size() * sizeof(OvlPlacedItem);
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    HIPCHK(c, ensure(c->cs_ref, (size_t)total));
-    HIPCHK(c, ensure(c->cs_counts, sizeof(int32_t) * 6 * (size_t)total));
-    HIPCHK(c, ensure(c->cs_called, (size_t)total));
-    HIPCHK(c, ensure(c->cs_ctr, 64));
-    HIPCHK(c, ensure(c->pl_in, o_q + (size_t)r_bytes));
-    HIPCHK(c, ensure(c->pl_slab, slab_words * 8));
-    HIPCHK(c, ensure(c->pl_aln, sizeof(int32_t) * 3 * (size_t)std::max(n_reads, 1)));
-    if (ctx->timing) HIPCHK(c, ensure_events(c->pl_ev));
-    HIPCHK(c, hipMemcpyAsync(c->cs_ref.p, first, (size_t)total, hipMemcpyHostToDevice, s));
+    HIPCHK(c, ensure(c->cs.ref, (size_t)total));
+    HIPCHK(c, ensure(c->cs.counts, sizeof(int32_t) * 6 * (size_t)total));
+    HIPCHK(c, ensure(c->cs.called, (size_t)total));
+    HIPCHK(c, ensure(c->cs.ctr, 64));
+    HIPCHK(c, ensure(c->pl.in, o_q + (size_t)r_bytes));
+    HIPCHK(c, ensure(c->pl.slab, slab_words * 8));
+    HIPCHK(c, ensure(c->pl.aln, sizeof(int32_t) * 3 * (size_t)std::max(n_reads, 1)));
+    HIPCHK(c, c->pl.timer.arm(ctx->timing));
+    HIPCHK(c, hipMemcpyAsync(c->cs.ref.p, first, (size_t)total, hipMemcpyHostToDevice, s));
     if (!items.empty()) {
-        HIPCHK(c, hipMemcpyAsync(c->pl_in.p, items.data(), o_q, hipMemcpyHostToDevice, s));
-        HIPCHK(c, hipMemcpyAsync(as<char>(c->pl_in) + o_q, reads + r_off[0], (size_t)r_bytes, hipMemcpyHostToDevice,
+        HIPCHK(c, hipMemcpyAsync(c->pl.in.p, items.data(), o_q, hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipMemcpyAsync(as<char>(c->pl.in) + o_q, reads + r_off[0], (size_t)r_bytes, hipMemcpyHostToDevice,
                                  s));
     }
-    unsigned long long* d_ctr = as<unsigned long long>(c->cs_ctr);  // {n_other, n_changed, -, voted, ops}
+    unsigned long long* d_ctr = as<unsigned long long>(c->cs.ctr);  // {n_other, n_changed, -, voted, ops}
 
     OvlPlacedArgs p{};
-    p.q = as<uint8_t>(c->pl_in) + o_q;
-    p.ref = as<uint8_t>(c->cs_ref);
-    p.slab = as<unsigned long long>(c->pl_slab);
+    p.q = as<uint8_t>(c->pl.in) + o_q;
+    p.ref = as<uint8_t>(c->cs.ref);
+    p.slab = as<unsigned long long>(c->pl.slab);
     p.slack = slack;
     // scores at or below -2^30 are never taken: the cells stay below 2^30 (check_placed)
     const int64_t floor30 = -(int64_t(1) << 30);
@@ -288,76 +285,70 @@ OVL_API int ovl_consensus_placed(ovl_ctx* ctx, const uint8_t* reads, const int64
     p.mismatch = (int32_t)std::max<int64_t>(mismatch, floor30);
     p.indel = (int32_t)std::max<int64_t>(clamp_score(indel), floor30);
     p.min_vote_score = min_vote_score;
-    p.counts = as<int32_t>(c->cs_counts);
-    p.aln = as<int32_t>(c->pl_aln);
+    p.counts = as<int32_t>(c->cs.counts);
+    p.aln = as<int32_t>(c->pl.aln);
     p.ctr = d_ctr;
 
     unsigned long long ctr[5] = {0, 0, 0, 0, 0};
     int32_t done = 0;
     for (;;) {
-        HIPCHK(c, hipMemsetAsync(c->cs_counts.p, 0, sizeof(int32_t) * 6 * (size_t)total, s));
-        HIPCHK(c, hipMemsetAsync(c->cs_ctr.p, 0, 64, s));
-        HIPCHK(c, hipMemsetAsync(c->pl_aln.p, 0, sizeof(int32_t) * 3 * (size_t)std::max(n_reads, 1), s));
-        if (ctx->timing) HIPCHK(c, hipEventRecord(c->pl_ev[0], s));
+        HIPCHK(c, hipMemsetAsync(c->cs.counts.p, 0, sizeof(int32_t) * 6 * (size_t)total, s));
+        HIPCHK(c, hipMemsetAsync(c->cs.ctr.p, 0, 64, s));
+        HIPCHK(c, hipMemsetAsync(c->pl.aln.p, 0, sizeof(int32_t) * 3 * (size_t)std::max(n_reads, 1), s));
+        HIPCHK(c, c->pl.timer.mark(0, s));
         for (size_t k = 0; k + 1 < cuts.size(); ++k) {
-            p.items = as<OvlPlacedItem>(c->pl_in) + cuts[k];
+            p.items = as<OvlPlacedItem>(c->pl.in) + cuts[k];
             p.n_items = cuts[k + 1] - cuts[k];
             p.pitch = (p.n_items + 63) / 64 * 64;
             HIPCHK(c, ovl_launch_consensus_placed(&p, s));
-            ++ctx->x_pl_launches;
+            ++last.launches;
         }
-        if (ctx->timing) HIPCHK(c, hipEventRecord(c->pl_ev[1], s));
-        HIPCHK(c, ovl_launch_consensus_vote(as<uint8_t>(c->cs_ref), as<int32_t>(c->cs_counts), total, min_depth,
-                                            as<uint8_t>(c->cs_called), d_ctr, s));
-        if (ctx->timing) HIPCHK(c, hipEventRecord(c->pl_ev[2], s));
+        HIPCHK(c, c->pl.timer.mark(1, s));
+        HIPCHK(c, ovl_launch_consensus_vote(as<uint8_t>(c->cs.ref), as<int32_t>(c->cs.counts), total, min_depth,
+                                            as<uint8_t>(c->cs.called), d_ctr, s));
+        HIPCHK(c, c->pl.timer.mark(2, s));
         // only the counters cross the link between rounds
-        HIPCHK(c, hipMemcpyAsync(ctr, c->cs_ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(ctr, c->cs.ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipStreamSynchronize(s));
-        if (ctx->timing) {
-            float ms = 0.f;
-            HIPCHK(c, hipEventElapsedTime(&ms, c->pl_ev[0], c->pl_ev[1]));
-            ctx->x_pl_ms[0] += ms;
-            HIPCHK(c, hipEventElapsedTime(&ms, c->pl_ev[1], c->pl_ev[2]));
-            ctx->x_pl_ms[1] += ms;
-        }
+        last.ms[0] += c->pl.timer.ms(0, 1);
+        last.ms[1] += c->pl.timer.ms(1, 2);
         ++done;
         if (ctr[1] == 0 || done >= rounds) break;
         // the called bases are the next round's contigs
-        HIPCHK(c, hipMemcpyAsync(c->cs_ref.p, c->cs_called.p, (size_t)total, hipMemcpyDeviceToDevice, s));
+        HIPCHK(c, hipMemcpyAsync(c->cs.ref.p, c->cs.called.p, (size_t)total, hipMemcpyDeviceToDevice, s));
     }
-    HIPCHK(c, hipMemcpyAsync(called, c->cs_called.p, (size_t)total, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(called, c->cs.called.p, (size_t)total, hipMemcpyDeviceToHost, s));
     if (counts)
-        HIPCHK(c, hipMemcpyAsync(counts, c->cs_counts.p, sizeof(int32_t) * 6 * (size_t)total, hipMemcpyDeviceToHost,
+        HIPCHK(c, hipMemcpyAsync(counts, c->cs.counts.p, sizeof(int32_t) * 6 * (size_t)total, hipMemcpyDeviceToHost,
                                  s));
     if (aln && n_reads > 0)
-        HIPCHK(c, hipMemcpyAsync(aln, c->pl_aln.p, sizeof(int32_t) * 3 * (size_t)n_reads, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(aln, c->pl.aln.p, sizeof(int32_t) * 3 * (size_t)n_reads, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     *n_other = (int64_t)ctr[0];
     *n_changed = (int64_t)ctr[1];
     *rounds_done = done;
     *total_changed = count_differences(called, first, total);
-    ctx->x_pl_voted = (int64_t)ctr[3];
-    ctx->x_pl_ops = (int64_t)ctr[4];
-    ctx->x_pl_rounds = done;
-    ctx->t_kernel_ms = ctx->x_pl_ms[0] + ctx->x_pl_ms[1];
-    ctx->t_call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
-    return OVL_OK;
+    last.voted = (int64_t)ctr[3];
+    last.ops = (int64_t)ctr[4];
+    last.rounds = done;
+    return call.done(last.ms[0] + last.ms[1]);
 }
 
 OVL_API int ovl_last_consensus_placed(const ovl_ctx* ctx, int64_t* voted_reads, int64_t* windowless_reads,
                                       int64_t* ops, int32_t* launches, int32_t* rounds) {
     if (!ctx) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
-    if (voted_reads) *voted_reads = ctx->x_pl_voted;
-    if (windowless_reads) *windowless_reads = ctx->x_pl_windowless;
-    if (ops) *ops = ctx->x_pl_ops;
-    if (launches) *launches = ctx->x_pl_launches;
-    if (rounds) *rounds = ctx->x_pl_rounds;
+    const PlacedState::Last& l = ctx->devs[0]->pl.last;
+    if (voted_reads) *voted_reads = l.voted;
+    if (windowless_reads) *windowless_reads = l.windowless;
+    if (ops) *ops = l.ops;
+    if (launches) *launches = l.launches;
+    if (rounds) *rounds = l.rounds;
     return OVL_OK;
 }
 
 OVL_API int ovl_last_consensus_placed_timing(const ovl_ctx* ctx, double* band_ms, double* vote_ms) {
     if (!ctx) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
-    if (band_ms) *band_ms = ctx->x_pl_ms[0];
-    if (vote_ms) *vote_ms = ctx->x_pl_ms[1];
+    if (band_ms) *band_ms = ctx->devs[0]->pl.last.ms[0];
+    if (vote_ms) *vote_ms = ctx->devs[0]->pl.last.ms[1];
     return OVL_OK;
 }

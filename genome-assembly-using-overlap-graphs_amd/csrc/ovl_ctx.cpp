@@ -134,36 +134,7 @@ void destroy_dev(Dev* d) {
     (void)hipSetDevice(d->device);
     for (hipStream_t s : {d->stream, d->s_in})
         if (s) (void)hipStreamSynchronize(s);
-    for (DevBuf* b : {&d->codes, &d->off, &d->len, &d->sfx, &d->pfx, &d->lut, &d->full, &d->raw, &d->rd, &d->a, &d->b,
-                      &d->score, &d->end, &d->tb, &d->err_flag, &d->k_pre, &d->k_suf, &d->k_sorted, &d->k_iota,
-                      &d->k_order, &d->k_lo, &d->k_hi, &d->k_cnt, &d->k_offs, &d->k_temp, &d->cand_a, &d->cand_b,
-                      &d->sh_cum, &d->sh_temp, &d->sh_cuts, &d->l_q, &d->l_r, &d->l_row, &d->l_tb, &d->l_best,
-                      &d->lane_col, &d->seed_s, &d->seed_e, &d->tile_flags, &d->heavy_ids, &d->cp_hbm, &d->lb_in,
-                      &d->lb_ctr, &d->lb_rows, &d->lb_slabs, &d->lb_wops, &d->lb_out, &d->lb_ops, &d->tr_off,
-                      &d->tr_edge, &d->tr_order, &d->tr_ctr, &d->tr_out, &d->rc_off, &d->rc_head, &d->rc_order,
-                      &d->rc_matrix, &d->rc_pivot, &d->rc_out, &d->rb_in, &d->rb_tile, &d->rb_res, &d->rb_bits, &d->cs_ref,
-                      &d->cs_counts, &d->cs_called, &d->cs_ctr, &d->cs_hits, &d->cand_o, &d->sd_glo, &d->sd_gn, &d->ly_in,
-                      &d->ly_work, &d->ly_bases, &d->ly_temp, &d->sp_in, &d->sp_work, &d->pl_in, &d->pl_slab, &d->pl_aln})
-        release(*b);
     if (d->l_tb_host) (void)hipHostFree(d->l_tb_host);
-    for (hipEvent_t e : d->lb_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : d->tr_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : d->rc_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : d->rb_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : d->cs_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : d->pl_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : d->sd_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : d->ly_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : d->sp_ev)
-        if (e) (void)hipEventDestroy(e);
     free_staging(d->st_in);
     free_staging(d->st_out);
     if (d->h_flag) (void)hipHostFree(d->h_flag);
@@ -180,7 +151,7 @@ void destroy_dev(Dev* d) {
     if (d->ev_last) (void)hipEventDestroy(d->ev_last);
     for (hipStream_t s : {d->stream, d->s_in})
         if (s) (void)hipStreamDestroy(s);
-    delete d;
+    delete d;  // every DevBuf and every stage's timer goes here, with the device still current
 }
 
 hipError_t init_dev(Dev* d) {

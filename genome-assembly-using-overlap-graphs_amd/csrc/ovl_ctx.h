@@ -5,7 +5,8 @@
 // depth), ovl_consensus_api.cpp (read pileup and consensus), ovl_consensus_placed_api.cpp (consensus at the layout's
 // placement), ovl_layout_api.cpp (best-successor layout),
 // ovl_spectrum_api.cpp (k-mer spectrum read correction) and the graph stages ovl_reduce_api.cpp /
-// ovl_reach_api.cpp.  What the local-alignment stages share on the host is in ovl_local_host.h.
+// ovl_reach_api.cpp.  What the local-alignment stages share on the host is in ovl_local_host.h; what every stage's
+// call, timing and device state share is in ovl_stage.h (included below, ahead of Dev).
 //
 // A context (ovl_ctx) drives one or more HIP devices from one host thread.  Each
 // device (Dev) owns: a compute stream and two copy streams (H2D, D2H), its copy
@@ -76,10 +77,17 @@ constexpr int kSlots = 3;              // pipeline depth: staging slots / events
 // coarse-grained kind.)
 constexpr unsigned kHostShared = hipHostMallocPortable | hipHostMallocCoherent;
 
+// Device memory that goes with its owner: freed when the Dev (or whatever holds it) is deleted, unless it is a view.
 struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
     bool view = false;  // a part of another buffer (set_view): not freed, not grown
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() {
+        if (p && !view) (void)hipFree(p);
+    }
 };
 
 extern thread_local std::string g_err;  // ovl_last_error(NULL): this thread's last error (ovl_ctx.cpp)
@@ -189,6 +197,7 @@ constexpr int64_t kCompactMin = int64_t(1) << 16;
 constexpr size_t kExpandPart = size_t(1) << 14;
 
 struct ovl_ctx;
+struct Dev;
 
 // ovl_last_score_form: the form the first scoring launch of the last scoring call took (launch_score_chunk records
 // it while `open`, which the call's entry sets)
@@ -198,120 +207,6 @@ struct ScoreForm {
     int32_t lane = 0, prof = 0, sfx = 0, ho = 0, h2 = 0;  // the lane-per-pair full DP and its arguments
     int32_t band_form = -1, split = 0;                    // the band knob's form (-1: none) and two lanes per pair
     int32_t rs_log2 = 0;                                  // the ungapped launch's rs_log2 (ungapped_rs_log2)
-};
-
-// Per-device state.
-struct Dev {
-    ovl_ctx* owner = nullptr;
-    int32_t device = 0;
-    hipStream_t stream = nullptr;  // kernels
-    hipStream_t s_in = nullptr;    // host-array calls: the pair list's copies and decodes, beside the kernels
-    int32_t cu_count = 256;
-    Knobs k;
-    ScoreForm form;
-    // resident reads
-    int32_t n_reads = -1;
-    int32_t lmax = 0;
-    int32_t planes = 2;
-    int32_t wmax = 0;  // 0: no bit-plane layout (reads longer than kFastMaxLen)
-    int32_t srow = 0;  // sfx row stride (words)
-    int32_t trow = 0;  // pfx row stride (words)
-    DevBuf codes, off, len, sfx, pfx, lut, full;  // full: bit r set iff len[r] == lmax
-    DevBuf raw;                                   // the uploaded read bytes (raw or 2-bit packed)
-    DevBuf rd;  // ovl_set_reads' upload block, the stage's layout; off, len, full, lut and raw are views into it
-    // scratch
-    DevBuf a, b, score, end, tb, err_flag;
-    DevBuf lane_col;      // lane-per-pair DP: per-wavefront strip hand-off columns
-    DevBuf seed_s, seed_e;  // band knob: the ungapped seed (score, j*) of each pair
-    hipEvent_t scratch_evt = nullptr;     // last launch that used lane_col / seed_* ...
-    hipEvent_t ev_last = nullptr;         // packed calls into pinned arrays: after the last (direct) chunk
-    double pack_pct = -1.0;               // live direct share of packed calls into pinned arrays (pack_share)
-    double pack_pct_h = -1.0;             // the same for calls with a compact host pair list (the host also
-                                          // encodes the list, so its balance point differs)
-    hipStream_t scratch_stream = nullptr; // ... and its stream (launches on other streams wait for it)
-    bool scratch_used = false;
-    int64_t codes_bytes = 0;
-    // device candidate enumeration (ovl_candidates): per-read keys / groups and the pair list
-    DevBuf k_pre, k_suf, k_sorted, k_iota, k_order, k_lo, k_hi, k_cnt, k_offs, k_temp, cand_a, cand_b;
-    int64_t cand_n = -1;  // -1: no candidate list for the resident reads
-    // seed candidates (ovl_seed_candidates): the offset of each pair of the list, every offset's group (count pass ->
-    // emit pass), and whether the resident list came from that rule
-    DevBuf cand_o, sd_glo, sd_gn;
-    bool cand_seed = false;
-    hipEvent_t sd_ev[6] = {};  // timing on: before the keys, after them, the sort, the count + scan; around the emit
-    // heavy tiles of the candidate list (tiles holding side pairs, scheduled first: uniform_kernel), built on
-    // the first throughput-mode launch over the list (ensure_heavy)
-    DevBuf tile_flags, heavy_ids;
-    std::vector<int32_t> h_heavy;
-    int64_t heavy_for = -1;  // cand_n the heavy tiles were built for (-1: none)
-    int64_t cand_tail[2] = {0, 0};
-    DevBuf sh_cum, sh_temp, sh_cuts;  // shard bounds (ovl_candidates_shards)
-    // local alignment (ovl_local_align): query / reference bytes, carried rows, progress, traceback
-    DevBuf l_q, l_r, l_row, l_tb, l_best;
-    uint32_t l_epoch = 0;  // tags this launch's row hand-off words (l_row is zeroed when allocated)
-    // pinned host copy of the part of the traceback table the walk can reach (grown on demand)
-    int8_t* l_tb_host = nullptr;
-    size_t l_tb_host_bytes = 0;
-    // batched local alignment (ovl_local_align_batch): the upload block (items, query bytes, reference), the two
-    // counters, per-wavefront rows / traceback slabs / op scratch, and the results (a record per query, packed ops)
-    DevBuf lb_in, lb_ctr, lb_rows, lb_slabs, lb_wops, lb_out, lb_ops;
-    hipEvent_t lb_ev[2] = {};  // timing on: around the batch kernel
-    // transitive reduction (ovl_reduce_api.cpp): the CSR, the node order, the counter and the mask
-    DevBuf tr_off, tr_edge, tr_order, tr_ctr, tr_out;
-    hipEvent_t tr_ev[2] = {};  // timing on: around the reduction kernel
-    // reachability reduction (ovl_reach_api.cpp): the CSR, the node order, the bit matrix, the pivot rows, the mask
-    DevBuf rc_off, rc_head, rc_order, rc_matrix, rc_pivot, rc_out;
-    hipEvent_t rc_ev[2] = {};  // timing on: around all of a call's launches
-    // read depth (ovl_depth_api.cpp): the upload block (padded reads, lengths, contigs, their offsets and lengths),
-    // a chunk's score / cell tile, the per-read results and the tie bits
-    DevBuf rb_in, rb_tile, rb_res, rb_bits;
-    hipEvent_t rb_ev[2] = {};  // timing on: around the score pass and its folds
-    // consensus (ovl_consensus_api.cpp): the contigs' bytes, the vote counts (6 int32 per base), the called bytes,
-    // the counters {n_other, n_changed, bad ops}, and the flat count indices of the single-pair reads' votes
-    DevBuf cs_ref, cs_counts, cs_called, cs_ctr, cs_hits;
-    hipEvent_t cs_ev[4] = {};  // timing on: a chunk's start, after its alignment launch, after its pileup; the vote
-    // placed consensus (ovl_consensus_placed_api.cpp; it shares cs_ref, cs_counts, cs_called and cs_ctr): the upload
-    // block (items, the reads' bytes), a chunk's code words ([row][lane]) and three int32 per read
-    DevBuf pl_in, pl_slab, pl_aln;
-    hipEvent_t pl_ev[3] = {};  // timing on: a round's start, after its band launches, after its vote
-    // layout (ovl_layout_api.cpp): the call's inputs (ovl_layout: lengths, offsets, bytes and the four columns;
-    // ovl_layout_candidates: the score and end columns and the code table), the per-read block (WorkPlan), the
-    // contigs' bytes and the scan's scratch
-    DevBuf ly_in, ly_work, ly_bases, ly_temp;
-    hipEvent_t ly_ev[5] = {};  // timing on: before and after the scoring launches, the link kernel, the forest, the spelling
-    // read correction (ovl_spectrum_api.cpp): the call's upload (offsets, window offsets, bytes) and its tables
-    // (WorkPlan: keys, sorted keys, head flags and their scan, run starts, counts, histogram, counters, outputs)
-    DevBuf sp_in, sp_work;
-    hipEvent_t sp_ev[6] = {};  // timing on: before the keys, after them, the sort, the count pass; around the correction
-    // host-array pipeline: events per slot and pinned staging (slots x cap pairs x {a, b} / {score, end})
-    hipEvent_t ev_k[kSlots] = {};
-    int32_t* st_in = nullptr;
-    int32_t* st_out = nullptr;
-    int32_t* st_in_dev = nullptr;   // device addresses of the staging rings (kernels read / store them)
-    int32_t* st_out_dev = nullptr;
-    int64_t st_cap = 0;
-    uint32_t* h_flag = nullptr;      // pinned error flag of host-array calls (the kernels store into it)
-    uint32_t* h_flag_dev = nullptr;  // its device address
-    uint32_t* cur_flag = nullptr;    // the flag the next launches write: err_flag (device calls) or h_flag_dev
-    int32_t out_mode = 0;            // result sink of the next ungapped launches (OvlUngappedArgs::host_out):
-                                     // 0 HBM, 1 host-mapped int32 arrays, 2 host-mapped packed uint16
-    std::vector<hipEvent_t> t_ev;  // timing: kernel start/end per chunk (recorded on the stream around the launch)
-    std::vector<hipEvent_t> k_ev;  // timing: the same recorded by an ungapped launch itself (kernel start / end)
-    hipEvent_t kev_start = nullptr, kev_stop = nullptr;  // the next ungapped launch records these (then cleared)
-    // compact host pair lists (encode_chunk): pinned encoding buffer (8 bytes per pair + slack), its device
-    // address, a decode event per chunk, and the encoded bytes of the last call
-    char* cp_host = nullptr;
-    char* cp_dev = nullptr;
-    size_t cp_bytes = 0;
-    DevBuf cp_hbm;  // the in-place encoding's chunks copied into HBM (same layout as cp_host)
-    std::vector<hipEvent_t> dec_ev;
-    int64_t cp_link = 0;
-    // the next ungapped launch reads its pair list in the host encoding (OvlUngappedArgs::ix_*), or null
-    const uint16_t* ix_b16 = nullptr;
-    const uint8_t* ix_d8 = nullptr;
-    const int32_t* ix_base = nullptr;
-    ResidentGrid res;  // the resident scoring grid (ovl_resident.h), launched by the first call that uses it
-    std::unique_ptr<DevWorker> worker;  // multi-device contexts: this device's host thread (run_pipeline)
 };
 
 // The host side of a read-set upload in one pinned block (grown on demand, kept by the context): offsets,
@@ -362,23 +257,6 @@ struct ovl_ctx {
     int64_t x_link_bytes = 0, x_packed_pairs = 0;  // ovl_last_transfer
     int64_t x_res_bytes = 0, x_rec_pairs = 0, x_esc = 0;  // ovl_last_results
     int64_t x_ix_pairs = 0, x_dec_pairs = 0;       // ovl_last_pair_list
-    int32_t x_lb_batched = 0, x_lb_single = 0, x_lb_waves = 0;  // ovl_last_local_batch
-    int32_t x_tr_window = 0, x_tr_passes = 0;                   // ovl_last_transitive
-    int64_t x_tr_steps = 0;
-    int32_t x_rc_words = 0, x_rc_blocks = 0, x_rc_window = 0;   // ovl_last_reach
-    int64_t x_rb_lane = 0, x_rb_fallback = 0;                   // ovl_last_read_best
-    int32_t x_rb_launches = 0;
-    int64_t x_cs_batch = 0, x_cs_single = 0, x_cs_ops = 0;      // ovl_last_consensus
-    int32_t x_cs_launches = 0;
-    double x_cs_ms[3] = {0.0, 0.0, 0.0};                        // ovl_last_consensus_timing
-    int64_t x_pl_voted = 0, x_pl_windowless = 0, x_pl_ops = 0;  // ovl_last_consensus_placed
-    int32_t x_pl_launches = 0, x_pl_rounds = 0;
-    double x_pl_ms[2] = {0.0, 0.0};                             // ovl_last_consensus_placed_timing
-    double x_sd_ms[4] = {0.0, 0.0, 0.0, 0.0};                   // ovl_last_seed_timing
-    int64_t x_ly_links = 0, x_ly_cycles = 0, x_ly_on_path = 0;  // ovl_last_layout
-    int32_t x_ly_levels = 0;
-    double x_ly_ms[4] = {0.0, 0.0, 0.0, 0.0};                   // ovl_last_layout_timing
-    double x_sp_ms[4] = {0.0, 0.0, 0.0, 0.0};                   // ovl_last_correct_timing
 };
 
 int fail(const ovl_ctx* c, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
@@ -434,15 +312,98 @@ struct DeviceGuard {
     }
 };
 
-// timing on: a stage's events (Dev::lb_ev and the like), created by the first call that records them
-template <size_t N>
-hipError_t ensure_events(hipEvent_t (&ev)[N]) {
-    for (hipEvent_t& e : ev) {
-        const hipError_t r = e ? hipSuccess : hipEventCreate(&e);
-        if (r != hipSuccess) return r;
-    }
-    return hipSuccess;
-}
+void quiet(ovl_ctx* c);  // ovl_ctx.cpp
+
+#include "ovl_stage.h"
+
+// Per-device state.
+struct Dev {
+    ovl_ctx* owner = nullptr;
+    int32_t device = 0;
+    hipStream_t stream = nullptr;  // kernels
+    hipStream_t s_in = nullptr;    // host-array calls: the pair list's copies and decodes, beside the kernels
+    int32_t cu_count = 256;
+    Knobs k;
+    ScoreForm form;
+    // resident reads
+    int32_t n_reads = -1;
+    int32_t lmax = 0;
+    int32_t planes = 2;
+    int32_t wmax = 0;  // 0: no bit-plane layout (reads longer than kFastMaxLen)
+    int32_t srow = 0;  // sfx row stride (words)
+    int32_t trow = 0;  // pfx row stride (words)
+    DevBuf codes, off, len, sfx, pfx, lut, full;  // full: bit r set iff len[r] == lmax
+    DevBuf raw;                                   // the uploaded read bytes (raw or 2-bit packed)
+    DevBuf rd;  // ovl_set_reads' upload block, the stage's layout; off, len, full, lut and raw are views into it
+    // scratch
+    DevBuf a, b, score, end, tb, err_flag;
+    DevBuf lane_col;      // lane-per-pair DP: per-wavefront strip hand-off columns
+    DevBuf seed_s, seed_e;  // band knob: the ungapped seed (score, j*) of each pair
+    hipEvent_t scratch_evt = nullptr;     // last launch that used lane_col / seed_* ...
+    hipEvent_t ev_last = nullptr;         // packed calls into pinned arrays: after the last (direct) chunk
+    double pack_pct = -1.0;               // live direct share of packed calls into pinned arrays (pack_share)
+    double pack_pct_h = -1.0;             // the same for calls with a compact host pair list (the host also
+                                          // encodes the list, so its balance point differs)
+    hipStream_t scratch_stream = nullptr; // ... and its stream (launches on other streams wait for it)
+    bool scratch_used = false;
+    int64_t codes_bytes = 0;
+    // device candidate enumeration (ovl_candidates): per-read keys / groups and the pair list
+    DevBuf k_pre, k_suf, k_sorted, k_iota, k_order, k_lo, k_hi, k_cnt, k_offs, k_temp, cand_a, cand_b;
+    int64_t cand_n = -1;  // -1: no candidate list for the resident reads
+    bool cand_seed = false;  // the resident list came from ovl_seed_candidates (its offsets: sd.offs)
+    // heavy tiles of the candidate list (tiles holding side pairs, scheduled first: uniform_kernel), built on
+    // the first throughput-mode launch over the list (ensure_heavy)
+    DevBuf tile_flags, heavy_ids;
+    std::vector<int32_t> h_heavy;
+    int64_t heavy_for = -1;  // cand_n the heavy tiles were built for (-1: none)
+    int64_t cand_tail[2] = {0, 0};
+    DevBuf sh_cum, sh_temp, sh_cuts;  // shard bounds (ovl_candidates_shards)
+    // local alignment (ovl_local_align): query / reference bytes, carried rows, progress, traceback
+    DevBuf l_q, l_r, l_row, l_tb, l_best;
+    uint32_t l_epoch = 0;  // tags this launch's row hand-off words (l_row is zeroed when allocated)
+    // pinned host copy of the part of the traceback table the walk can reach (grown on demand)
+    int8_t* l_tb_host = nullptr;
+    size_t l_tb_host_bytes = 0;
+    // the stages, each with its buffers, its timer and what its last call reports (ovl_stage.h)
+    SeedState sd;
+    LocalBatchState lb;
+    TransitiveState tr;
+    ReachState rc;
+    ReadBestState rb;
+    ConsensusState cs;
+    PlacedState pl;
+    LayoutState ly;
+    SpectrumState sp;
+    // host-array pipeline: events per slot and pinned staging (slots x cap pairs x {a, b} / {score, end})
+    hipEvent_t ev_k[kSlots] = {};
+    int32_t* st_in = nullptr;
+    int32_t* st_out = nullptr;
+    int32_t* st_in_dev = nullptr;   // device addresses of the staging rings (kernels read / store them)
+    int32_t* st_out_dev = nullptr;
+    int64_t st_cap = 0;
+    uint32_t* h_flag = nullptr;      // pinned error flag of host-array calls (the kernels store into it)
+    uint32_t* h_flag_dev = nullptr;  // its device address
+    uint32_t* cur_flag = nullptr;    // the flag the next launches write: err_flag (device calls) or h_flag_dev
+    int32_t out_mode = 0;            // result sink of the next ungapped launches (OvlUngappedArgs::host_out):
+                                     // 0 HBM, 1 host-mapped int32 arrays, 2 host-mapped packed uint16
+    std::vector<hipEvent_t> t_ev;  // timing: kernel start/end per chunk (recorded on the stream around the launch)
+    std::vector<hipEvent_t> k_ev;  // timing: the same recorded by an ungapped launch itself (kernel start / end)
+    hipEvent_t kev_start = nullptr, kev_stop = nullptr;  // the next ungapped launch records these (then cleared)
+    // compact host pair lists (encode_chunk): pinned encoding buffer (8 bytes per pair + slack), its device
+    // address, a decode event per chunk, and the encoded bytes of the last call
+    char* cp_host = nullptr;
+    char* cp_dev = nullptr;
+    size_t cp_bytes = 0;
+    DevBuf cp_hbm;  // the in-place encoding's chunks copied into HBM (same layout as cp_host)
+    std::vector<hipEvent_t> dec_ev;
+    int64_t cp_link = 0;
+    // the next ungapped launch reads its pair list in the host encoding (OvlUngappedArgs::ix_*), or null
+    const uint16_t* ix_b16 = nullptr;
+    const uint8_t* ix_d8 = nullptr;
+    const int32_t* ix_base = nullptr;
+    ResidentGrid res;  // the resident scoring grid (ovl_resident.h), launched by the first call that uses it
+    std::unique_ptr<DevWorker> worker;  // multi-device contexts: this device's host thread (run_pipeline)
+};
 
 struct Plan {
     int kernel = OVL_KERNEL_NONE;
@@ -528,7 +489,6 @@ struct PipeTrace {
 void free_staging(int32_t*& p);
 hipError_t alloc_staging(int32_t*& p, int32_t*& p_dev, int64_t cap);
 bool host_pinned(const void* p, size_t bytes);
-void quiet(ovl_ctx* c);
 // ovl_plan.cpp
 int launch_score(Dev* c, const Plan& pl, const int32_t* d_a, const int32_t* d_b, int64_t n_pairs,
                  int32_t match, int32_t mismatch, int64_t indel, int32_t* d_score, int32_t* d_end,

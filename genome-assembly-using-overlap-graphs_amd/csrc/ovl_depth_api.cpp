@@ -115,18 +115,15 @@ OVL_API int ovl_read_best(ovl_ctx* ctx, const uint8_t* reads, const int64_t* r_o
                           int32_t* n_best, int32_t* best_start, int32_t* best_end, uint32_t* tie_bits,
                           int32_t* scores) {
     if (!ctx) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
-    quiet(ctx);
-    Dev* c = ctx->devs[0];
-    DeviceGuard guard;
-    const auto t_call = std::chrono::steady_clock::now();
+    StageCall call(ctx);
+    Dev* c = call.dev;
     SeqShape sh;
     const int rc = check_read_best(c, reads, r_off, n_reads, contigs, c_off, n_contigs, read_length, match,
                                    best_score, first_best, n_best, best_start, best_end, &sh);
     if (rc != OVL_OK) return rc;
     zero_outputs(n_reads, n_contigs, best_score, first_best, n_best, best_start, best_end, tie_bits, scores);
-    ctx->x_rb_lane = ctx->x_rb_fallback = 0;
-    ctx->x_rb_launches = 0;
-    ctx->t_kernel_ms = ctx->t_call_ms = 0.0;
+    call.begin();
+    c->rb.last = {};
     if (n_reads == 0 || n_contigs == 0) return OVL_OK;
     const int32_t C = n_contigs;
     const int64_t words = ((int64_t)C + 31) / 32;
@@ -195,36 +192,34 @@ OVL_API int ovl_read_best(ovl_ctx* ctx, const uint8_t* reads, const int64_t* r_o
         const size_t res_bytes = sizeof(int32_t) * (size_t)pitch;
         HIPCHK(c, hipSetDevice(c->device));
         hipStream_t s = c->stream;
-        HIPCHK(c, ensure(c->rb_in, blob.size()));
-        HIPCHK(c, ensure(c->rb_tile, 2 * tile_half));
-        HIPCHK(c, ensure(c->rb_res, 4 * res_bytes));
-        if (tie_bits) HIPCHK(c, ensure(c->rb_bits, sizeof(uint32_t) * (size_t)nl * (size_t)words));
-        HIPCHK(c, hipMemcpyAsync(c->rb_in.p, blob.data(), blob.size(), hipMemcpyHostToDevice, s));
-        HIPCHK(c, hipMemsetAsync(c->rb_res.p, 0, 4 * res_bytes, s));
-        HIPCHK(c, hipMemsetAsync(as<char>(c->rb_res) + res_bytes, 0xFF, res_bytes, s));  // first = -1
-        if (tie_bits) HIPCHK(c, hipMemsetAsync(c->rb_bits.p, 0, sizeof(uint32_t) * (size_t)nl * (size_t)words, s));
+        HIPCHK(c, ensure(c->rb.in, blob.size()));
+        HIPCHK(c, ensure(c->rb.tile, 2 * tile_half));
+        HIPCHK(c, ensure(c->rb.res, 4 * res_bytes));
+        if (tie_bits) HIPCHK(c, ensure(c->rb.bits, sizeof(uint32_t) * (size_t)nl * (size_t)words));
+        HIPCHK(c, hipMemcpyAsync(c->rb.in.p, blob.data(), blob.size(), hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipMemsetAsync(c->rb.res.p, 0, 4 * res_bytes, s));
+        HIPCHK(c, hipMemsetAsync(as<char>(c->rb.res) + res_bytes, 0xFF, res_bytes, s));  // first = -1
+        if (tie_bits) HIPCHK(c, hipMemsetAsync(c->rb.bits.p, 0, sizeof(uint32_t) * (size_t)nl * (size_t)words, s));
         OvlLocalLaneArgs a{};
-        a.reads = as<uint8_t>(c->rb_in);
-        a.r_len = reinterpret_cast<const int32_t*>(as<char>(c->rb_in) + o_len);
-        a.c_off = reinterpret_cast<const int64_t*>(as<char>(c->rb_in) + o_coff);
-        a.c_len = reinterpret_cast<const int32_t*>(as<char>(c->rb_in) + o_clen);
-        a.contigs = as<uint8_t>(c->rb_in) + o_sym;
+        a.reads = as<uint8_t>(c->rb.in);
+        a.r_len = reinterpret_cast<const int32_t*>(as<char>(c->rb.in) + o_len);
+        a.c_off = reinterpret_cast<const int64_t*>(as<char>(c->rb.in) + o_coff);
+        a.c_len = reinterpret_cast<const int32_t*>(as<char>(c->rb.in) + o_clen);
+        a.contigs = as<uint8_t>(c->rb.in) + o_sym;
         a.pitch = pitch;
         a.read_length = read_length;
         a.match = match;
         a.mismatch = mismatch;
         a.indel = (int32_t)std::max<int64_t>(indel, -(int64_t(1) << 30));  // below: never taken either way
-        a.tile_score = as<int32_t>(c->rb_tile);
-        a.tile_end = reinterpret_cast<uint32_t*>(as<char>(c->rb_tile) + tile_half);
-        int32_t* d_best = as<int32_t>(c->rb_res);
+        a.tile_score = as<int32_t>(c->rb.tile);
+        a.tile_end = reinterpret_cast<uint32_t*>(as<char>(c->rb.tile) + tile_half);
+        int32_t* d_best = as<int32_t>(c->rb.res);
         int32_t* d_first = d_best + pitch;
         int32_t* d_nbest = d_first + pitch;
         uint32_t* d_cell = reinterpret_cast<uint32_t*>(d_nbest + pitch);
         const int32_t groups = (int32_t)(pitch / 64);
-        if (ctx->timing) {
-            HIPCHK(c, ensure_events(c->rb_ev));
-            HIPCHK(c, hipEventRecord(c->rb_ev[0], s));
-        }
+        HIPCHK(c, c->rb.timer.arm(ctx->timing));
+        HIPCHK(c, c->rb.timer.mark(0, s));
         std::vector<int32_t> h_tile;
         for (int64_t lo = 0; lo < C; lo += chunk) {
             a.c_lo = (int32_t)lo;
@@ -233,9 +228,9 @@ OVL_API int ovl_read_best(ovl_ctx* ctx, const uint8_t* reads, const int64_t* r_o
             const int32_t split = (int32_t)std::min<int64_t>(
                 a.c_hi - a.c_lo, std::max<int64_t>(1, ((int64_t)c->cu_count * 8 + groups - 1) / groups));
             HIPCHK(c, ovl_launch_local_lane(&a, rows, groups, split, s));
-            ++ctx->x_rb_launches;
+            ++c->rb.last.launches;
             HIPCHK(c, ovl_launch_read_best_fold(&a, nl, (int32_t)words, d_best, d_first, d_nbest, d_cell,
-                                                tie_bits ? as<uint32_t>(c->rb_bits) : nullptr, s));
+                                                tie_bits ? as<uint32_t>(c->rb.bits) : nullptr, s));
             if (scores) {
                 const size_t cnt = (size_t)pitch * (size_t)(a.c_hi - a.c_lo);
                 h_tile.resize(cnt);
@@ -248,19 +243,15 @@ OVL_API int ovl_read_best(ovl_ctx* ctx, const uint8_t* reads, const int64_t* r_o
                             h_tile[(size_t)(cc - a.c_lo) * (size_t)pitch + (size_t)k];
             }
         }
-        if (ctx->timing) HIPCHK(c, hipEventRecord(c->rb_ev[1], s));
+        HIPCHK(c, c->rb.timer.mark(1, s));
         std::vector<int32_t> res(4 * (size_t)pitch);
         std::vector<uint32_t> h_bits(tie_bits ? (size_t)nl * (size_t)words : 0);
-        HIPCHK(c, hipMemcpyAsync(res.data(), c->rb_res.p, 4 * res_bytes, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(res.data(), c->rb.res.p, 4 * res_bytes, hipMemcpyDeviceToHost, s));
         if (tie_bits)
-            HIPCHK(c, hipMemcpyAsync(h_bits.data(), c->rb_bits.p, h_bits.size() * sizeof(uint32_t),
+            HIPCHK(c, hipMemcpyAsync(h_bits.data(), c->rb.bits.p, h_bits.size() * sizeof(uint32_t),
                                      hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipStreamSynchronize(s));
-        if (ctx->timing) {
-            float ms = 0.f;
-            HIPCHK(c, hipEventElapsedTime(&ms, c->rb_ev[0], c->rb_ev[1]));
-            kernel_ms += ms;
-        }
+        kernel_ms = c->rb.timer.ms(0, 1);
         for (int32_t k = 0; k < nl; ++k) {
             const int32_t r = lane[(size_t)k];
             const int32_t f = res[(size_t)pitch + (size_t)k];
@@ -276,7 +267,7 @@ OVL_API int ovl_read_best(ovl_ctx* ctx, const uint8_t* reads, const int64_t* r_o
                 memcpy(tie_bits + r * words, h_bits.data() + (size_t)k * (size_t)words,
                        sizeof(uint32_t) * (size_t)words);
         }
-        ctx->x_rb_lane = (int64_t)nl * C;
+        c->rb.last.lane = (int64_t)nl * C;
     }
 
     // the other reads: one batched call per read, its copies against every contig's window, scores only
@@ -319,7 +310,7 @@ OVL_API int ovl_read_best(ovl_ctx* ctx, const uint8_t* reads, const int64_t* r_o
             cell_i[(size_t)r] = p.bi;
             cell_j[(size_t)r] = p.bj;
         }
-        ctx->x_rb_fallback = (int64_t)other.size() * C;
+        c->rb.last.fallback = (int64_t)other.size() * C;
     }
 
     // start positions: every read with a positive score against its first best contig, with the traceback.  The
@@ -386,15 +377,14 @@ OVL_API int ovl_read_best(ovl_ctx* ctx, const uint8_t* reads, const int64_t* r_o
         }
         r0 = r1;
     }
-    ctx->t_kernel_ms = kernel_ms;
-    ctx->t_call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
-    return OVL_OK;
+    return call.done(kernel_ms);
 }
 
 OVL_API int ovl_last_read_best(const ovl_ctx* ctx, int64_t* lane_pairs, int64_t* fallback_pairs, int32_t* launches) {
     if (!ctx) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
-    if (lane_pairs) *lane_pairs = ctx->x_rb_lane;
-    if (fallback_pairs) *fallback_pairs = ctx->x_rb_fallback;
-    if (launches) *launches = ctx->x_rb_launches;
+    const ReadBestState::Last& r = ctx->devs[0]->rb.last;
+    if (lane_pairs) *lane_pairs = r.lane;
+    if (fallback_pairs) *fallback_pairs = r.fallback;
+    if (launches) *launches = r.launches;
     return OVL_OK;
 }

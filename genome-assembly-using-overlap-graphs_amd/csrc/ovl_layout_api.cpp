@@ -8,11 +8,7 @@
 
 namespace {
 
-struct LayoutStats {
-    int64_t links = 0, cycles = 0, on_path = 0;
-    int32_t levels = 0;
-};
-thread_local LayoutStats g_host_stats;  // ovl_last_layout(NULL): this thread's last ovl_layout_host
+thread_local LayoutState::Last g_host_stats;  // ovl_last_layout(NULL): this thread's last ovl_layout_host
 
 constexpr int64_t kLayoutMax = int64_t(1) << 31;
 
@@ -108,25 +104,26 @@ int work_bytes(Dev* c, int32_t n, int64_t total, bool spell, size_t* bytes, size
 int check_fits(Dev* c, size_t need) {
     size_t free_b = 0, total_b = 0;
     HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
-    const size_t held = c->ly_in.bytes + c->ly_work.bytes + c->ly_bases.bytes + c->ly_temp.bytes;
+    const size_t held = c->ly.in.bytes + c->ly.work.bytes + c->ly.bases.bytes + c->ly.temp.bytes;
     if (need > free_b + held)
         return fail(c, OVL_E_UNSUPPORTED, "layout: %zu bytes of columns and tables do not fit the device (%zu free)",
                     need, free_b + held);
     return OVL_OK;
 }
 
-// From the link kernel to the outputs, on c->stream; the events of timing are recorded from ly_ev[1] on.
-int run_layout(ovl_ctx* ctx, Dev* c, const DeviceColumns& in, int32_t min_score, int32_t min_overlap, size_t temp,
+// From the link kernel to the outputs, on c->stream; the timer's marks are recorded from mark 1 on (the caller armed it
+// and recorded 0 and 1).  On success the stream is synchronised and the phases' times are read.
+int run_layout(Dev* c, const DeviceColumns& in, int32_t min_score, int32_t min_overlap, size_t temp,
                const Outputs& o) {
     hipStream_t s = c->stream;
     const int32_t n = in.n;
     const int32_t levels = ovl_layout_levels(n);
-    ctx->x_ly_levels = levels;
+    c->ly.last.levels = levels;
     const WorkPlan w(n, levels);
-    HIPCHK(c, ensure(c->ly_work, w.bytes));
-    if (temp) HIPCHK(c, ensure(c->ly_temp, temp));
-    if (o.bases && in.total > 0) HIPCHK(c, ensure(c->ly_bases, (size_t)in.total));
-    char* base = as<char>(c->ly_work);
+    HIPCHK(c, ensure(c->ly.work, w.bytes));
+    if (temp) HIPCHK(c, ensure(c->ly.temp, temp));
+    if (o.bases && in.total > 0) HIPCHK(c, ensure(c->ly.bases, (size_t)in.total));
+    char* base = as<char>(c->ly.work);
     OvlLayoutArgs g{};
     g.n = n;
     g.levels = levels;
@@ -158,7 +155,7 @@ int run_layout(ovl_ctx* ctx, Dev* c, const DeviceColumns& in, int32_t min_score,
     g.seqs = in.seqs;
     g.off = in.off;
     g.table = in.table;
-    g.bases = o.bases && in.total > 0 ? as<uint8_t>(c->ly_bases) : nullptr;
+    g.bases = o.bases && in.total > 0 ? as<uint8_t>(c->ly.bases) : nullptr;
     g.bases_cap = in.total;
 
     unsigned long long ctr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -166,7 +163,7 @@ int run_layout(ovl_ctx* ctx, Dev* c, const DeviceColumns& in, int32_t min_score,
         HIPCHK(c, hipMemsetAsync(g.best, 0, sizeof(unsigned long long) * (size_t)n, s));
         HIPCHK(c, hipMemsetAsync(g.ctr, 0, 64, s));
         HIPCHK(c, ovl_launch_layout_link(&g, c->k.layout_runs, s));
-        if (ctx->timing) HIPCHK(c, hipEventRecord(c->ly_ev[2], s));
+        HIPCHK(c, c->ly.timer.mark(2, s));
         HIPCHK(c, ovl_launch_layout_double(&g, 1, s));
         HIPCHK(c, ovl_launch_layout_cut(&g, s));
         HIPCHK(c, hipMemcpyAsync(ctr, g.ctr, 64, hipMemcpyDeviceToHost, s));
@@ -175,10 +172,10 @@ int run_layout(ovl_ctx* ctx, Dev* c, const DeviceColumns& in, int32_t min_score,
             if (ctr[0] == 0) return fail(c, OVL_E_INTERNAL, "layout: %llu nodes on cycles and no cut", ctr[3]);
             HIPCHK(c, ovl_launch_layout_double(&g, 0, s));
         }
-        HIPCHK(c, ovl_launch_layout_place(&g, c->ly_temp.p, c->ly_temp.bytes, s));
-        if (ctx->timing) HIPCHK(c, hipEventRecord(c->ly_ev[3], s));
+        HIPCHK(c, ovl_launch_layout_place(&g, c->ly.temp.p, c->ly.temp.bytes, s));
+        HIPCHK(c, c->ly.timer.mark(3, s));
         HIPCHK(c, ovl_launch_layout_spell(&g, (int32_t)std::min<int64_t>(n, (int64_t)c->cu_count * 32), s));
-        if (ctx->timing) HIPCHK(c, hipEventRecord(c->ly_ev[4], s));
+        HIPCHK(c, c->ly.timer.mark(4, s));
         HIPCHK(c, hipMemcpyAsync(ctr, g.ctr, 64, hipMemcpyDeviceToHost, s));
         const size_t n4 = sizeof(int32_t) * (size_t)n;
         if (o.succ) HIPCHK(c, hipMemcpyAsync(o.succ, g.succ, n4, hipMemcpyDeviceToHost, s));
@@ -200,18 +197,19 @@ int run_layout(ovl_ctx* ctx, Dev* c, const DeviceColumns& in, int32_t min_score,
         o.c_off[0] = 0;
     }
     *o.n_contigs = (int32_t)ctr[4];
-    ctx->x_ly_cycles = (int64_t)ctr[0];
-    ctx->x_ly_links = (int64_t)ctr[1];
-    ctx->x_ly_on_path = (int64_t)ctr[2];
-    if (ctx->timing && n > 0) {
-        float ms = 0.f;
-        for (int i = 0; i < 4; ++i) {
-            HIPCHK(c, hipEventElapsedTime(&ms, c->ly_ev[i], c->ly_ev[i + 1]));
-            ctx->x_ly_ms[i] = ms;
-        }
-        ctx->t_kernel_ms = ctx->x_ly_ms[0] + ctx->x_ly_ms[1] + ctx->x_ly_ms[2] + ctx->x_ly_ms[3];
-    }
+    c->ly.last.cycles = (int64_t)ctr[0];
+    c->ly.last.links = (int64_t)ctr[1];
+    c->ly.last.on_path = (int64_t)ctr[2];
+    if (n > 0)
+        for (int i = 0; i < 4; ++i) c->ly.last.ms[i] = c->ly.timer.ms(i, i + 1);
     return OVL_OK;
+}
+
+// A layout call's end, whether run_layout succeeded or not: the phases' sum and the clock
+int finish(StageCall& call, int rc) {
+    const double* ms = call.dev->ly.last.ms;
+    call.done(ms[0] + ms[1] + ms[2] + ms[3]);
+    return rc;
 }
 
 // From the first copy enqueued to the return: whichever way a device call leaves, the stream is drained before the
@@ -226,13 +224,6 @@ struct StreamDrain {
     }
 };
 
-void reset_stats(ovl_ctx* ctx) {
-    ctx->x_ly_links = ctx->x_ly_cycles = ctx->x_ly_on_path = 0;
-    ctx->x_ly_levels = 0;
-    for (double& ms : ctx->x_ly_ms) ms = 0.0;
-    ctx->t_kernel_ms = ctx->t_call_ms = 0.0;
-}
-
 }  // namespace
 
 OVL_API int ovl_layout_host(const uint8_t* seqs, const int64_t* offsets, int32_t n_reads, const int32_t* a,
@@ -245,7 +236,7 @@ OVL_API int ovl_layout_host(const uint8_t* seqs, const int64_t* offsets, int32_t
     const int rc = check_layout(none, seqs, offsets, n_reads, a, b, score, end, n_pairs, true, min_overlap, bases,
                                 n_contigs, &total);
     if (rc != OVL_OK) return rc;
-    g_host_stats = LayoutStats{};
+    g_host_stats = {};
     const size_t n = (size_t)n_reads;
     try {
         auto len = [&](int32_t r) { return (int32_t)(offsets[r + 1] - offsets[r]); };
@@ -356,10 +347,8 @@ OVL_API int ovl_layout(ovl_ctx* ctx, const uint8_t* seqs, const int64_t* offsets
                        int32_t min_overlap, int32_t* succ, int32_t* link, int32_t* contig, int32_t* offset,
                        uint8_t* on_path, uint8_t* bases, int64_t* c_off, int32_t* n_contigs) {
     if (!ctx) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
-    quiet(ctx);
-    Dev* c = ctx->devs[0];
-    DeviceGuard guard;
-    const auto t_call = std::chrono::steady_clock::now();
+    StageCall call(ctx);
+    Dev* c = call.dev;
     int64_t total = 0;
     int rc = check_layout(c, seqs, offsets, n_reads, a, b, score, end, n_pairs, true, min_overlap, bases, n_contigs,
                           &total);
@@ -374,7 +363,8 @@ OVL_API int ovl_layout(ovl_ctx* ctx, const uint8_t* seqs, const int64_t* offsets
     size_t work = 0, temp = 0;
     if ((rc = work_bytes(c, n_reads, total, spell, &work, &temp)) != OVL_OK) return rc;
     if ((rc = check_fits(c, in_bytes + work)) != OVL_OK) return rc;
-    reset_stats(ctx);
+    call.begin();
+    c->ly.last = {};
     std::vector<int32_t> h_len(N, 0);
     std::vector<int64_t> h_off(N + 1, 0);
     for (int32_t r = 0; r < n_reads; ++r) {
@@ -382,9 +372,9 @@ OVL_API int ovl_layout(ovl_ctx* ctx, const uint8_t* seqs, const int64_t* offsets
         h_off[(size_t)r + 1] = offsets[r + 1] - offsets[0];
     }
     hipStream_t s = c->stream;
-    HIPCHK(c, ensure(c->ly_in, in_bytes));
-    if (ctx->timing) HIPCHK(c, ensure_events(c->ly_ev));
-    char* in = as<char>(c->ly_in);
+    HIPCHK(c, ensure(c->ly.in, in_bytes));
+    HIPCHK(c, c->ly.timer.arm(ctx->timing));
+    char* in = as<char>(c->ly.in);
     StreamDrain drain(s);
     HIPCHK(c, hipMemcpyAsync(in + o_len, h_len.data(), 4 * N, hipMemcpyHostToDevice, s));
     HIPCHK(c, hipMemcpyAsync(in + o_off, h_off.data(), 8 * (N + 1), hipMemcpyHostToDevice, s));
@@ -395,10 +385,8 @@ OVL_API int ovl_layout(ovl_ctx* ctx, const uint8_t* seqs, const int64_t* offsets
         HIPCHK(c, hipMemcpyAsync(in + o_s, score, 4 * E, hipMemcpyHostToDevice, s));
         HIPCHK(c, hipMemcpyAsync(in + o_e, end, 4 * E, hipMemcpyHostToDevice, s));
     }
-    if (ctx->timing) {  // after the uploads; nothing is scored here
-        HIPCHK(c, hipEventRecord(c->ly_ev[0], s));
-        HIPCHK(c, hipEventRecord(c->ly_ev[1], s));
-    }
+    HIPCHK(c, c->ly.timer.mark(0, s));  // after the uploads; nothing is scored here
+    HIPCHK(c, c->ly.timer.mark(1, s));
     DeviceColumns d;
     d.n = n_reads;
     d.n_pairs = n_pairs;
@@ -410,13 +398,11 @@ OVL_API int ovl_layout(ovl_ctx* ctx, const uint8_t* seqs, const int64_t* offsets
     d.b = reinterpret_cast<const int32_t*>(in + o_b);
     d.score = reinterpret_cast<const int32_t*>(in + o_s);
     d.end = reinterpret_cast<const int32_t*>(in + o_e);
-    rc = run_layout(ctx, c, d, min_score, min_overlap, temp,
+    rc = run_layout(c, d, min_score, min_overlap, temp,
                     Outputs{succ, link, contig, offset, on_path, bases, c_off, n_contigs});
     drain.armed = rc != OVL_OK;  // (a successful run_layout ends with the stream synchronised)
-    ctx->t_kernel_ms -= ctx->x_ly_ms[0];  // (two events with nothing between them)
-    ctx->x_ly_ms[0] = 0.0;
-    ctx->t_call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
-    return rc;
+    c->ly.last.ms[0] = 0.0;      // (two marks with nothing between them)
+    return finish(call, rc);
 }
 
 OVL_API int ovl_layout_candidates(ovl_ctx* ctx, int32_t match, int32_t mismatch, int64_t indel, int32_t band,
@@ -424,12 +410,10 @@ OVL_API int ovl_layout_candidates(ovl_ctx* ctx, int32_t match, int32_t mismatch,
                                   int32_t* contig, int32_t* offset, uint8_t* on_path, uint8_t* bases, int64_t* c_off,
                                   int32_t* n_contigs) {
     if (!ctx) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
-    quiet(ctx);
-    Dev* c = ctx->devs[0];
+    StageCall call(ctx);
+    Dev* c = call.dev;
     if (c->n_reads < 0 || !ctx->res_valid) return fail(c, OVL_E_STATE, "no resident reads: call ovl_set_reads first");
     if (c->cand_n < 0) return fail(c, OVL_E_STATE, "no candidate list: call ovl_candidates or ovl_seed_candidates first");
-    DeviceGuard guard;
-    const auto t_call = std::chrono::steady_clock::now();
     const int32_t n_reads = c->n_reads;
     const int64_t n_pairs = c->cand_n;
     int64_t total = 0;
@@ -446,23 +430,22 @@ OVL_API int ovl_layout_candidates(ovl_ctx* ctx, int32_t match, int32_t mismatch,
     size_t work = 0, temp = 0;
     if ((rc = work_bytes(c, n_reads, total, spell, &work, &temp)) != OVL_OK) return rc;
     if ((rc = check_fits(c, in_bytes + work)) != OVL_OK) return rc;
-    reset_stats(ctx);
+    call.begin();
+    c->ly.last = {};
     hipStream_t s = c->stream;
-    HIPCHK(c, ensure(c->ly_in, in_bytes));
-    char* in = as<char>(c->ly_in);
+    HIPCHK(c, ensure(c->ly.in, in_bytes));
+    char* in = as<char>(c->ly.in);
     StreamDrain drain(s);
     // the resident reads are symbol codes: code k is the k-th byte value of the read set
     HIPCHK(c, hipMemcpyAsync(in + o_t, ctx->hreads.inv, 256, hipMemcpyHostToDevice, s));
-    if (ctx->timing) {
-        HIPCHK(c, ensure_events(c->ly_ev));
-        HIPCHK(c, hipEventRecord(c->ly_ev[0], s));
-    }
+    HIPCHK(c, c->ly.timer.arm(ctx->timing));
+    HIPCHK(c, c->ly.timer.mark(0, s));
     if (n_pairs > 0) {
         rc = launch_score(c, p, as<int32_t>(c->cand_a), as<int32_t>(c->cand_b), n_pairs, match, mismatch, indel,
                           reinterpret_cast<int32_t*>(in + o_s), reinterpret_cast<int32_t*>(in + o_e), s);
         if (rc != OVL_OK) return rc;
     }
-    if (ctx->timing) HIPCHK(c, hipEventRecord(c->ly_ev[1], s));
+    HIPCHK(c, c->ly.timer.mark(1, s));
     DeviceColumns d;
     d.n = n_reads;
     d.n_pairs = n_pairs;
@@ -475,22 +458,15 @@ OVL_API int ovl_layout_candidates(ovl_ctx* ctx, int32_t match, int32_t mismatch,
     d.b = as<int32_t>(c->cand_b);
     d.score = reinterpret_cast<const int32_t*>(in + o_s);
     d.end = reinterpret_cast<const int32_t*>(in + o_e);
-    rc = run_layout(ctx, c, d, min_score, min_overlap, temp,
+    rc = run_layout(c, d, min_score, min_overlap, temp,
                     Outputs{succ, link, contig, offset, on_path, bases, c_off, n_contigs});
     drain.armed = rc != OVL_OK;
-    ctx->t_call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
-    return rc;
+    return finish(call, rc);
 }
 
 OVL_API int ovl_last_layout(const ovl_ctx* ctx, int64_t* links, int64_t* cycles, int32_t* levels,
                             int64_t* on_path_reads) {
-    LayoutStats st = g_host_stats;
-    if (ctx) {
-        st.links = ctx->x_ly_links;
-        st.cycles = ctx->x_ly_cycles;
-        st.on_path = ctx->x_ly_on_path;
-        st.levels = ctx->x_ly_levels;
-    }
+    const LayoutState::Last& st = ctx ? ctx->devs[0]->ly.last : g_host_stats;
     if (links) *links = st.links;
     if (cycles) *cycles = st.cycles;
     if (levels) *levels = st.levels;
@@ -501,9 +477,10 @@ OVL_API int ovl_last_layout(const ovl_ctx* ctx, int64_t* links, int64_t* cycles,
 OVL_API int ovl_last_layout_timing(const ovl_ctx* ctx, double* score_ms, double* link_ms, double* forest_ms,
                                    double* spell_ms) {
     if (!ctx) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
-    if (score_ms) *score_ms = ctx->x_ly_ms[0];
-    if (link_ms) *link_ms = ctx->x_ly_ms[1];
-    if (forest_ms) *forest_ms = ctx->x_ly_ms[2];
-    if (spell_ms) *spell_ms = ctx->x_ly_ms[3];
+    const double* ms = ctx->devs[0]->ly.last.ms;
+    if (score_ms) *score_ms = ms[0];
+    if (link_ms) *link_ms = ms[1];
+    if (forest_ms) *forest_ms = ms[2];
+    if (spell_ms) *spell_ms = ms[3];
     return OVL_OK;
 }

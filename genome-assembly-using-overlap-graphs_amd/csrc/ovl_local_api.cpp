@@ -209,41 +209,39 @@ int local_batch_launch(ovl_ctx* ctx, Dev* c, const uint8_t* queries, const int64
     if (!d_reference) memcpy(blob.data() + o_r, reference, (size_t)ref_len);
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    HIPCHK(c, ensure(c->lb_in, blob.size()));
-    HIPCHK(c, ensure(c->lb_ctr, 16));
-    HIPCHK(c, ensure(c->lb_out, sizeof(OvlLocalBatchRecord) * (size_t)nb));
-    if (!row_lds) HIPCHK(c, ensure(c->lb_rows, sizeof(int32_t) * (size_t)row_max * (size_t)waves));
+    HIPCHK(c, ensure(c->lb.in, blob.size()));
+    HIPCHK(c, ensure(c->lb.ctr, 16));
+    HIPCHK(c, ensure(c->lb.out, sizeof(OvlLocalBatchRecord) * (size_t)nb));
+    if (!row_lds) HIPCHK(c, ensure(c->lb.rows, sizeof(int32_t) * (size_t)row_max * (size_t)waves));
     if (with_ops) {
-        HIPCHK(c, ensure(c->lb_slabs, slab_pitch * (size_t)waves));
-        HIPCHK(c, ensure(c->lb_wops, (size_t)wops_pitch * (size_t)waves));
-        HIPCHK(c, ensure(c->lb_ops, (size_t)nm_sum));
+        HIPCHK(c, ensure(c->lb.slabs, slab_pitch * (size_t)waves));
+        HIPCHK(c, ensure(c->lb.wops, (size_t)wops_pitch * (size_t)waves));
+        HIPCHK(c, ensure(c->lb.ops, (size_t)nm_sum));
     }
-    HIPCHK(c, hipMemcpyAsync(c->lb_in.p, blob.data(), blob.size(), hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemsetAsync(c->lb_ctr.p, 0, 16, s));
+    HIPCHK(c, hipMemcpyAsync(c->lb.in.p, blob.data(), blob.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemsetAsync(c->lb.ctr.p, 0, 16, s));
     OvlLocalBatchArgs a{};
-    a.items = as<OvlLocalBatchItem>(c->lb_in);
-    a.q = as<uint8_t>(c->lb_in) + o_q;
-    a.ref = d_reference ? d_reference : as<uint8_t>(c->lb_in) + o_r;
+    a.items = as<OvlLocalBatchItem>(c->lb.in);
+    a.q = as<uint8_t>(c->lb.in) + o_q;
+    a.ref = d_reference ? d_reference : as<uint8_t>(c->lb.in) + o_r;
     a.n_items = nb;
     a.match = match;
     a.mismatch = mismatch;
     a.indel = indel;
-    a.counter = as<uint32_t>(c->lb_ctr);
-    a.ops_total = reinterpret_cast<unsigned long long*>(as<char>(c->lb_ctr) + 8);
-    a.rows = row_lds ? nullptr : as<int32_t>(c->lb_rows);
+    a.counter = as<uint32_t>(c->lb.ctr);
+    a.ops_total = reinterpret_cast<unsigned long long*>(as<char>(c->lb.ctr) + 8);
+    a.rows = row_lds ? nullptr : as<int32_t>(c->lb.rows);
     a.row_pitch = row_lds ? 0 : row_max;
-    a.slabs = with_ops ? as<int8_t>(c->lb_slabs) : nullptr;
+    a.slabs = with_ops ? as<int8_t>(c->lb.slabs) : nullptr;
     a.slab_pitch = (int64_t)slab_pitch;
-    a.wave_ops = with_ops ? as<int8_t>(c->lb_wops) : nullptr;
+    a.wave_ops = with_ops ? as<int8_t>(c->lb.wops) : nullptr;
     a.wave_ops_pitch = wops_pitch;
-    a.out = as<OvlLocalBatchRecord>(c->lb_out);
-    a.ops = with_ops ? as<int8_t>(c->lb_ops) : nullptr;
-    if (ctx->timing) {
-        HIPCHK(c, ensure_events(c->lb_ev));
-        HIPCHK(c, hipEventRecord(c->lb_ev[0], s));
-    }
+    a.out = as<OvlLocalBatchRecord>(c->lb.out);
+    a.ops = with_ops ? as<int8_t>(c->lb.ops) : nullptr;
+    HIPCHK(c, c->lb.timer.arm(ctx->timing));
+    HIPCHK(c, c->lb.timer.mark(0, s));
     HIPCHK(c, ovl_launch_local_batch(&a, (int32_t)waves, row_lds ? (uint32_t)(row_max * 4) : 0u, s));
-    if (ctx->timing) HIPCHK(c, hipEventRecord(c->lb_ev[1], s));
+    HIPCHK(c, c->lb.timer.mark(1, s));
     run->o_q = o_q;
     run->nb = nb;
     run->waves = (int32_t)waves;
@@ -260,10 +258,8 @@ OVL_API int ovl_local_align_batch(ovl_ctx* ctx, const uint8_t* queries, const in
                                   int32_t* out_score, int32_t* out_end_i, int32_t* out_end_j, int32_t* out_start_i,
                                   int32_t* out_start_j, int8_t* ops, const int64_t* ops_off, int64_t* out_n_ops) {
     if (!ctx) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
-    quiet(ctx);
-    Dev* c = ctx->devs[0];
-    DeviceGuard guard;
-    const auto t_call = std::chrono::steady_clock::now();
+    StageCall call(ctx);
+    Dev* c = call.dev;
     if (n_queries < 0 || ref_len < 0) return fail(c, OVL_E_ARG, "negative count or length");
     if (n_queries > 0 && !q_off) return fail(c, OVL_E_ARG, "q_off is NULL");
     if ((win_lo == nullptr) != (win_len == nullptr))
@@ -290,8 +286,9 @@ OVL_API int ovl_local_align_batch(ovl_ctx* ctx, const uint8_t* queries, const in
             return fail(c, OVL_E_UNSUPPORTED,
                         "local alignment, query %d: lengths < 2^20 and match * min(n, m) < 2^24 required", k);
     }
-    ctx->x_lb_batched = ctx->x_lb_single = ctx->x_lb_waves = 0;
-    ctx->t_kernel_ms = ctx->t_call_ms = 0.0;
+    call.begin();
+    c->lb.last = {};
+    double kernel_ms = 0.0;  // the batch kernel
     // route the queries: the slab limit holds only where a traceback is asked for
     std::vector<LocalBatchQuery> batch;
     std::vector<int32_t> single;
@@ -316,21 +313,17 @@ OVL_API int ovl_local_align_batch(ovl_ctx* ctx, const uint8_t* queries, const in
         const int64_t nm_sum = run.nm_sum;
         std::vector<OvlLocalBatchRecord> res((size_t)nb);
         unsigned long long ctr[2] = {0, 0};
-        HIPCHK(c, hipMemcpyAsync(res.data(), c->lb_out.p, res.size() * sizeof(res[0]), hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipMemcpyAsync(ctr, c->lb_ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(res.data(), c->lb.out.p, res.size() * sizeof(res[0]), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(ctr, c->lb.ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipStreamSynchronize(s));
-        if (ctx->timing) {
-            float ms = 0.f;
-            HIPCHK(c, hipEventElapsedTime(&ms, c->lb_ev[0], c->lb_ev[1]));
-            ctx->t_kernel_ms = ms;
-        }
+        kernel_ms = c->lb.timer.ms(0, 1);
         const unsigned long long total = ctr[1];
         if (total > (unsigned long long)nm_sum)
             return fail(c, OVL_E_INTERNAL, "batched local alignment: %llu ops for a capacity of %lld", total,
                         (long long)nm_sum);
         std::vector<int8_t> packed((size_t)total);
         if (total) {
-            HIPCHK(c, hipMemcpyAsync(packed.data(), c->lb_ops.p, (size_t)total, hipMemcpyDeviceToHost, s));
+            HIPCHK(c, hipMemcpyAsync(packed.data(), c->lb.ops.p, (size_t)total, hipMemcpyDeviceToHost, s));
             HIPCHK(c, hipStreamSynchronize(s));
         }
         for (int32_t b = 0; b < nb; ++b) {
@@ -347,8 +340,8 @@ OVL_API int ovl_local_align_batch(ovl_ctx* ctx, const uint8_t* queries, const in
                 out_n_ops[k] = o.n_ops;
             }
         }
-        ctx->x_lb_batched = nb;
-        ctx->x_lb_waves = run.waves;
+        c->lb.last.batched = nb;
+        c->lb.last.waves = run.waves;
     }
     for (int32_t k : single) {
         const int32_t n = (int32_t)(q_off[k + 1] - q_off[k]);
@@ -359,15 +352,15 @@ OVL_API int ovl_local_align_batch(ovl_ctx* ctx, const uint8_t* queries, const in
                                        out_n_ops + k);
         if (rc != OVL_OK) return rc;
     }
-    ctx->x_lb_single = (int32_t)single.size();
-    ctx->t_call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
-    return OVL_OK;
+    c->lb.last.single = (int32_t)single.size();
+    return call.done(kernel_ms);
 }
 
 OVL_API int ovl_last_local_batch(const ovl_ctx* ctx, int32_t* batched, int32_t* single, int32_t* waves) {
     if (!ctx) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
-    if (batched) *batched = ctx->x_lb_batched;
-    if (single) *single = ctx->x_lb_single;
-    if (waves) *waves = ctx->x_lb_waves;
+    const LocalBatchState::Last& l = ctx->devs[0]->lb.last;
+    if (batched) *batched = l.batched;
+    if (single) *single = l.single;
+    if (waves) *waves = l.waves;
     return OVL_OK;
 }

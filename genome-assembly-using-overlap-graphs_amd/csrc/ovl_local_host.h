@@ -36,15 +36,15 @@ struct LocalBatchQuery {
 };
 struct LocalBatchRun {
     std::vector<char> blob;  // the upload block: alive until the stream has been synchronised
-    size_t o_q = 0;          // offset of the queries' bytes in it (and in Dev::lb_in)
+    size_t o_q = 0;          // offset of the queries' bytes in it (and in Dev::lb.in)
     int32_t nb = 0, waves = 0;
-    int64_t nm_sum = 0;      // capacity of Dev::lb_ops
+    int64_t nm_sum = 0;      // capacity of Dev::lb.ops
 };
 
 // ovl_local_api.cpp: the batch kernel over `batch` (routed by the caller: every query fits the kernel), issued on
 // the device's stream and not waited for.  It sorts `batch` by descending cost; query batch[b] becomes item b, whose
-// OvlLocalBatchRecord is Dev::lb_out[b] and whose ops (with_ops) lie packed in Dev::lb_ops, their total at
-// Dev::lb_ctr + 8.  The windows are of `reference` (host, uploaded behind the queries) or, when d_reference is not
+// OvlLocalBatchRecord is Dev::lb.out[b] and whose ops (with_ops) lie packed in Dev::lb.ops, their total at
+// Dev::lb.ctr + 8.  The windows are of `reference` (host, uploaded behind the queries) or, when d_reference is not
 // NULL, of that device copy of it.
 int local_batch_launch(ovl_ctx* ctx, Dev* c, const uint8_t* queries, const int64_t* q_off,
                        std::vector<LocalBatchQuery>& batch, const uint8_t* reference, int32_t ref_len,

@@ -89,20 +89,16 @@ OVL_API int ovl_reach_reduce_host(const int64_t* off, const int32_t* head, int32
 OVL_API int ovl_reach_reduce(ovl_ctx* ctx, const int64_t* off, const int32_t* head, int32_t n_nodes, uint8_t* reduced,
                              int64_t* n_reduced, uint64_t* closure) {
     if (!ctx) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
-    quiet(ctx);
-    Dev* c = ctx->devs[0];
-    DeviceGuard guard;
-    const auto t_call = std::chrono::steady_clock::now();
+    StageCall call(ctx);
+    Dev* c = call.dev;
     const int rc = check_graph(c, off, head, nullptr, false, n_nodes, reduced, n_reduced, nullptr, nullptr);
     if (rc != OVL_OK) return rc;
     const int64_t n_edges = n_nodes > 0 ? off[n_nodes] : 0;
     const int32_t words = (int32_t)(((int64_t)n_nodes + 63) / 64);
     int32_t window_words = kReachWindowWords;
     if (c->k.reach_window > 0) window_words = std::min(kReachWindowWords, (c->k.reach_window + 63) / 64);
-    ctx->x_rc_words = words;
-    ctx->x_rc_blocks = words;  // ceil(n_nodes / 64) pivot blocks: one per word column
-    ctx->x_rc_window = window_words * 64;
-    ctx->t_kernel_ms = ctx->t_call_ms = 0.0;
+    call.begin();
+    c->rc.last = {words, words, window_words * 64};  // (ceil(n_nodes / 64) pivot blocks: one per word column)
     const size_t matrix_bytes = sizeof(uint64_t) * (size_t)n_nodes * (size_t)words;
     if (n_edges == 0) {  // nothing reaches anything
         if (closure && matrix_bytes) memset(closure, 0, matrix_bytes);
@@ -117,37 +113,35 @@ OVL_API int ovl_reach_reduce(ovl_ctx* ctx, const int64_t* off, const int32_t* he
                      [&](int32_t x, int32_t y) { return off[x + 1] - off[x] > off[y + 1] - off[y]; });
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    HIPCHK(c, ensure(c->rc_matrix, matrix_bytes));
-    HIPCHK(c, ensure(c->rc_pivot, sizeof(uint64_t) * 64 * (size_t)words));
-    HIPCHK(c, ensure(c->rc_off, sizeof(int64_t) * ((size_t)n_nodes + 1)));
-    HIPCHK(c, ensure(c->rc_head, sizeof(int32_t) * (size_t)n_edges));
-    HIPCHK(c, ensure(c->rc_order, sizeof(int32_t) * order.size()));
-    HIPCHK(c, ensure(c->rc_out, (size_t)n_edges));
-    HIPCHK(c, hipMemcpyAsync(c->rc_off.p, off, sizeof(int64_t) * ((size_t)n_nodes + 1), hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(c->rc_head.p, head, sizeof(int32_t) * (size_t)n_edges, hipMemcpyHostToDevice, s));
+    HIPCHK(c, ensure(c->rc.matrix, matrix_bytes));
+    HIPCHK(c, ensure(c->rc.pivot, sizeof(uint64_t) * 64 * (size_t)words));
+    HIPCHK(c, ensure(c->rc.off, sizeof(int64_t) * ((size_t)n_nodes + 1)));
+    HIPCHK(c, ensure(c->rc.head, sizeof(int32_t) * (size_t)n_edges));
+    HIPCHK(c, ensure(c->rc.order, sizeof(int32_t) * order.size()));
+    HIPCHK(c, ensure(c->rc.out, (size_t)n_edges));
+    HIPCHK(c, hipMemcpyAsync(c->rc.off.p, off, sizeof(int64_t) * ((size_t)n_nodes + 1), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(c->rc.head.p, head, sizeof(int32_t) * (size_t)n_edges, hipMemcpyHostToDevice, s));
     if (!order.empty())
-        HIPCHK(c, hipMemcpyAsync(c->rc_order.p, order.data(), sizeof(int32_t) * order.size(), hipMemcpyHostToDevice,
+        HIPCHK(c, hipMemcpyAsync(c->rc.order.p, order.data(), sizeof(int32_t) * order.size(), hipMemcpyHostToDevice,
                                  s));
-    HIPCHK(c, hipMemsetAsync(c->rc_out.p, 0, (size_t)n_edges, s));  // (nodes with one out-edge keep it)
+    HIPCHK(c, hipMemsetAsync(c->rc.out.p, 0, (size_t)n_edges, s));  // (nodes with one out-edge keep it)
     OvlReachArgs a{};
-    a.off = as<int64_t>(c->rc_off);
-    a.head = as<int32_t>(c->rc_head);
-    a.order = as<int32_t>(c->rc_order);
+    a.off = as<int64_t>(c->rc.off);
+    a.head = as<int32_t>(c->rc.head);
+    a.order = as<int32_t>(c->rc.order);
     a.n_nodes = n_nodes;
     a.n_order = (int32_t)order.size();
     a.words = words;
-    a.matrix = as<uint64_t>(c->rc_matrix);
-    a.pivot = as<uint64_t>(c->rc_pivot);
-    a.reduced = as<uint8_t>(c->rc_out);
+    a.matrix = as<uint64_t>(c->rc.matrix);
+    a.pivot = as<uint64_t>(c->rc.pivot);
+    a.reduced = as<uint8_t>(c->rc.out);
     const int32_t row_group = pow2_at_least(words, 64);
     // the window the marking walks with: never wider than a row, so that rows of up to 64 words take the
     // one-word-per-lane form (ovl_launch_reach_mark) at the default window too
     const int32_t mark_window = std::min(words, window_words);
     const int32_t mark_group = pow2_at_least(mark_window, 64);
-    if (ctx->timing) {
-        HIPCHK(c, ensure_events(c->rc_ev));
-        HIPCHK(c, hipEventRecord(c->rc_ev[0], s));
-    }
+    HIPCHK(c, c->rc.timer.arm(ctx->timing));
+    HIPCHK(c, c->rc.timer.mark(0, s));
     HIPCHK(c, ovl_launch_reach_fill(&a, s));
     if (closure || !order.empty()) {
         for (int32_t K = 0; K < words; ++K) {
@@ -156,26 +150,21 @@ OVL_API int ovl_reach_reduce(ovl_ctx* ctx, const int64_t* off, const int32_t* he
         }
     }
     HIPCHK(c, ovl_launch_reach_mark(&a, mark_group, mark_window, s));
-    if (ctx->timing) HIPCHK(c, hipEventRecord(c->rc_ev[1], s));
-    HIPCHK(c, hipMemcpyAsync(reduced, c->rc_out.p, (size_t)n_edges, hipMemcpyDeviceToHost, s));
-    if (closure) HIPCHK(c, hipMemcpyAsync(closure, c->rc_matrix.p, matrix_bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, c->rc.timer.mark(1, s));
+    HIPCHK(c, hipMemcpyAsync(reduced, c->rc.out.p, (size_t)n_edges, hipMemcpyDeviceToHost, s));
+    if (closure) HIPCHK(c, hipMemcpyAsync(closure, c->rc.matrix.p, matrix_bytes, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
-    if (ctx->timing) {
-        float ms = 0.f;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->rc_ev[0], c->rc_ev[1]));
-        ctx->t_kernel_ms = ms;
-    }
     int64_t count = 0;
     for (int64_t e = 0; e < n_edges; ++e) count += reduced[e];
     *n_reduced = count;
-    ctx->t_call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
-    return OVL_OK;
+    return call.done(c->rc.timer.ms(0, 1));
 }
 
 OVL_API int ovl_last_reach(const ovl_ctx* ctx, int32_t* words_per_row, int32_t* pivot_blocks, int32_t* window_bits) {
     if (!ctx) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
-    if (words_per_row) *words_per_row = ctx->x_rc_words;
-    if (pivot_blocks) *pivot_blocks = ctx->x_rc_blocks;
-    if (window_bits) *window_bits = ctx->x_rc_window;
+    const ReachState::Last& r = ctx->devs[0]->rc.last;
+    if (words_per_row) *words_per_row = r.words;
+    if (pivot_blocks) *pivot_blocks = r.blocks;
+    if (window_bits) *window_bits = r.window;
     return OVL_OK;
 }

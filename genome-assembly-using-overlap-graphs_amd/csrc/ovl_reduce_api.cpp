@@ -52,20 +52,16 @@ OVL_API int ovl_transitive_reduce_host(const int64_t* off, const int32_t* head, 
 OVL_API int ovl_transitive_reduce(ovl_ctx* ctx, const int64_t* off, const int32_t* head, const int64_t* weight,
                                   int32_t n_nodes, uint8_t* reduced, int64_t* n_reduced) {
     if (!ctx) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
-    quiet(ctx);
-    Dev* c = ctx->devs[0];
-    DeviceGuard guard;
-    const auto t_call = std::chrono::steady_clock::now();
+    StageCall call(ctx);
+    Dev* c = call.dev;
     std::vector<int64_t> work;
     int64_t steps = 0;
     const int rc = check_graph(c, off, head, weight, true, n_nodes, reduced, n_reduced, &work, &steps);
     if (rc != OVL_OK) return rc;
     const int64_t n_edges = n_nodes > 0 ? off[n_nodes] : 0;
     const int32_t window = std::min(kReduceWindow, c->k.tr_window > 0 ? c->k.tr_window : kReduceWindow);
-    ctx->x_tr_window = window;
-    ctx->x_tr_passes = (int32_t)(((int64_t)n_nodes + window - 1) / window);
-    ctx->x_tr_steps = steps;
-    ctx->t_kernel_ms = ctx->t_call_ms = 0.0;
+    call.begin();
+    c->tr.last = {window, (int32_t)(((int64_t)n_nodes + window - 1) / window), steps};
     *n_reduced = 0;
     if (n_edges == 0) return OVL_OK;
     // nodes with out-edges, heaviest first (ties in node order)
@@ -83,51 +79,44 @@ OVL_API int ovl_transitive_reduce(ovl_ctx* ctx, const int64_t* off, const int32_
     while (group < 64 && group * kReduceLoads < mean) group *= 2;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    HIPCHK(c, ensure(c->tr_off, sizeof(int64_t) * ((size_t)n_nodes + 1)));
-    HIPCHK(c, ensure(c->tr_edge, sizeof(int2) * (size_t)n_edges));
-    HIPCHK(c, ensure(c->tr_order, sizeof(int32_t) * order.size()));
-    HIPCHK(c, ensure(c->tr_ctr, 16));
-    HIPCHK(c, ensure(c->tr_out, (size_t)n_edges));
-    HIPCHK(c, hipMemcpyAsync(c->tr_off.p, off, sizeof(int64_t) * ((size_t)n_nodes + 1), hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(c->tr_edge.p, edge.data(), sizeof(int2) * (size_t)n_edges, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(c->tr_order.p, order.data(), sizeof(int32_t) * order.size(), hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemsetAsync(c->tr_ctr.p, 0, 16, s));
-    HIPCHK(c, hipMemsetAsync(c->tr_out.p, 0, (size_t)n_edges, s));
+    HIPCHK(c, ensure(c->tr.off, sizeof(int64_t) * ((size_t)n_nodes + 1)));
+    HIPCHK(c, ensure(c->tr.edge, sizeof(int2) * (size_t)n_edges));
+    HIPCHK(c, ensure(c->tr.order, sizeof(int32_t) * order.size()));
+    HIPCHK(c, ensure(c->tr.ctr, 16));
+    HIPCHK(c, ensure(c->tr.out, (size_t)n_edges));
+    HIPCHK(c, hipMemcpyAsync(c->tr.off.p, off, sizeof(int64_t) * ((size_t)n_nodes + 1), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(c->tr.edge.p, edge.data(), sizeof(int2) * (size_t)n_edges, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(c->tr.order.p, order.data(), sizeof(int32_t) * order.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemsetAsync(c->tr.ctr.p, 0, 16, s));
+    HIPCHK(c, hipMemsetAsync(c->tr.out.p, 0, (size_t)n_edges, s));
     OvlReduceArgs a{};
-    a.off = as<int64_t>(c->tr_off);
-    a.edge = as<int2>(c->tr_edge);
-    a.order = as<int32_t>(c->tr_order);
+    a.off = as<int64_t>(c->tr.off);
+    a.edge = as<int2>(c->tr.edge);
+    a.order = as<int32_t>(c->tr.order);
     a.n_nodes = n_nodes;
     a.n_order = (int32_t)order.size();
     a.window = window;
     a.group = group;
-    a.counter = as<uint32_t>(c->tr_ctr);
-    a.reduced = as<uint8_t>(c->tr_out);
+    a.counter = as<uint32_t>(c->tr.ctr);
+    a.reduced = as<uint8_t>(c->tr.out);
     const int32_t blocks = (int32_t)std::min<int64_t>((int64_t)order.size(), (int64_t)c->cu_count * kReduceBlocksPerCu);
-    if (ctx->timing) {
-        HIPCHK(c, ensure_events(c->tr_ev));
-        HIPCHK(c, hipEventRecord(c->tr_ev[0], s));
-    }
+    HIPCHK(c, c->tr.timer.arm(ctx->timing));
+    HIPCHK(c, c->tr.timer.mark(0, s));
     HIPCHK(c, ovl_launch_reduce(&a, blocks, s));
-    if (ctx->timing) HIPCHK(c, hipEventRecord(c->tr_ev[1], s));
-    HIPCHK(c, hipMemcpyAsync(reduced, c->tr_out.p, (size_t)n_edges, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, c->tr.timer.mark(1, s));
+    HIPCHK(c, hipMemcpyAsync(reduced, c->tr.out.p, (size_t)n_edges, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
-    if (ctx->timing) {
-        float ms = 0.f;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->tr_ev[0], c->tr_ev[1]));
-        ctx->t_kernel_ms = ms;
-    }
     int64_t count = 0;
     for (int64_t e = 0; e < n_edges; ++e) count += reduced[e];
     *n_reduced = count;
-    ctx->t_call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
-    return OVL_OK;
+    return call.done(c->tr.timer.ms(0, 1));
 }
 
 OVL_API int ovl_last_transitive(const ovl_ctx* ctx, int32_t* window_nodes, int32_t* passes, int64_t* two_hop_steps) {
     if (!ctx) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
-    if (window_nodes) *window_nodes = ctx->x_tr_window;
-    if (passes) *passes = ctx->x_tr_passes;
-    if (two_hop_steps) *two_hop_steps = ctx->x_tr_steps;
+    const TransitiveState::Last& t = ctx->devs[0]->tr.last;
+    if (window_nodes) *window_nodes = t.window;
+    if (passes) *passes = t.passes;
+    if (two_hop_steps) *two_hop_steps = t.steps;
     return OVL_OK;
 }

@@ -135,11 +135,6 @@ struct StreamDrain {
     ~StreamDrain() { (void)hipStreamSynchronize(s); }
 };
 
-void reset_stats(ovl_ctx* ctx) {
-    for (double& ms : ctx->x_sp_ms) ms = 0.0;
-    ctx->t_kernel_ms = ctx->t_call_ms = 0.0;
-}
-
 // Uploads the reads and runs the key, sort and count passes: on return the stream is synchronised, g describes the
 // spectrum in device memory (n_distinct, spec_keys, spec_counts, hist) and ctr holds the device's counters.
 int device_spectrum(ovl_ctx* ctx, Dev* c, const char* what, const uint8_t* seqs, const int64_t* offsets,
@@ -155,19 +150,19 @@ int device_spectrum(ovl_ctx* ctx, Dev* c, const char* what, const uint8_t* seqs,
                  in_bytes = al256(o_seq + (size_t)std::max<int64_t>(total, 1));
     size_t free_b = 0, total_b = 0;
     HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
-    if (in_bytes + w.bytes > free_b + c->sp_in.bytes + c->sp_work.bytes)
+    if (in_bytes + w.bytes > free_b + c->sp.in.bytes + c->sp.work.bytes)
         return fail(c, OVL_E_UNSUPPORTED, "%s: %zu bytes of keys and tables do not fit the device (%zu free)", what,
-                    in_bytes + w.bytes, free_b + c->sp_in.bytes + c->sp_work.bytes);
+                    in_bytes + w.bytes, free_b + c->sp.in.bytes + c->sp.work.bytes);
     std::vector<int64_t> h_off(N + 1, 0), h_woff(N + 1, 0);
     for (int32_t r = 0; r < n_reads; ++r) {
         h_off[(size_t)r + 1] = offsets[r + 1] - offsets[0];
         h_woff[(size_t)r + 1] = h_woff[(size_t)r] + std::max<int64_t>(offsets[r + 1] - offsets[r] - k + 1, 0);
     }
-    HIPCHK(c, ensure(c->sp_in, in_bytes));
-    HIPCHK(c, ensure(c->sp_work, w.bytes));
-    if (ctx->timing) HIPCHK(c, ensure_events(c->sp_ev));
-    char* in = as<char>(c->sp_in);
-    char* base = as<char>(c->sp_work);
+    HIPCHK(c, ensure(c->sp.in, in_bytes));
+    HIPCHK(c, ensure(c->sp.work, w.bytes));
+    HIPCHK(c, c->sp.timer.arm(ctx->timing));
+    char* in = as<char>(c->sp.in);
+    char* base = as<char>(c->sp.work);
     StreamDrain drain(s);  // the copies read this call's vectors: drained whichever way the routine leaves
     HIPCHK(c, hipMemcpyAsync(in + o_off, h_off.data(), 8 * (N + 1), hipMemcpyHostToDevice, s));
     HIPCHK(c, hipMemcpyAsync(in + o_woff, h_woff.data(), 8 * (N + 1), hipMemcpyHostToDevice, s));
@@ -196,20 +191,25 @@ int device_spectrum(ovl_ctx* ctx, Dev* c, const char* what, const uint8_t* seqs,
     void* d_temp = base + w.temp;
     HIPCHK(c, hipMemsetAsync(g->ctr, 0, 64, s));
     HIPCHK(c, hipMemsetAsync(g->hist, 0, 4 * (size_t)kSpecHistBins, s));
-    if (ctx->timing) HIPCHK(c, hipEventRecord(c->sp_ev[0], s));
+    HIPCHK(c, c->sp.timer.mark(0, s));
     HIPCHK(c, ovl_launch_spectrum_keys(g, s));
-    if (ctx->timing) HIPCHK(c, hipEventRecord(c->sp_ev[1], s));
+    HIPCHK(c, c->sp.timer.mark(1, s));
     HIPCHK(c, ovl_launch_spectrum_sort(g, d_temp, temp, s));
-    if (ctx->timing) HIPCHK(c, hipEventRecord(c->sp_ev[2], s));
+    HIPCHK(c, c->sp.timer.mark(2, s));
     HIPCHK(c, ovl_launch_spectrum_heads(g, d_temp, temp, s));
     HIPCHK(c, hipMemcpyAsync(ctr, g->ctr, 64, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     if ((int64_t)ctr[0] > n_win) return fail(c, OVL_E_INTERNAL, "%s: %llu distinct keys from %lld windows", what, ctr[0], (long long)n_win);
     g->n_distinct = (int32_t)ctr[0];
     HIPCHK(c, ovl_launch_spectrum_counts(g, s));
-    if (ctx->timing) HIPCHK(c, hipEventRecord(c->sp_ev[3], s));
+    HIPCHK(c, c->sp.timer.mark(3, s));
     HIPCHK(c, hipMemcpyAsync(ctr, g->ctr, 64, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
+    // the key, sort and count passes' times (the count pass's includes the host's wait for the number of distinct
+    // keys); ovl_last_timing has them from here, so that a call refused further on still reports them
+    double* ms = c->sp.last.ms;
+    for (int i = 0; i < 3; ++i) ms[i] = c->sp.timer.ms(i, i + 1);
+    ctx->t_kernel_ms = ms[0] + ms[1] + ms[2];
     return OVL_OK;
 }
 
@@ -219,16 +219,6 @@ int device_limits(Dev* c, const char* what, const int64_t* offsets, int32_t k, i
                     (long long)(offsets[long_read + 1] - offsets[long_read]), kSpecMaxWindows - 1);
     if (n_win >= kSpecMax) return fail(c, OVL_E_UNSUPPORTED, "%s: fewer than 2^31 windows required", what);
     return OVL_OK;
-}
-
-// the key, sort and count passes' times (the count pass's includes the host's wait for the number of distinct keys)
-void read_times(ovl_ctx* ctx, Dev* c) {
-    float ms = 0.f;
-    for (int i = 0; i < 3; ++i)
-        if (hipEventElapsedTime(&ms, c->sp_ev[i], c->sp_ev[i + 1]) == hipSuccess) {
-            ctx->x_sp_ms[i] = ms;
-            ctx->t_kernel_ms += ms;
-        }
 }
 
 }  // namespace
@@ -333,10 +323,8 @@ OVL_API int ovl_correct_reads_host(const uint8_t* seqs, const int64_t* offsets, 
 OVL_API int ovl_kmer_spectrum(ovl_ctx* ctx, const uint8_t* seqs, const int64_t* offsets, int32_t n_reads, int32_t k,
                               uint64_t* out_keys, int32_t* out_counts, int64_t capacity, int64_t* out_n_distinct) {
     if (!ctx) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
-    quiet(ctx);
-    Dev* c = ctx->devs[0];
-    DeviceGuard guard;
-    const auto t_call = std::chrono::steady_clock::now();
+    StageCall call(ctx);
+    Dev* c = call.dev;
     int64_t n_win = 0;
     int32_t max_win = 0, long_read = -1;
     int rc = check_reads(c, "kmer_spectrum", seqs, offsets, n_reads, k, &n_win, &max_win, &long_read);
@@ -346,13 +334,13 @@ OVL_API int ovl_kmer_spectrum(ovl_ctx* ctx, const uint8_t* seqs, const int64_t* 
         return fail(c, OVL_E_ARG, "kmer_spectrum: capacity %lld without output arrays", (long long)capacity);
     if ((rc = device_limits(c, "kmer_spectrum", offsets, k, n_win, long_read)) != OVL_OK) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    reset_stats(ctx);
+    call.begin();
+    c->sp.last = {};
     OvlSpectrumArgs g;
     unsigned long long ctr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if ((rc = device_spectrum(ctx, c, "kmer_spectrum", seqs, offsets, n_reads, k, n_win, max_win, false, &g, ctr)) !=
         OVL_OK)
         return rc;
-    if (ctx->timing) read_times(ctx, c);
     *out_n_distinct = g.n_distinct;
     if (g.n_distinct > capacity)
         return fail(c, OVL_E_RANGE, "kmer_spectrum: %d distinct keys, capacity %lld", g.n_distinct, (long long)capacity);
@@ -360,17 +348,14 @@ OVL_API int ovl_kmer_spectrum(ovl_ctx* ctx, const uint8_t* seqs, const int64_t* 
         HIPCHK(c, hipMemcpy(out_keys, g.spec_keys, 8 * (size_t)g.n_distinct, hipMemcpyDeviceToHost));
         HIPCHK(c, hipMemcpy(out_counts, g.spec_counts, 4 * (size_t)g.n_distinct, hipMemcpyDeviceToHost));
     }
-    ctx->t_call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
-    return OVL_OK;
+    return call.done(ctx->t_kernel_ms);  // (device_spectrum's passes)
 }
 
 OVL_API int ovl_correct_reads(ovl_ctx* ctx, const uint8_t* seqs, const int64_t* offsets, int32_t n_reads, int32_t k,
                               int32_t min_count, uint8_t* out_seqs, int32_t* out_changed, int64_t* out_stats) {
     if (!ctx) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
-    quiet(ctx);
-    Dev* c = ctx->devs[0];
-    DeviceGuard guard;
-    const auto t_call = std::chrono::steady_clock::now();
+    StageCall call(ctx);
+    Dev* c = call.dev;
     int64_t n_win = 0;
     int32_t max_win = 0, long_read = -1;
     int rc = check_reads(c, "correct_reads", seqs, offsets, n_reads, k, &n_win, &max_win, &long_read);
@@ -382,13 +367,13 @@ OVL_API int ovl_correct_reads(ovl_ctx* ctx, const uint8_t* seqs, const int64_t* 
     if (total > 0 && !out_seqs) return fail(c, OVL_E_ARG, "correct_reads: out_seqs is NULL");
     if ((rc = device_limits(c, "correct_reads", offsets, k, n_win, long_read)) != OVL_OK) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    reset_stats(ctx);
+    call.begin();
+    c->sp.last = {};
     OvlSpectrumArgs g;
     unsigned long long ctr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if ((rc = device_spectrum(ctx, c, "correct_reads", seqs, offsets, n_reads, k, n_win, max_win, true, &g, ctr)) !=
         OVL_OK)
         return rc;
-    if (ctx->timing) read_times(ctx, c);
     hipStream_t s = c->stream;
     if (min_count == 0) {  // the threshold rule, from the device's histogram where that is exact
         std::vector<uint32_t> hist((size_t)kSpecHistBins, 0);
@@ -405,18 +390,14 @@ OVL_API int ovl_correct_reads(ovl_ctx* ctx, const uint8_t* seqs, const int64_t* 
         StreamDrain drain(s);
         HIPCHK(c, hipMemcpyAsync(g.out, g.seqs, (size_t)total, hipMemcpyDeviceToDevice, s));
         HIPCHK(c, hipMemsetAsync(g.changed, 0, 4 * (size_t)n_reads, s));
-        if (ctx->timing) HIPCHK(c, hipEventRecord(c->sp_ev[4], s));
+        HIPCHK(c, c->sp.timer.mark(4, s));
         HIPCHK(c, ovl_launch_spectrum_correct(&g, c->cu_count * 8, s));
-        if (ctx->timing) HIPCHK(c, hipEventRecord(c->sp_ev[5], s));
+        HIPCHK(c, c->sp.timer.mark(5, s));
         HIPCHK(c, hipMemcpyAsync(ctr, g.ctr, 64, hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipMemcpyAsync(out_seqs + offsets[0], g.out, (size_t)total, hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipMemcpyAsync(out_changed, g.changed, 4 * (size_t)n_reads, hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipStreamSynchronize(s));
-        float ms = 0.f;
-        if (ctx->timing && hipEventElapsedTime(&ms, c->sp_ev[4], c->sp_ev[5]) == hipSuccess) {
-            ctx->x_sp_ms[3] = ms;
-            ctx->t_kernel_ms += ms;
-        }
+        c->sp.last.ms[3] = c->sp.timer.ms(4, 5);
     } else {  // no read has a window: nothing to decide
         if (total > 0) memmove(out_seqs + offsets[0], seqs + offsets[0], (size_t)total);
         for (int32_t r = 0; r < n_reads; ++r) out_changed[r] = 0;
@@ -424,16 +405,16 @@ OVL_API int ovl_correct_reads(ovl_ctx* ctx, const uint8_t* seqs, const int64_t* 
     const int64_t st[8] = {(int64_t)ctr[7], g.n_distinct, (int64_t)ctr[2], (int64_t)ctr[3], (int64_t)ctr[4],
                            (int64_t)ctr[5], min_count, n_win};
     std::copy(st, st + 8, out_stats);
-    ctx->t_call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
-    return OVL_OK;
+    return call.done(ctx->t_kernel_ms + c->sp.last.ms[3]);  // (the spectrum's passes and the correction)
 }
 
 OVL_API int ovl_last_correct_timing(const ovl_ctx* ctx, double* keys_ms, double* sort_ms, double* count_ms,
                                     double* correct_ms) {
     if (!ctx) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
-    if (keys_ms) *keys_ms = ctx->x_sp_ms[0];
-    if (sort_ms) *sort_ms = ctx->x_sp_ms[1];
-    if (count_ms) *count_ms = ctx->x_sp_ms[2];
-    if (correct_ms) *correct_ms = ctx->x_sp_ms[3];
+    const double* ms = ctx->devs[0]->sp.last.ms;
+    if (keys_ms) *keys_ms = ms[0];
+    if (sort_ms) *sort_ms = ms[1];
+    if (count_ms) *count_ms = ms[2];
+    if (correct_ms) *correct_ms = ms[3];
     return OVL_OK;
 }

@@ -138,3 +138,39 @@ def test_pipeline_with_polish_equals_its_host_route(engine):
     assert (pile.rounds, pile.total_changed, pile.n_changed) == (ref["rounds"], ref["total_changed"], ref["n_changed"])
     assert np.array_equal(np.concatenate(pile.counts), ref["counts"]) and np.array_equal(pile.aln, ref["aln"])
     assert pile.total_changed > 0 and engine.last_consensus_placed()["voted_reads"] > 1900
+
+
+def test_timing_reports_the_band_and_the_vote(engine, host_results):
+    """The smallest case that runs two rounds (eight reads of 20 bases): band_ms and vote_ms are summed over the
+    rounds, and kernel_ms is their sum."""
+    from stage_timing import timed_and_untimed
+    case = BY_NAME["rounds_2"]
+    a, kw = native_args(case, rounds=2)
+    got_on, on, got_off, off = timed_and_untimed(engine, lambda: engine.consensus_placed(*a, **kw),
+                                                 engine.last_consensus_placed)
+    assert on["band_ms"] > 0.0 and on["vote_ms"] > 0.0, on
+    assert abs(on["kernel_ms"] - (on["band_ms"] + on["vote_ms"])) <= 1e-6 and on["kernel_ms"] <= on["call_ms"], on
+    assert off["band_ms"] == off["vote_ms"] == off["kernel_ms"] == 0.0 and off["call_ms"] > 0.0, off
+    want = host_results[case.name]
+    assert want["rounds"] == on["rounds"] == 2
+    assert_same(got_on, want, "timing on")
+    assert_same(got_off, want, "timing off")
+
+
+def test_timer_made_by_a_later_call_and_used_again(host_results):
+    """A fresh engine whose first call has timing off makes its events only when timing is turned on, and the next
+    timed call uses them again: both report every phase, and all three calls give the same result."""
+    from ovlgraph import OverlapEngine
+    case = BY_NAME["rounds_2"]
+    a, kw = native_args(case)
+    with OverlapEngine(0) as eng:
+        first = eng.consensus_placed(*a, **kw)
+        assert eng.last_consensus_placed()["band_ms"] == 0.0
+        eng.set_timing(True)
+        for what in ("first timed call", "second timed call"):
+            got = eng.consensus_placed(*a, **kw)
+            last = eng.last_consensus_placed()
+            assert last["band_ms"] > 0.0 and last["vote_ms"] > 0.0, (what, last)
+            assert last["rounds"] == 2
+            assert_same(got, first, what)
+    assert_same(first, host_results[case.name], "timing off")

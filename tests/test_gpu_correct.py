@@ -170,3 +170,21 @@ def test_assembly_of_device_corrected_reads_equals_host_corrected(engine):
     assert assemble_contigs_best_successor(dev, k=12, engine=engine) == \
         assemble_contigs_best_successor(host, k=12, engine=engine)
     assert engine.correct_reads(reads, 12)[2]["changed"] > 0  # the engine's thin wrapper, threshold by the rule
+
+
+def test_timing_of_the_two_entry_points(engine):
+    """A dozen 40-base reads, k = 8 (every read has windows): ovl_correct_reads times four parts that add up to
+    kernel_ms, ovl_kmer_spectrum the first three, and with timing off all are zero."""
+    from stage_timing import timed_and_untimed
+    reads = small_quality_reads()[0][:12]
+    parts = ("keys_ms", "sort_ms", "count_ms", "correct_ms")
+    got_on, on, got_off, off = timed_and_untimed(engine, lambda: engine.correct_reads(reads, 8), engine.last_correct)
+    assert all(on[p] > 0.0 for p in parts), on
+    assert abs(on["kernel_ms"] - sum(on[p] for p in parts)) <= 1e-6 and on["kernel_ms"] <= on["call_ms"], on
+    assert all(off[p] == 0.0 for p in parts) and off["kernel_ms"] == 0.0 and off["call_ms"] > 0.0, off
+    assert np.array_equal(got_on[0], got_off[0]) and np.array_equal(got_on[1], got_off[1]) and got_on[2] == got_off[2]
+    sp_on, on, sp_off, off = timed_and_untimed(engine, lambda: engine.kmer_spectrum(reads, 8), engine.last_correct)
+    assert on["correct_ms"] == 0.0 and all(on[p] > 0.0 for p in parts[:3]), on
+    assert abs(on["kernel_ms"] - sum(on[p] for p in parts)) <= 1e-6, on
+    assert all(off[p] == 0.0 for p in parts) and off["kernel_ms"] == 0.0, off
+    assert np.array_equal(sp_on[0], sp_off[0]) and np.array_equal(sp_on[1], sp_off[1])

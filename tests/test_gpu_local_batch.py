@@ -275,3 +275,19 @@ def test_batch_errors_write_nothing(engine):
         engine.local_align_batch(queries, ref, [(0, 50), (0, 50), (30, 21)])
     # the context still works
     assert engine.local_align_batch(queries, ref, windows)[0].tolist() == [0, 80, 100]
+
+
+def test_timing_covers_the_batch_kernel(engine, genome):
+    """Four 50-base queries against a 300-base reference: all take the batch kernel."""
+    from stage_timing import assert_kernel_inside_call, timed_and_untimed
+    rng = random.Random(4)
+    ref = genome[1000:1300]
+    queries = [_mutated(rng, ref[lo:lo + 50], 50) for lo in (0, 70, 140, 250)]
+    got_on, on, got_off, off = timed_and_untimed(engine, lambda: engine.local_align_batch(queries, ref),
+                                                 engine.last_local_batch)
+    assert on["batched"] == off["batched"] == 4 and on["single"] == 0
+    assert_kernel_inside_call(on, off)
+    for x, y in zip(got_on[:5], got_off[:5]):
+        assert np.array_equal(x, y)
+    assert all(np.array_equal(x, y) for x, y in zip(got_on[5], got_off[5])) and len(got_on[5]) == 4
+    assert (got_on[0] > 0).all()

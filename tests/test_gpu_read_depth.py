@@ -246,3 +246,19 @@ def test_argument_errors_leave_the_outputs_alone(engine):
     res = engine.read_best(["ACGT"], [], 4)
     assert res["first_best"].tolist() == [-1] and res["best_score"].tolist() == [0]
     assert engine.read_best([], ["ACGT"], 4)["best_score"].shape == (0,)
+
+
+def test_timing_covers_the_score_pass(engine):
+    """Eight 32-base reads against three contigs of about 100 bases at the default scoring: the lane kernel takes them
+    all, and kernel_ms is its launches and folds."""
+    from ovlgraph.reads import read_genome_from_fasta
+    from stage_timing import assert_kernel_inside_call, timed_and_untimed
+    genome = read_genome_from_fasta()
+    contigs = [genome[0:100], genome[80:185], genome[150:248]]
+    reads = [genome[lo:lo + 32] for lo in (0, 20, 60, 85, 110, 150, 190, 215)]
+    got_on, on, got_off, off = timed_and_untimed(engine, lambda: engine.read_best(reads, contigs, 32),
+                                                 engine.last_read_best)
+    assert on["lane_pairs"] == off["lane_pairs"] == 8 * 3 and on["launches"] == 1
+    assert_kernel_inside_call(on, off)
+    for k in got_on:
+        assert np.array_equal(got_on[k], got_off[k]), k

@@ -184,3 +184,16 @@ def test_error_codes_leave_reduced_untouched(engine):
         rc = L.ovl_transitive_reduce(engine._ctx, p(o), p(h), p(w), 3, p(reduced), ctypes.byref(n))
         assert rc == want and n.value == -7 and reduced.tolist() == [9, 9, 9]
     assert engine.transitive_reduce(off, heads, weights).tolist() == [0, 1, 0]
+
+
+def test_timing_covers_the_reduction_kernel(engine):
+    """Four nodes, one two-hop path (0 -> 1 -> 2) beside the edge it removes."""
+    from ovlgraph.engine import transitive_reduce_host
+    from stage_timing import assert_kernel_inside_call, timed_and_untimed
+    off, heads, weights = [0, 2, 3, 4, 4], [1, 2, 2, 3], [3, 5, 4, 1]
+    got_on, on, got_off, off_t = timed_and_untimed(engine, lambda: engine.transitive_reduce(off, heads, weights),
+                                                   engine.last_transitive)
+    assert on["two_hop_steps"] == 3
+    assert_kernel_inside_call(on, off_t)
+    want = transitive_reduce_host(off, heads, weights)
+    assert want.sum() >= 1 and np.array_equal(got_on, want) and np.array_equal(got_off, want)

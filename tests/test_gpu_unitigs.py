@@ -211,3 +211,15 @@ def test_buffers_reused_across_sizes(engine, family_graphs):
         got, closure = engine.reach_reduce(off, heads, closure=True)
         assert np.array_equal(got, want) and np.array_equal(closure, want_closure), small
         assert_padding_is_zero(closure, off.shape[0] - 1)
+
+
+def test_timing_covers_a_calls_launches(engine):
+    """Four nodes, one removable edge: 0 -> 2 goes, since 0's earlier successor 1 reaches 2."""
+    from ovlgraph.engine import reach_reduce_host
+    from stage_timing import assert_kernel_inside_call, timed_and_untimed
+    off, heads = [0, 2, 3, 4, 4], [1, 2, 2, 3]
+    got_on, on, got_off, off_t = timed_and_untimed(engine, lambda: engine.reach_reduce(off, heads), engine.last_reach)
+    assert on["words_per_row"] == 1
+    assert_kernel_inside_call(on, off_t)
+    want = reach_reduce_host(off, heads)
+    assert want.tolist() == [0, 1, 0, 0] and np.array_equal(got_on, want) and np.array_equal(got_off, want)
