@@ -3,11 +3,9 @@
 The library is built in-tree by ``csrc/Makefile`` (``__graft_entry__.build()``)
 into ``genome-assembly-using-overlap-graphs_amd/build/libovl.so``.  There is no
 CPU fallback: if the library is missing or no GPU is visible the engine
-raises ``OvlError`` (the host forms -- ``ovl_remove_cycles``, ``ovl_transitive_reduce_host``,
-``ovl_reach_reduce_host``, ``ovl_read_best_host``, ``ovl_consensus_host``, ``ovl_consensus_placed_host``,
-``ovl_layout_host``, ``ovl_kmer_spectrum_host``, ``ovl_correct_reads_host`` -- need neither a
-context nor a GPU).  ctypes
-releases the GIL for the duration of each call.
+raises ``OvlError`` (the host forms -- ``ovl_remove_cycles`` and the ``*_host`` functions of
+``stages.py`` -- need neither a context nor a GPU).  ctypes releases the GIL for the
+duration of each call.
 """
 from __future__ import annotations
 
@@ -36,6 +34,7 @@ _i32 = ctypes.c_int32
 _i64 = ctypes.c_int64
 _pi32 = ctypes.POINTER(ctypes.c_int32)
 _pi64 = ctypes.POINTER(ctypes.c_int64)
+_pf64 = ctypes.POINTER(ctypes.c_double)
 SIGNATURES = {
     "ovl_version": (ctypes.c_int, []),
     "ovl_device_count": (ctypes.c_int, [_pi32]),
@@ -50,12 +49,11 @@ SIGNATURES = {
     "ovl_host_pool": (ctypes.c_int, [_pi32, _pi32, _pi32, _pi32]),
     "ovl_host_pool_rule": (ctypes.c_int32, [_i32, _i32, _i32]),
     "ovl_set_timing": (ctypes.c_int, [_P, _i32]),
-    "ovl_last_timing": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
+    "ovl_last_timing": (ctypes.c_int, [_P, _pf64, _pf64]),
     "ovl_last_launches": (ctypes.c_int, [_P, _i32, _P, _P, _P, _P, _pi32]),
-    "ovl_last_transfer": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
-    "ovl_last_pair_list": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
-    "ovl_last_results": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
-                                        ctypes.POINTER(ctypes.c_int64)]),
+    "ovl_last_transfer": (ctypes.c_int, [_P, _pi64, _pi64]),
+    "ovl_last_pair_list": (ctypes.c_int, [_P, _pi64, _pi64]),
+    "ovl_last_results": (ctypes.c_int, [_P, _pi64, _pi64, _pi64]),
     "ovl_last_error": (ctypes.c_char_p, [_P]),
     "ovl_score_pairs": (ctypes.c_int, [_P, _P, _P, _i32, _P, _P, _i64, _i32, _i32, _i64, _i32, _P, _P]),
     "ovl_set_reads": (ctypes.c_int, [_P, _P, _P, _i32]),
@@ -69,7 +67,7 @@ SIGNATURES = {
     "ovl_candidates": (ctypes.c_int, [_P, _i32, _pi64]),
     "ovl_seed_candidates": (ctypes.c_int, [_P, _i32, _pi64]),
     "ovl_seed_offsets_copy": (ctypes.c_int, [_P, _P]),
-    "ovl_last_seed_timing": (ctypes.c_int, [_P] + [ctypes.POINTER(ctypes.c_double)] * 4),
+    "ovl_last_seed_timing": (ctypes.c_int, [_P] + [_pf64] * 4),
     "ovl_candidates_copy": (ctypes.c_int, [_P, _P, _P]),
     "ovl_candidates_device": (ctypes.c_int, [_P, ctypes.POINTER(_P), ctypes.POINTER(_P), _pi64]),
     "ovl_score_candidates": (ctypes.c_int, [_P, _i32, _i32, _i64, _i32, _P, _P]),
@@ -101,15 +99,13 @@ SIGNATURES = {
     "ovl_consensus_host": (ctypes.c_int, [_P, _P, _i32, _P, _P, _i32, _P, _i32, _i32, _i32, _i64, _i32, _P, _P, _pi64,
                                           _pi64, _P]),
     "ovl_last_consensus": (ctypes.c_int, [_P, _pi64, _pi64, _pi64, _pi32]),
-    "ovl_last_consensus_timing": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double),
-                                                 ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
+    "ovl_last_consensus_timing": (ctypes.c_int, [_P, _pf64, _pf64, _pf64]),
     "ovl_consensus_placed": (ctypes.c_int, [_P, _P, _P, _i32, _P, _P, _P, _i32, _P, _P, _i32, _i32, _i32, _i64, _i32,
                                             _i32, _i32, _P, _P, _pi64, _pi64, _pi64, _pi32, _P]),
     "ovl_consensus_placed_host": (ctypes.c_int, [_P, _P, _i32, _P, _P, _P, _i32, _P, _P, _i32, _i32, _i32, _i64, _i32,
                                                  _i32, _i32, _P, _P, _pi64, _pi64, _pi64, _pi32, _P]),
     "ovl_last_consensus_placed": (ctypes.c_int, [_P, _pi64, _pi64, _pi64, _pi32, _pi32]),
-    "ovl_last_consensus_placed_timing": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double),
-                                                        ctypes.POINTER(ctypes.c_double)]),
+    "ovl_last_consensus_placed_timing": (ctypes.c_int, [_P, _pf64, _pf64]),
     "ovl_layout_host": (ctypes.c_int, [_P, _P, _i32, _P, _P, _P, _P, _i64, _i32, _i32, _P, _P, _P, _P, _P, _P, _P,
                                        _pi32]),
     "ovl_layout": (ctypes.c_int, [_P, _P, _P, _i32, _P, _P, _P, _P, _i64, _i32, _i32, _P, _P, _P, _P, _P, _P, _P,
@@ -117,12 +113,12 @@ SIGNATURES = {
     "ovl_layout_candidates": (ctypes.c_int, [_P, _i32, _i32, _i64, _i32, _i32, _i32, _P, _P, _P, _P, _P, _P, _P,
                                              _pi32]),
     "ovl_last_layout": (ctypes.c_int, [_P, _pi64, _pi64, _pi32, _pi64]),
-    "ovl_last_layout_timing": (ctypes.c_int, [_P] + [ctypes.POINTER(ctypes.c_double)] * 4),
+    "ovl_last_layout_timing": (ctypes.c_int, [_P] + [_pf64] * 4),
     "ovl_kmer_spectrum_host": (ctypes.c_int, [_P, _P, _i32, _i32, _P, _P, _i64, _pi64]),
     "ovl_correct_reads_host": (ctypes.c_int, [_P, _P, _i32, _i32, _i32, _P, _P, _P]),
     "ovl_kmer_spectrum": (ctypes.c_int, [_P, _P, _P, _i32, _i32, _P, _P, _i64, _pi64]),
     "ovl_correct_reads": (ctypes.c_int, [_P, _P, _P, _i32, _i32, _i32, _P, _P, _P]),
-    "ovl_last_correct_timing": (ctypes.c_int, [_P] + [ctypes.POINTER(ctypes.c_double)] * 4),
+    "ovl_last_correct_timing": (ctypes.c_int, [_P] + [_pf64] * 4),
 }
 
 
@@ -193,3 +189,20 @@ def last_error(ctx=None) -> str:
 def check(rc: int, ctx=None) -> None:
     if rc != OVL_OK:
         raise OvlError(rc, last_error(ctx))
+
+
+def _ptr(a) -> ctypes.c_void_p:
+    """The data pointer of a numpy array."""
+    return ctypes.c_void_p(a.ctypes.data)
+
+
+def read_out(fn, *head, ctx=None) -> tuple:
+    """Call ``fn(*head, &x0, &x1, ...)``, a scalar ``x`` per argument type left in ``fn.argtypes`` (each a POINTER to
+    a simple type, as ``SIGNATURES`` spells it), and return the values: ``int`` for c_int32 / c_int64, ``float`` for
+    c_double.  Errors are read from ``ctx``."""
+    types = fn.argtypes[len(head):]
+    if not all(issubclass(t, ctypes._Pointer) and issubclass(t._type_, ctypes._SimpleCData) for t in types):
+        raise TypeError(f"{fn.__name__}: the arguments after the first {len(head)} are not all pointers to scalars")
+    outs = [t._type_() for t in types]
+    check(fn(*head, *[ctypes.byref(x) for x in outs]), ctx)
+    return tuple(x.value for x in outs)

@@ -89,12 +89,10 @@ def _window_len(L: int, m: int, read_length: int) -> int:
 
 def _place(contigs, reads, read_length, scoring, engine, device):
     """first_best of read_best / read_best_host, chosen as ``read_depth`` chooses."""
-    from .engine import default_engine, device_count, read_best_host
+    from .engine import default_engine, read_best_host, use_device
     from .performanceMeasures import READ_DEPTH_DEVICE_MIN_CELLS
-    if device is None:
-        cells = sum(len(r) for r in reads) * sum(len(c) for c in contigs)
-        device = cells >= READ_DEPTH_DEVICE_MIN_CELLS and (engine is not None or device_count() > 0)
-    if device:
+    if use_device(device, lambda: sum(len(r) for r in reads) * sum(len(c) for c in contigs),
+                  READ_DEPTH_DEVICE_MIN_CELLS, engine):
         res = (engine or default_engine()).read_best(reads, contigs, read_length, *scoring)
     else:
         res = read_best_host(reads, contigs, read_length, *scoring)
@@ -109,7 +107,7 @@ def pileup(contigs, reads, read_length, place=None, depth=None, min_depth=3, mat
     ``depth.chosen`` when a ``ReadDepth`` is given, else ``first_best`` of ``read_best`` (on the device or the host by
     ``read_depth``'s rule).  ``device=None`` takes the host form when no GPU is visible or the placed reads hold
     fewer than ``CONSENSUS_DEVICE_MIN_CELLS`` cells; True / False force the choice."""
-    from .engine import consensus_host, default_engine, device_count
+    from .engine import consensus_host, default_engine, use_device
     contigs, reads = list(contigs), list(reads)
     scoring = (match_score, mismatch, indel)
     if place is None:
@@ -117,12 +115,11 @@ def pileup(contigs, reads, read_length, place=None, depth=None, min_depth=3, mat
     place = np.ascontiguousarray(place, dtype=np.int32)
     if place.shape != (len(reads),):
         raise OvlError(-1, "place must hold one contig position (or -1) per read")
-    if device is None:
-        C = len(contigs)
-        cells = sum(len(r) * _window_len(len(r), len(contigs[p]), read_length)
-                    for r, p in zip(reads, place.tolist()) if 0 <= p < C)
-        device = cells >= CONSENSUS_DEVICE_MIN_CELLS and (engine is not None or device_count() > 0)
-    if device:
+
+    def cells():
+        return sum(len(r) * _window_len(len(r), len(contigs[p]), read_length)
+                   for r, p in zip(reads, place.tolist()) if 0 <= p < len(contigs))
+    if use_device(device, cells, CONSENSUS_DEVICE_MIN_CELLS, engine):
         res = (engine or default_engine()).consensus(reads, contigs, place, read_length, *scoring, min_depth)
     else:
         res = consensus_host(reads, contigs, place, read_length, *scoring, min_depth)
@@ -182,16 +179,15 @@ def pileup_placed(contigs, reads, contig, offset, slack=8, weights=None, rounds=
     ``device=None`` takes the host form when no GPU is visible, when ``slack > 15`` or when the band cells, the sum of
     read length x (2 * slack + 1), are fewer than ``CONSENSUS_PLACED_DEVICE_MIN_CELLS``; True / False force the
     choice."""
-    from .engine import consensus_placed_host, default_engine, device_count
+    from .engine import consensus_placed_host, default_engine, use_device
     contigs, reads = list(contigs), list(reads)
     contig = np.ascontiguousarray(contig, dtype=np.int32)
     offset = np.ascontiguousarray(offset, dtype=np.int32)
     if contig.shape != (len(reads),) or offset.shape != (len(reads),):
         raise OvlError(-1, "contig and offset must hold one int32 per read")
     if device is None:
-        cells = sum(len(r) for r in reads) * (2 * slack + 1)
-        device = (slack <= CONSENSUS_PLACED_MAX_DEVICE_SLACK and cells >= CONSENSUS_PLACED_DEVICE_MIN_CELLS
-                  and (engine is not None or device_count() > 0))
+        device = slack <= CONSENSUS_PLACED_MAX_DEVICE_SLACK and use_device(
+            None, lambda: sum(len(r) for r in reads) * (2 * slack + 1), CONSENSUS_PLACED_DEVICE_MIN_CELLS, engine)
     args = (reads, contigs, contig, offset, slack, weights, rounds, min_depth, min_vote_score, match_score, mismatch,
             indel)
     res = (engine or default_engine()).consensus_placed(*args) if device else consensus_placed_host(*args)

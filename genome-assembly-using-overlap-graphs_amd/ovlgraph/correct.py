@@ -152,12 +152,10 @@ def _windows(offs: np.ndarray, k: int) -> int:
 
 
 def _use_device(form: str, engine, windows: int) -> bool:
-    from .engine import device_count
+    from .engine import use_device
     if form not in FORMS:
         raise ValueError(f"form must be one of {FORMS}")
-    if form == "auto":
-        return windows >= CORRECT_DEVICE_MIN_WINDOWS and (engine is not None or device_count() > 0)
-    return form == "device"
+    return use_device({"auto": None, "device": True}.get(form, False), windows, CORRECT_DEVICE_MIN_WINDOWS, engine)
 
 
 def kmer_spectrum(reads: Sequence[str], k: int, engine=None, form: str = "auto") -> Tuple[np.ndarray, np.ndarray]:

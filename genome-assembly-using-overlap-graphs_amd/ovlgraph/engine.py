@@ -7,6 +7,11 @@ per-pair Python->Numba call of overlapGraphs.py:53.  A multi-GPU engine
 call over its GPUs from this one thread.  Results come back in
 pinned host arrays (``hostmem.PinnedPool``) unless ``out=`` is given.  It never
 computes on the CPU: a missing library or GPU raises ``OvlError``.
+
+The stages that also have a host form (the graph reductions, read depth, consensus,
+layout, read correction) are marshalled in ``stages.py``; the engine's methods of those
+names are the device form of the same call.  ``use_device`` is the one rule by which
+the package's entry points choose between the two forms.
 """
 from __future__ import annotations
 
@@ -19,8 +24,14 @@ from typing import Dict, List, Optional, Sequence, Tuple, Union
 import numpy as np
 
 from . import _lib
-from ._lib import OvlError, check
+from ._lib import OvlError, _ptr, check, read_out
 from .hostmem import pinned_empty
+# (the stage names are also this module's: callers import the host forms and encode_reads from here)
+from .stages import (CORRECT_STATS, LAYOUT_COUNTS, _consensus_call, _correct_call, _layout_call,  # noqa: F401
+                     _layout_outputs, _layout_result, _placed_call, _reach_call, _read_best_call, _spectrum_call,
+                     _transitive_call, consensus_host, consensus_placed_host, correct_reads_host, encode_reads,
+                     kmer_spectrum_host, last_layout_host, layout_host, reach_reduce_host, read_best_host,
+                     transitive_reduce_host)
 
 INDEL_DEFAULT = -(2 ** 31)  # aligners.py:7 default indel (the report's "-inf", REPORT p.3)
 
@@ -36,38 +47,6 @@ def quiesce_all() -> None:
             eng.quiesce()
 
 
-def encode_reads(reads: Sequence[str]) -> Tuple[np.ndarray, np.ndarray]:
-    """Concatenate reads into one byte buffer + int64 offsets.
-
-    Bytes are symbols compared for equality only, so any injective
-    character->byte map preserves the reference's ``s[i-1] == t[j-1]`` test
-    (aligners.py:35).  Latin-1 covers every str whose characters are < 256;
-    otherwise up to 256 distinct characters are renumbered.
-    """
-    n = len(reads)
-    offs = np.zeros(n + 1, dtype=np.int64)
-    if n:
-        np.cumsum(np.fromiter((len(r) for r in reads), dtype=np.int64, count=n), out=offs[1:])
-    joined = "".join(reads)
-    try:
-        buf = np.frombuffer(joined.encode("latin-1"), dtype=np.uint8)
-    except UnicodeEncodeError:
-        table: Dict[str, int] = {}
-        for ch in joined:
-            if ch not in table:
-                if len(table) >= 256:
-                    raise OvlError(-4, "more than 256 distinct symbols in the read set")
-                table[ch] = len(table)
-        buf = np.fromiter((table[ch] for ch in joined), dtype=np.uint8, count=len(joined))
-    if buf.size == 0:
-        buf = np.zeros(1, dtype=np.uint8)
-    return np.ascontiguousarray(buf), offs
-
-
-def _ptr(a: np.ndarray) -> ctypes.c_void_p:
-    return ctypes.c_void_p(a.ctypes.data)
-
-
 def _outputs(n: int, out) -> Tuple[np.ndarray, np.ndarray]:
     """Result arrays: the caller's ``out=(score, end)`` (int32, contiguous, >= n) or pinned ones."""
     if out is None:
@@ -80,255 +59,36 @@ def _outputs(n: int, out) -> Tuple[np.ndarray, np.ndarray]:
     return sc[:n], en[:n]
 
 
-def _csr_arrays(off, heads, weights) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-    """A CSR graph as the contiguous (int64 off, int32 heads, int64 weights) the C ABI takes."""
-    off = np.ascontiguousarray(off, dtype=np.int64)
-    heads = np.ascontiguousarray(heads, dtype=np.int32)
-    weights = np.ascontiguousarray(weights, dtype=np.int64)
-    if off.ndim != 1 or off.shape[0] < 1 or heads.ndim != 1 or heads.shape != weights.shape:
-        raise OvlError(-1, "CSR graph: off needs n_nodes + 1 entries, heads and weights one entry per edge")
-    if int(off[-1]) > heads.shape[0]:
-        raise OvlError(-1, f"CSR graph: off[-1] = {int(off[-1])} exceeds the {heads.shape[0]} edges given")
-    return off, heads, weights
-
-
-def transitive_reduce_host(off, heads, weights) -> np.ndarray:
-    """``OverlapEngine.transitive_reduce`` by the library's host loop (ovl_transitive_reduce_host): no context,
-    no GPU."""
-    off, heads, weights = _csr_arrays(off, heads, weights)
-    reduced = np.zeros(max(heads.shape[0], 1), dtype=np.uint8)
-    n_reduced = ctypes.c_int64(0)
-    check(_lib.load().ovl_transitive_reduce_host(_ptr(off), _ptr(heads), _ptr(weights), off.shape[0] - 1,
-                                                 _ptr(reduced), ctypes.byref(n_reduced)))
-    return reduced[:heads.shape[0]]
-
-
-def _reach_arrays(off, heads, closure: bool):
-    """A weightless CSR graph as the C ABI takes it, with the mask and (``closure``) the n x ceil(n / 64) uint64
-    matrix to receive the results."""
-    off = np.ascontiguousarray(off, dtype=np.int64)
-    heads = np.ascontiguousarray(heads, dtype=np.int32)
-    if off.ndim != 1 or off.shape[0] < 1 or heads.ndim != 1:
-        raise OvlError(-1, "CSR graph: off needs n_nodes + 1 entries, heads one entry per edge")
-    if int(off[-1]) > heads.shape[0]:
-        raise OvlError(-1, f"CSR graph: off[-1] = {int(off[-1])} exceeds the {heads.shape[0]} edges given")
-    n = off.shape[0] - 1
-    reduced = np.zeros(max(heads.shape[0], 1), dtype=np.uint8)
-    matrix = np.zeros((n, (n + 63) // 64), dtype=np.uint64) if closure else None
-    return off, heads, reduced, matrix
-
-
-def reach_reduce_host(off, heads, closure: bool = False):
-    """``OverlapEngine.reach_reduce`` on one host thread (ovl_reach_reduce_host): no context, no GPU."""
-    off, heads, reduced, matrix = _reach_arrays(off, heads, closure)
-    n_reduced = ctypes.c_int64(0)
-    check(_lib.load().ovl_reach_reduce_host(_ptr(off), _ptr(heads), off.shape[0] - 1, _ptr(reduced),
-                                            ctypes.byref(n_reduced), _ptr(matrix) if closure else None))
-    mask = reduced[:heads.shape[0]]
-    return (mask, matrix) if closure else mask
-
-
-def _read_best_arrays(reads, contigs, scores: bool):
-    """Reads and contigs as the C ABI of ovl_read_best takes them (one symbol map for both), with the arrays to
-    receive the results: five int32 arrays over the reads, the tie bits and (``scores``) the score matrix."""
-    reads, contigs = list(reads), list(contigs)
-    R, C = len(reads), len(contigs)
-    buf, offs = encode_reads(reads + contigs)
-    r_off = np.ascontiguousarray(offs[: R + 1])
-    c_off = np.ascontiguousarray(offs[R:])
-    outs = [np.zeros(max(R, 1), dtype=np.int32) for _ in range(5)]
-    bits = np.zeros((max(R, 1), max((C + 31) // 32, 1)), dtype=np.uint32)
-    sc = np.zeros((max(R, 1), max(C, 1)), dtype=np.int32) if scores else None
-    return R, C, buf, r_off, c_off, outs, bits, sc
-
-
-def _read_best_result(R: int, C: int, outs, bits, sc) -> Dict[str, np.ndarray]:
-    res = dict(zip(("best_score", "first_best", "n_best", "start", "end"), (o[:R] for o in outs)))
-    res["tie_bits"] = bits[:R, : (C + 31) // 32]
-    if sc is not None:
-        res["scores"] = sc[:R, :C]
-    return res
-
-
-def read_best_host(reads, contigs, read_length: int, match: int = 10, mismatch: int = -1, indel: int = -1,
-                   scores: bool = False) -> Dict[str, np.ndarray]:
-    """``OverlapEngine.read_best`` on one host thread (ovl_read_best_host): no context, no GPU."""
-    R, C, buf, r_off, c_off, outs, bits, sc = _read_best_arrays(reads, contigs, scores)
-    check(_lib.load().ovl_read_best_host(_ptr(buf), _ptr(r_off), R, _ptr(buf), _ptr(c_off), C, int(read_length),
-                                         int(match), int(mismatch), int(indel), *[_ptr(o) for o in outs], _ptr(bits),
-                                         _ptr(sc) if scores else None))
-    return _read_best_result(R, C, outs, bits, sc)
-
-
-def _consensus_arrays(reads, contigs, place, counts: bool):
-    """Reads, contigs and the placement as the C ABI of ovl_consensus takes them, with the arrays to receive the
-    results: the counts (total bases x 6 int32, when asked for), the called bytes and three int32 per read."""
-    reads, contigs = list(reads), list(contigs)
-    R, C = len(reads), len(contigs)
-    if not all(s.isascii() for s in reads + contigs):
-        raise OvlError(-4, "consensus needs ASCII reads and contigs (the called bases are bytes)")
-    buf, offs = encode_reads(reads + contigs)
-    place = np.ascontiguousarray(place, dtype=np.int32)
-    if place.shape != (R,):
-        raise OvlError(-1, "place must hold one contig position (or -1) per read")
-    total = int(offs[-1] - offs[R])
-    cnt = np.zeros((max(total, 1), 6), dtype=np.int32) if counts else None
-    called = np.zeros(max(total, 1), dtype=np.uint8)
-    aln = np.zeros((max(R, 1), 3), dtype=np.int32)
-    return R, C, buf, np.ascontiguousarray(offs[: R + 1]), np.ascontiguousarray(offs[R:]), place, total, cnt, called, aln
-
-
-def _consensus_result(R, total, cnt, called, aln, n_changed, n_other) -> Dict[str, object]:
-    res = {"called": called[:total], "n_changed": int(n_changed.value), "n_other": int(n_other.value),
-           "aln": aln[:R]}
-    if cnt is not None:
-        res["counts"] = cnt[:total]
-    return res
-
-
-def consensus_host(reads, contigs, place, read_length: int, match: int = 10, mismatch: int = -1, indel: int = -1,
-                   min_depth: int = 3, counts: bool = True) -> Dict[str, object]:
-    """``OverlapEngine.consensus`` on one host thread (ovl_consensus_host): no context, no GPU."""
-    R, C, buf, r_off, c_off, place, total, cnt, called, aln = _consensus_arrays(reads, contigs, place, counts)
-    n_changed, n_other = ctypes.c_int64(0), ctypes.c_int64(0)
-    check(_lib.load().ovl_consensus_host(_ptr(buf), _ptr(r_off), R, _ptr(buf), _ptr(c_off), C, _ptr(place),
-                                         int(read_length), int(match), int(mismatch), int(indel), int(min_depth),
-                                         _ptr(cnt) if counts else None, _ptr(called), ctypes.byref(n_changed),
-                                         ctypes.byref(n_other), _ptr(aln)))
-    return _consensus_result(R, total, cnt, called, aln, n_changed, n_other)
-
-
-def _placed_call(fn, head, reads, contigs, contig, offset, slack, weights, rounds, min_depth, min_vote_score, match,
-                 mismatch, indel, counts):
-    """One call of ovl_consensus_placed / ovl_consensus_placed_host (``head``: the arguments before ``reads``)."""
-    R, C, buf, r_off, c_off, contig, total, cnt, called, aln = _consensus_arrays(reads, contigs, contig, counts)
-    offset = np.ascontiguousarray(offset, dtype=np.int32)
-    if offset.shape != (R,):
-        raise OvlError(-1, "offset must hold one int32 per read")
-    if weights is not None:
-        weights = np.ascontiguousarray(weights, dtype=np.int32)
-        if weights.shape != (R,):
-            raise OvlError(-1, "weights must hold one int32 per read")
-    n_changed, n_other, total_changed = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
-    rounds_done = ctypes.c_int32(0)
-    rc = fn(*head, _ptr(buf), _ptr(r_off), R, _ptr(weights) if weights is not None else None, _ptr(buf), _ptr(c_off),
-            C, _ptr(contig), _ptr(offset), int(slack), int(match), int(mismatch), int(indel), int(min_vote_score),
-            int(min_depth), int(rounds), _ptr(cnt) if counts else None, _ptr(called), ctypes.byref(n_changed),
-            ctypes.byref(n_other), ctypes.byref(total_changed), ctypes.byref(rounds_done), _ptr(aln))
-    check(rc, head[0] if head else None)
-    res = _consensus_result(R, total, cnt, called, aln, n_changed, n_other)
-    res["total_changed"] = int(total_changed.value)
-    res["rounds"] = int(rounds_done.value)
-    return res
-
-
-def consensus_placed_host(reads, contigs, contig, offset, slack: int = 8, weights=None, rounds: int = 1,
-                          min_depth: int = 3, min_vote_score: int = 1, match: int = 10, mismatch: int = -1,
-                          indel: int = -1, counts: bool = True) -> Dict[str, object]:
-    """``OverlapEngine.consensus_placed`` on one host thread (ovl_consensus_placed_host): no context, no GPU, any
-    slack."""
-    return _placed_call(_lib.load().ovl_consensus_placed_host, (), reads, contigs, contig, offset, slack, weights,
-                        rounds, min_depth, min_vote_score, match, mismatch, indel, counts)
-
-
-def _layout_outputs(n: int, total: int):
-    """The arrays that receive a layout: succ, link, contig, offset (int32 per read), on_path (uint8 per read), the
-    contigs' bytes (at most the reads' bytes) and their offsets (n + 1 int64)."""
-    outs = [np.zeros(max(n, 1), dtype=np.int32) for _ in range(4)]
-    return outs, np.zeros(max(n, 1), dtype=np.uint8), np.zeros(max(total, 1), dtype=np.uint8), \
-        np.zeros(n + 1, dtype=np.int64)
-
-
-def _layout_columns(n: int, a, b, score, end):
-    cols = [np.ascontiguousarray(x, dtype=np.int32) for x in (a, b, score, end)]
-    if any(x.ndim != 1 or x.shape != cols[0].shape for x in cols):
-        raise OvlError(-1, "layout: a, b, score and end must be 1-D arrays of equal length")
-    return cols
-
-
-def _layout_result(n: int, outs, on_path, bases, c_off, n_contigs: int, stats) -> Dict[str, object]:
-    res: Dict[str, object] = dict(zip(("succ", "link", "contig", "offset"), (o[:n] for o in outs)))
-    res["on_path"] = on_path[:n]
-    res["c_off"] = c_off[: n_contigs + 1]
-    res["bases"] = bases[: int(c_off[n_contigs])]
-    res["n_contigs"] = n_contigs
-    res.update(stats)
-    return res
-
-
-def last_layout_host() -> Dict[str, int]:
-    """{links, cycles, levels, on_path_reads} of this thread's last ``layout_host`` (ovl_last_layout without a
-    context)."""
-    li, cy, pa, lv = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32()
-    check(_lib.load().ovl_last_layout(None, ctypes.byref(li), ctypes.byref(cy), ctypes.byref(lv), ctypes.byref(pa)))
-    return {"links": li.value, "cycles": cy.value, "levels": lv.value, "on_path_reads": pa.value}
-
-
-def layout_host(reads, a, b, score, end, min_score: int = 1, min_overlap: int = 1, encoded=None) -> Dict[str, object]:
-    """``OverlapEngine.layout`` on one host thread (ovl_layout_host): no context, no GPU."""
-    buf, offs = encoded if encoded is not None else encode_reads(reads)
-    n = offs.shape[0] - 1
-    cols = _layout_columns(n, a, b, score, end)
-    outs, on_path, bases, c_off = _layout_outputs(n, int(offs[-1] - offs[0]))
-    nc = ctypes.c_int32(0)
-    check(_lib.load().ovl_layout_host(_ptr(buf), _ptr(offs), n, *[_ptr(x) for x in cols], cols[0].shape[0],
-                                      int(min_score), int(min_overlap), *[_ptr(o) for o in outs], _ptr(on_path),
-                                      _ptr(bases), _ptr(c_off), ctypes.byref(nc)))
-    return _layout_result(n, outs, on_path, bases, c_off, nc.value, last_layout_host())
-
-
-CORRECT_STATS = ("kmers", "distinct", "solid", "untrusted", "changed", "ties", "threshold", "windows")
-
-
-def _spectrum_call(fn, ctx_args, buf, offs, k: int, err_ctx=None):
-    """The two-call protocol of ovl_kmer_spectrum(_host): size the arrays, then fill them."""
-    n = offs.shape[0] - 1
-    nd = ctypes.c_int64(0)
-    rc = fn(*ctx_args, _ptr(buf), _ptr(offs), n, int(k), None, None, 0, ctypes.byref(nd))
-    if rc not in (0, -5):
-        check(rc, err_ctx)
-    keys = np.zeros(max(nd.value, 1), dtype=np.uint64)
-    counts = np.zeros(max(nd.value, 1), dtype=np.int32)
-    if nd.value > 0:
-        check(fn(*ctx_args, _ptr(buf), _ptr(offs), n, int(k), _ptr(keys), _ptr(counts), nd.value, ctypes.byref(nd)),
-              err_ctx)
-    return keys[: nd.value], counts[: nd.value]
-
-
-def _correct_call(fn, ctx_args, buf, offs, k: int, min_count: int, err_ctx=None):
-    """ovl_correct_reads(_host): (the corrected bytes, the changed bases per read, the stats as a dict)."""
-    n = offs.shape[0] - 1
-    out = np.zeros(max(buf.shape[0], 1), dtype=np.uint8)
-    changed = np.zeros(max(n, 1), dtype=np.int32)
-    stats = np.zeros(8, dtype=np.int64)
-    check(fn(*ctx_args, _ptr(buf), _ptr(offs), n, int(k), int(min_count), _ptr(out), _ptr(changed), _ptr(stats)),
-          err_ctx)
-    return out[: int(offs[-1])], changed[:n], dict(zip(CORRECT_STATS, (int(v) for v in stats)))
-
-
-def kmer_spectrum_host(reads, k: int, encoded=None):
-    """``OverlapEngine.kmer_spectrum`` on one host thread (ovl_kmer_spectrum_host): no context, no GPU."""
-    buf, offs = encoded if encoded is not None else encode_reads(reads)
-    return _spectrum_call(_lib.load().ovl_kmer_spectrum_host, (), buf, offs, k)
-
-
-def correct_reads_host(reads, k: int, min_count: int = 0, encoded=None):
-    """``OverlapEngine.correct_reads`` on one host thread (ovl_correct_reads_host): no context, no GPU."""
-    buf, offs = encoded if encoded is not None else encode_reads(reads)
-    return _correct_call(_lib.load().ovl_correct_reads_host, (), buf, offs, k, min_count)
+def _pair_arrays(a_idx, b_idx) -> Tuple[np.ndarray, np.ndarray]:
+    """A host pair list as the two contiguous int32 arrays the C ABI takes."""
+    a = np.ascontiguousarray(a_idx, dtype=np.int32)
+    b = np.ascontiguousarray(b_idx, dtype=np.int32)
+    if a.shape != b.shape or a.ndim != 1:
+        raise OvlError(-1, "a_idx and b_idx must be 1-D arrays of equal length")
+    return a, b
 
 
 def host_pool() -> Dict[str, int]:
     """The host thread pool's plan, recounted now (ovl_host_pool): {threads, sharers, cpus, packed}."""
-    v = [ctypes.c_int32() for _ in range(4)]
-    check(_lib.load().ovl_host_pool(*[ctypes.byref(x) for x in v]))
-    return dict(zip(("threads", "sharers", "cpus", "packed"), (x.value for x in v)))
+    return dict(zip(("threads", "sharers", "cpus", "packed"), read_out(_lib.load().ovl_host_pool)))
 
 
 def device_count() -> int:
     n = ctypes.c_int32(0)
     rc = _lib.load().ovl_device_count(ctypes.byref(n))
     return n.value if rc == 0 else 0
+
+
+def use_device(device: Optional[bool], work, min_work: int, engine) -> bool:
+    """Whether a stage takes its device form: ``device`` when the caller forced it (True / False), else whether the
+    ``work`` (a number, or a function that counts it) reaches the stage's threshold and a device can serve it -- an
+    engine was given, or one is visible.  The count is asked for last: on a box without a GPU it loads the library,
+    which small inputs do not pay for."""
+    if device is not None:
+        return device
+    if callable(work):
+        work = work()
+    return work >= min_work and (engine is not None or device_count() > 0)
 
 
 class OverlapEngine:
@@ -358,15 +118,25 @@ class OverlapEngine:
         self._dev0 = self.devices[0]  # device pointers given to score_device / score_tensors live here
         _LIVE.add(self)
 
-    def _check_tensors(self, what: str, *ts) -> None:
-        """Contiguous int32 tensors on this engine's first device (kernels there read and write them)."""
+    def _get(self, fn, keys, *args) -> dict:
+        """``keys`` zipped with the out-parameters of ``fn(ctx, *args, ...)``."""
+        return dict(zip(keys, read_out(fn, self._ctx, *args, ctx=self._ctx)))
+
+    def _tensor_args(self, what: str, a, b, out_score, out_end, stream) -> Tuple[int, int]:
+        """(n_pairs, stream handle) of a scoring launch over contiguous int32 tensors on this engine's first device
+        (kernels there read and write them), on torch's current stream unless ``stream`` is given."""
         import torch
-        for t in ts:
+        for t in (a, b, out_score, out_end):
             if t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous():
                 raise OvlError(-1, f"{what} needs contiguous int32 device tensors")
             if t.device.index != self._dev0:
                 raise OvlError(-1, f"{what}: tensor on cuda:{t.device.index}, but this engine's kernels run on "
                                    f"cuda:{self._dev0}")
+        n = a.numel()
+        if b.numel() != n or out_score.numel() < n or out_end.numel() < n:
+            raise OvlError(-1, "tensor sizes disagree")
+        s = stream if stream is not None else torch.cuda.current_stream(a.device)
+        return n, s.cuda_stream
 
     @property
     def devices(self) -> List[int]:
@@ -382,9 +152,7 @@ class OverlapEngine:
 
     def last_timing(self) -> Dict[str, float]:
         """{kernel_ms: summed kernel time of the busiest device, call_ms: wall time} of the last call."""
-        k, w = ctypes.c_double(), ctypes.c_double()
-        check(self._L.ovl_last_timing(self._ctx, ctypes.byref(k), ctypes.byref(w)), self._ctx)
-        return {"kernel_ms": k.value, "call_ms": w.value}
+        return self._get(self._L.ovl_last_timing, ("kernel_ms", "call_ms"))
 
     def last_launches(self) -> List[Dict[str, float]]:
         """The scoring launches of the last host-array call made with timing on (ovl_last_launches):
@@ -402,19 +170,13 @@ class OverlapEngine:
     def last_transfer(self) -> Dict[str, int]:
         """{link_bytes, packed_pairs} of the last host-array scoring call (ovl_last_transfer) and its results'
         part: result_bytes, record_pairs (crossed as tile records), escapes (ovl_last_results)."""
-        b, p = ctypes.c_int64(), ctypes.c_int64()
-        check(self._L.ovl_last_transfer(self._ctx, ctypes.byref(b), ctypes.byref(p)), self._ctx)
-        r, q, e = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
-        check(self._L.ovl_last_results(self._ctx, ctypes.byref(r), ctypes.byref(q), ctypes.byref(e)), self._ctx)
-        return {"link_bytes": b.value, "packed_pairs": p.value, "result_bytes": r.value, "record_pairs": q.value,
-                "escapes": e.value}
+        return {**self._get(self._L.ovl_last_transfer, ("link_bytes", "packed_pairs")),
+                **self._get(self._L.ovl_last_results, ("result_bytes", "record_pairs", "escapes"))}
 
     def last_pair_list(self) -> Dict[str, int]:
         """{in_place_pairs, decoded_pairs} of the last host-array call (ovl_last_pair_list): how the compact
         host pair list reached the kernels (read in place by uniform_kernel, or decoded into HBM first)."""
-        i, d = ctypes.c_int64(), ctypes.c_int64()
-        check(self._L.ovl_last_pair_list(self._ctx, ctypes.byref(i), ctypes.byref(d)), self._ctx)
-        return {"in_place_pairs": i.value, "decoded_pairs": d.value}
+        return self._get(self._L.ovl_last_pair_list, ("in_place_pairs", "decoded_pairs"))
 
     # ---------------------------------------------------------------- lifecycle
     def close(self) -> None:
@@ -443,11 +205,7 @@ class OverlapEngine:
         self._reads_key = id(reads)
 
     def info(self) -> Dict[str, int]:
-        n, lmax, planes = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
-        nbytes = ctypes.c_int64()
-        check(self._L.ovl_reads_info(self._ctx, ctypes.byref(n), ctypes.byref(lmax), ctypes.byref(planes),
-                                     ctypes.byref(nbytes)), self._ctx)
-        return {"n_reads": n.value, "lmax": lmax.value, "planes": planes.value, "device_bytes": nbytes.value}
+        return self._get(self._L.ovl_reads_info, ("n_reads", "lmax", "planes", "device_bytes"))
 
     def plan(self, match: int = 10, mismatch: int = -1, indel: int = INDEL_DEFAULT, band: int = -1) -> str:
         k = ctypes.c_int32()
@@ -463,9 +221,7 @@ class OverlapEngine:
         or "lane": the band form as launched), ``split`` (the band lane kernel's two lanes per pair) and ``rs_log2`` (an
         ungapped launch: 0 in throughput mode)."""
         names = ("kernel", "key64", "wide", "lane", "prof", "sfx", "ho", "h2", "band_form", "split", "rs_log2")
-        v = [ctypes.c_int32() for _ in names]
-        check(self._L.ovl_last_score_form(self._ctx, *[ctypes.byref(x) for x in v]), self._ctx)
-        form: Dict[str, object] = dict(zip(names, (x.value for x in v)))
+        form: Dict[str, object] = self._get(self._L.ovl_last_score_form, names)
         form["kernel"] = _lib.KERNELS[form["kernel"]]
         form["band_form"] = _lib.BAND_FORMS[form["band_form"]]
         return form
@@ -520,9 +276,7 @@ class OverlapEngine:
     def last_seed_timing(self) -> Dict[str, float]:
         """Device times (ms) of the last ``enumerate_seed_candidates`` made with timing on
         (ovl_last_seed_timing): keys_ms, sort_ms, count_ms (the count kernel and the scan), emit_ms."""
-        v = [ctypes.c_double() for _ in range(4)]
-        check(self._L.ovl_last_seed_timing(self._ctx, *[ctypes.byref(x) for x in v]), self._ctx)
-        return dict(zip(("keys_ms", "sort_ms", "count_ms", "emit_ms"), (x.value for x in v)))
+        return self._get(self._L.ovl_last_seed_timing, ("keys_ms", "sort_ms", "count_ms", "emit_ms"))
 
     def candidates_device(self) -> Tuple[int, int, int]:
         """(device ptr of a_idx, device ptr of b_idx, n_pairs) of the resident candidate list."""
@@ -575,9 +329,7 @@ class OverlapEngine:
 
     def devices_for(self, n_pairs: int) -> int:
         """How many of this context's devices a host-array call over n_pairs uses (ovl_devices_for)."""
-        k = ctypes.c_int32()
-        check(self._L.ovl_devices_for(self._ctx, int(n_pairs), ctypes.byref(k)), self._ctx)
-        return k.value
+        return read_out(self._L.ovl_devices_for, self._ctx, int(n_pairs), ctx=self._ctx)[0]
 
     def quiesce(self) -> None:
         """Make this context's resident scoring grids leave the device now (ovl_quiesce): before a whole-device
@@ -587,11 +339,7 @@ class OverlapEngine:
 
     def resident_stats(self) -> Dict[str, int]:
         """{alive, launches, relaunches, broken} of this context's resident grids (ovl_resident_stats)."""
-        al, br = ctypes.c_int32(), ctypes.c_int32()
-        ln, rl = ctypes.c_int64(), ctypes.c_int64()
-        check(self._L.ovl_resident_stats(self._ctx, ctypes.byref(al), ctypes.byref(ln), ctypes.byref(rl),
-                                         ctypes.byref(br)), self._ctx)
-        return {"alive": al.value, "launches": ln.value, "relaunches": rl.value, "broken": br.value}
+        return self._get(self._L.ovl_resident_stats, ("alive", "launches", "relaunches", "broken"))
 
     def candidate_shards(self, n_shards: int) -> List[int]:
         """Shard bounds of the resident candidate list balanced by sum len(a)*len(b) + 1 (on the device)."""
@@ -667,9 +415,7 @@ class OverlapEngine:
     def last_local_batch(self) -> Dict[str, int]:
         """{batched, single, waves} of the last ``local_align_batch`` (ovl_last_local_batch): the queries that took
         the batch kernel, those that took the single-pair path, and the batch kernel's wavefronts."""
-        v = [ctypes.c_int32() for _ in range(3)]
-        check(self._L.ovl_last_local_batch(self._ctx, *[ctypes.byref(x) for x in v]), self._ctx)
-        return dict(zip(("batched", "single", "waves"), (x.value for x in v)))
+        return self._get(self._L.ovl_last_local_batch, ("batched", "single", "waves"))
 
     def read_best(self, reads, contigs, read_length: int, match: int = 10, mismatch: int = -1, indel: int = -1,
                   scores: bool = False) -> Dict[str, np.ndarray]:
@@ -678,19 +424,14 @@ class OverlapEngine:
         ``n_best``, ``start`` and ``end`` (the aligned stretch on that contig) as int32 arrays, ``tie_bits``
         (reads x ceil(contigs / 32) uint32: bit c of row r set iff contig c attains the best score) and, with
         ``scores=True``, the reads x contigs score matrix."""
-        R, C, buf, r_off, c_off, outs, bits, sc = _read_best_arrays(reads, contigs, scores)
-        check(self._L.ovl_read_best(self._ctx, _ptr(buf), _ptr(r_off), R, _ptr(buf), _ptr(c_off), C,
-                                    int(read_length), int(match), int(mismatch), int(indel),
-                                    *[_ptr(o) for o in outs], _ptr(bits), _ptr(sc) if scores else None), self._ctx)
-        return _read_best_result(R, C, outs, bits, sc)
+        return _read_best_call(self._L.ovl_read_best, (self._ctx,), reads, contigs, read_length, match, mismatch,
+                               indel, scores)
 
     def last_read_best(self) -> Dict[str, int]:
         """{lane_pairs, fallback_pairs, launches} of the last ``read_best`` (ovl_last_read_best): the (read, contig)
         pairs the lane-per-read kernel scored, those that went through the existing local-alignment kernels, and
         the lane kernel's launches."""
-        a, b, n = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32()
-        check(self._L.ovl_last_read_best(self._ctx, ctypes.byref(a), ctypes.byref(b), ctypes.byref(n)), self._ctx)
-        return {"lane_pairs": a.value, "fallback_pairs": b.value, "launches": n.value}
+        return self._get(self._L.ovl_last_read_best, ("lane_pairs", "fallback_pairs", "launches"))
 
     def consensus(self, reads, contigs, place, read_length: int, match: int = 10, mismatch: int = -1,
                   indel: int = -1, min_depth: int = 3, counts: bool = True) -> Dict[str, object]:
@@ -699,25 +440,15 @@ class OverlapEngine:
         concatenated contigs), ``n_changed``, ``n_other`` (read bytes outside ACGT on a diagonal), ``aln`` (reads x 3
         int32: score, first column, one past the last column, in the contig's own coordinates) and, with
         ``counts=True``, ``counts`` (bases x 6 int32: A, C, G, T, gap, ins)."""
-        R, C, buf, r_off, c_off, place, total, cnt, called, aln = _consensus_arrays(reads, contigs, place, counts)
-        n_changed, n_other = ctypes.c_int64(0), ctypes.c_int64(0)
-        check(self._L.ovl_consensus(self._ctx, _ptr(buf), _ptr(r_off), R, _ptr(buf), _ptr(c_off), C, _ptr(place),
-                                    int(read_length), int(match), int(mismatch), int(indel), int(min_depth),
-                                    _ptr(cnt) if counts else None, _ptr(called), ctypes.byref(n_changed),
-                                    ctypes.byref(n_other), _ptr(aln)), self._ctx)
-        return _consensus_result(R, total, cnt, called, aln, n_changed, n_other)
+        return _consensus_call(self._L.ovl_consensus, (self._ctx,), reads, contigs, place, read_length, match,
+                               mismatch, indel, min_depth, counts)
 
     def last_consensus(self) -> Dict[str, float]:
         """{batch_reads, single_reads, ops, launches} of the last ``consensus`` (ovl_last_consensus): the reads that
         took the batch kernel and the single-pair path, the ops piled up and the batch kernel's launches; with timing
         on also {align_ms, pileup_ms, vote_ms} (ovl_last_consensus_timing)."""
-        a, b, o, n = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32()
-        check(self._L.ovl_last_consensus(self._ctx, ctypes.byref(a), ctypes.byref(b), ctypes.byref(o),
-                                         ctypes.byref(n)), self._ctx)
-        t = [ctypes.c_double() for _ in range(3)]
-        check(self._L.ovl_last_consensus_timing(self._ctx, *[ctypes.byref(x) for x in t]), self._ctx)
-        return {"batch_reads": a.value, "single_reads": b.value, "ops": o.value, "launches": n.value,
-                "align_ms": t[0].value, "pileup_ms": t[1].value, "vote_ms": t[2].value}
+        return {**self._get(self._L.ovl_last_consensus, ("batch_reads", "single_reads", "ops", "launches")),
+                **self._get(self._L.ovl_last_consensus_timing, ("align_ms", "pileup_ms", "vote_ms"))}
 
     def consensus_placed(self, reads, contigs, contig, offset, slack: int = 8, weights=None, rounds: int = 1,
                          min_depth: int = 3, min_vote_score: int = 1, match: int = 10, mismatch: int = -1,
@@ -734,29 +465,17 @@ class OverlapEngine:
         (ovl_last_consensus_placed): the reads that voted in the last round, the placed reads without a window, the
         ops of the last round's walks, the band kernel's launches and the rounds; with timing on also {band_ms,
         vote_ms} over all rounds (ovl_last_consensus_placed_timing)."""
-        a, b, o = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
-        n, r = ctypes.c_int32(), ctypes.c_int32()
-        check(self._L.ovl_last_consensus_placed(self._ctx, ctypes.byref(a), ctypes.byref(b), ctypes.byref(o),
-                                                ctypes.byref(n), ctypes.byref(r)), self._ctx)
-        t = [ctypes.c_double() for _ in range(2)]
-        check(self._L.ovl_last_consensus_placed_timing(self._ctx, *[ctypes.byref(x) for x in t]), self._ctx)
-        return {"voted_reads": a.value, "windowless_reads": b.value, "ops": o.value, "launches": n.value,
-                "rounds": r.value, "band_ms": t[0].value, "vote_ms": t[1].value}
+        return {**self._get(self._L.ovl_last_consensus_placed,
+                            ("voted_reads", "windowless_reads", "ops", "launches", "rounds")),
+                **self._get(self._L.ovl_last_consensus_placed_timing, ("band_ms", "vote_ms"))}
 
     def layout(self, reads, a, b, score, end, min_score: int = 1, min_overlap: int = 1,
                encoded=None) -> Dict[str, object]:
         """The best-successor layout of scored pairs (ovl_layout; the rule: ``ovlgraph.layout``): ``succ``, ``link``,
         ``contig``, ``offset`` (int32 per read), ``on_path`` (uint8 per read), ``bases`` (the contigs' bytes) with
         ``c_off`` and ``n_contigs``, and the counts of ``last_layout``."""
-        buf, offs = encoded if encoded is not None else encode_reads(reads)
-        n = offs.shape[0] - 1
-        cols = _layout_columns(n, a, b, score, end)
-        outs, on_path, bases, c_off = _layout_outputs(n, int(offs[-1] - offs[0]))
-        nc = ctypes.c_int32(0)
-        check(self._L.ovl_layout(self._ctx, _ptr(buf), _ptr(offs), n, *[_ptr(x) for x in cols], cols[0].shape[0],
-                                 int(min_score), int(min_overlap), *[_ptr(o) for o in outs], _ptr(on_path),
-                                 _ptr(bases), _ptr(c_off), ctypes.byref(nc)), self._ctx)
-        return _layout_result(n, outs, on_path, bases, c_off, nc.value, self.last_layout())
+        return _layout_call(self._L.ovl_layout, (self._ctx,), self.last_layout, reads, a, b, score, end, min_score,
+                            min_overlap, encoded)
 
     def layout_candidates(self, match: int = 10, mismatch: int = -1, indel: int = INDEL_DEFAULT, band: int = -1,
                           min_score: int = 1, min_overlap: int = 1) -> Dict[str, object]:
@@ -776,51 +495,37 @@ class OverlapEngine:
         """{links, cycles, levels, on_path_reads} of the last ``layout`` / ``layout_candidates`` (ovl_last_layout): the
         links of the forest after the cuts, the cycles cut, the doubling levels and the reads on contig paths; with
         timing on also {score_ms, link_ms, forest_ms, spell_ms} (ovl_last_layout_timing)."""
-        li, cy, pa, lv = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32()
-        check(self._L.ovl_last_layout(self._ctx, ctypes.byref(li), ctypes.byref(cy), ctypes.byref(lv),
-                                      ctypes.byref(pa)), self._ctx)
-        t = [ctypes.c_double() for _ in range(4)]
-        check(self._L.ovl_last_layout_timing(self._ctx, *[ctypes.byref(x) for x in t]), self._ctx)
-        return {"links": li.value, "cycles": cy.value, "levels": lv.value, "on_path_reads": pa.value,
-                "score_ms": t[0].value, "link_ms": t[1].value, "forest_ms": t[2].value, "spell_ms": t[3].value}
+        return {**self._get(self._L.ovl_last_layout, LAYOUT_COUNTS),
+                **self._get(self._L.ovl_last_layout_timing, ("score_ms", "link_ms", "forest_ms", "spell_ms"))}
 
     def kmer_spectrum(self, reads, k: int, encoded=None):
         """The k-mer spectrum of ``reads`` (ovl_kmer_spectrum; the rule: ``ovlgraph.correct``): the distinct keys
         ascending (uint64) and their counts (int32)."""
         buf, offs = encoded if encoded is not None else encode_reads(reads)
-        return _spectrum_call(self._L.ovl_kmer_spectrum, (self._ctx,), buf, offs, k, self._ctx)
+        return _spectrum_call(self._L.ovl_kmer_spectrum, (self._ctx,), buf, offs, k)
 
     def correct_reads(self, reads, k: int, min_count: int = 0, encoded=None):
         """One round of k-mer spectrum correction (ovl_correct_reads): the corrected bytes in the layout of
         ``encode_reads``, the changed bases per read (int32) and the stats ``engine.CORRECT_STATS`` as a dict.
         ``min_count`` 0 takes the threshold rule."""
         buf, offs = encoded if encoded is not None else encode_reads(reads)
-        return _correct_call(self._L.ovl_correct_reads, (self._ctx,), buf, offs, k, min_count, self._ctx)
+        return _correct_call(self._L.ovl_correct_reads, (self._ctx,), buf, offs, k, min_count)
 
     def last_correct(self) -> Dict[str, float]:
         """With timing on, {keys_ms, sort_ms, count_ms, correct_ms} of the last ``kmer_spectrum`` / ``correct_reads``
         (ovl_last_correct_timing); zeros with timing off."""
-        t = [ctypes.c_double() for _ in range(4)]
-        check(self._L.ovl_last_correct_timing(self._ctx, *[ctypes.byref(x) for x in t]), self._ctx)
-        return {"keys_ms": t[0].value, "sort_ms": t[1].value, "count_ms": t[2].value, "correct_ms": t[3].value}
+        return self._get(self._L.ovl_last_correct_timing, ("keys_ms", "sort_ms", "count_ms", "correct_ms"))
 
     # ---------------------------------------------------------------- graph stages
     def transitive_reduce(self, off, heads, weights) -> np.ndarray:
         """The reference's transitive reduction (overlapGraphs.py:235-303) of a CSR graph on the GPU
         (ovl_transitive_reduce): a uint8 mask over the CSR edges, 1 where the reference removes the edge."""
-        off, heads, weights = _csr_arrays(off, heads, weights)
-        reduced = np.zeros(max(heads.shape[0], 1), dtype=np.uint8)
-        n_reduced = ctypes.c_int64(0)
-        check(self._L.ovl_transitive_reduce(self._ctx, _ptr(off), _ptr(heads), _ptr(weights), off.shape[0] - 1,
-                                            _ptr(reduced), ctypes.byref(n_reduced)), self._ctx)
-        return reduced[:heads.shape[0]]
+        return _transitive_call(self._L.ovl_transitive_reduce, (self._ctx,), off, heads, weights)
 
     def last_transitive(self) -> Dict[str, int]:
         """{window, passes, two_hop_steps} of the last ``transitive_reduce`` (ovl_last_transitive): the out-row
         entries held in LDS per pass, the passes per node, and the two-hop paths walked."""
-        w, p, s = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int64()
-        check(self._L.ovl_last_transitive(self._ctx, ctypes.byref(w), ctypes.byref(p), ctypes.byref(s)), self._ctx)
-        return {"window": w.value, "passes": p.value, "two_hop_steps": s.value}
+        return self._get(self._L.ovl_last_transitive, ("window", "passes", "two_hop_steps"))
 
     def reach_reduce(self, off, heads, closure: bool = False):
         """The reference's ``transitive_reduction2`` (overlapGraphs.py:354-367) of a weightless CSR graph on the GPU
@@ -828,19 +533,12 @@ class OverlapEngine:
         goes iff a successor of v that stands before w reaches w.  ``closure=True`` returns ``(mask, matrix)``, the
         matrix n x ceil(n / 64) uint64: bit x & 63 of word x >> 6 of row u is set iff a path of at least one edge
         leads from u to x."""
-        off, heads, reduced, matrix = _reach_arrays(off, heads, closure)
-        n_reduced = ctypes.c_int64(0)
-        check(self._L.ovl_reach_reduce(self._ctx, _ptr(off), _ptr(heads), off.shape[0] - 1, _ptr(reduced),
-                                       ctypes.byref(n_reduced), _ptr(matrix) if closure else None), self._ctx)
-        mask = reduced[:heads.shape[0]]
-        return (mask, matrix) if closure else mask
+        return _reach_call(self._L.ovl_reach_reduce, (self._ctx,), off, heads, closure)
 
     def last_reach(self) -> Dict[str, int]:
         """{words_per_row, pivot_blocks, window_bits} of the last ``reach_reduce`` (ovl_last_reach): the bit matrix's
         row width, the closure's pivot blocks of 64 nodes, and the columns the marking holds in registers per pass."""
-        v = [ctypes.c_int32() for _ in range(3)]
-        check(self._L.ovl_last_reach(self._ctx, *[ctypes.byref(x) for x in v]), self._ctx)
-        return dict(zip(("words_per_row", "pivot_blocks", "window_bits"), (x.value for x in v)))
+        return self._get(self._L.ovl_last_reach, ("words_per_row", "pivot_blocks", "window_bits"))
 
     # ---------------------------------------------------------------- scoring
     def score_pairs(self, reads: Sequence[str], a_idx, b_idx, match: int = 10, mismatch: int = -1,
@@ -849,10 +547,7 @@ class OverlapEngine:
         """The one-shot ABI call ``ovl_score_pairs``: host reads + host pair list -> host
         (score, end); the reads are uploaded, packed and left resident (as ``set_reads``)."""
         buf, offs = encoded if encoded is not None else encode_reads(reads)
-        a = np.ascontiguousarray(a_idx, dtype=np.int32)
-        b = np.ascontiguousarray(b_idx, dtype=np.int32)
-        if a.shape != b.shape or a.ndim != 1:
-            raise OvlError(-1, "a_idx and b_idx must be 1-D arrays of equal length")
+        a, b = _pair_arrays(a_idx, b_idx)
         sc, en = _outputs(a.shape[0], out)
         check(self._L.ovl_score_pairs(self._ctx, _ptr(buf), _ptr(offs), offs.shape[0] - 1, _ptr(a), _ptr(b),
                                       a.shape[0], match, mismatch, indel, band, _ptr(sc), _ptr(en)), self._ctx)
@@ -863,10 +558,7 @@ class OverlapEngine:
               band: int = -1, out=None) -> Tuple[np.ndarray, np.ndarray]:
         """Score pairs (host arrays) against the resident reads -> (score, end) int32 arrays
         (pinned unless ``out=(score, end)`` is given); sharded over the engine's devices."""
-        a = np.ascontiguousarray(a_idx, dtype=np.int32)
-        b = np.ascontiguousarray(b_idx, dtype=np.int32)
-        if a.shape != b.shape or a.ndim != 1:
-            raise OvlError(-1, "a_idx and b_idx must be 1-D arrays of equal length")
+        a, b = _pair_arrays(a_idx, b_idx)
         sc, en = _outputs(a.shape[0], out)
         check(self._L.ovl_score_host(self._ctx, _ptr(a), _ptr(b), a.shape[0], match, mismatch, indel, band,
                                      _ptr(sc), _ptr(en)), self._ctx)
@@ -883,14 +575,9 @@ class OverlapEngine:
     def score_tensors(self, a, b, out_score, out_end, match: int = 10, mismatch: int = -1,
                       indel: int = INDEL_DEFAULT, band: int = -1, stream=None) -> None:
         """torch int32 device tensors in/out, launched on torch's current stream (or `stream`)."""
-        import torch
-        self._check_tensors("score_tensors", a, b, out_score, out_end)
-        n = a.numel()
-        if b.numel() != n or out_score.numel() < n or out_end.numel() < n:
-            raise OvlError(-1, "tensor sizes disagree")
-        s = stream if stream is not None else torch.cuda.current_stream(a.device)
+        n, s = self._tensor_args("score_tensors", a, b, out_score, out_end, stream)
         self.score_device(a.data_ptr(), b.data_ptr(), n, out_score.data_ptr(), out_end.data_ptr(),
-                          match, mismatch, indel, band, stream=s.cuda_stream)
+                          match, mismatch, indel, band, stream=s)
 
     def launcher(self, a, b, out_score, out_end, match: int = 10, mismatch: int = -1,
                  indel: int = INDEL_DEFAULT, band: int = -1, stream=None):
@@ -900,18 +587,13 @@ class OverlapEngine:
         foreign call (the launch itself) instead of per-call tensor checks.
         The tensors must stay alive while the launcher is used.
         """
-        import torch
-        self._check_tensors("launcher", a, b, out_score, out_end)
-        n = a.numel()
-        if b.numel() != n or out_score.numel() < n or out_end.numel() < n:
-            raise OvlError(-1, "tensor sizes disagree")
-        s = stream if stream is not None else torch.cuda.current_stream(a.device)
+        n, s = self._tensor_args("launcher", a, b, out_score, out_end, stream)
         fn = self._L.ovl_score_device
         ctx = self._ctx
         args = (ctx, ctypes.c_void_p(a.data_ptr()), ctypes.c_void_p(b.data_ptr()), ctypes.c_int64(n),
                 ctypes.c_int32(match), ctypes.c_int32(mismatch), ctypes.c_int64(indel), ctypes.c_int32(band),
                 ctypes.c_void_p(out_score.data_ptr()), ctypes.c_void_p(out_end.data_ptr()),
-                ctypes.c_void_p(s.cuda_stream or None))
+                ctypes.c_void_p(s or None))
         check(self._L.ovl_plan(ctx, match, mismatch, indel, band, ctypes.byref(ctypes.c_int32())), ctx)
 
         def launch() -> None:

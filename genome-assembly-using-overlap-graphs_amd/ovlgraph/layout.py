@@ -141,12 +141,10 @@ def layout(reads: Sequence[str], a, b, score, end, min_score: int = 1, min_overl
 
     ``device=None`` takes the host form (ovl_layout_host) when no GPU is visible or the list holds fewer than
     ``LAYOUT_DEVICE_MIN_PAIRS`` pairs, else the device form (ovl_layout); True / False force the choice."""
-    from .engine import default_engine, device_count, layout_host
+    from .engine import default_engine, layout_host, use_device
     reads = list(reads)
     _check_text(reads)
-    if device is None:
-        device = len(a) >= LAYOUT_DEVICE_MIN_PAIRS and (engine is not None or device_count() > 0)
-    if device:
+    if use_device(device, lambda: len(a), LAYOUT_DEVICE_MIN_PAIRS, engine):
         return _with_contigs((engine or default_engine()).layout(reads, a, b, score, end, min_score, min_overlap))
     return _with_contigs(layout_host(reads, a, b, score, end, min_score, min_overlap))
 

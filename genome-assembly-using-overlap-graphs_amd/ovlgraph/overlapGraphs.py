@@ -794,13 +794,11 @@ TRANSITIVE_DEVICE_MIN_STEPS = 866_400
 
 def _reduced_mask(off, heads, weights, engine: Optional[OverlapEngine], device: Optional[bool]) -> np.ndarray:
     """uint8 mask over the CSR edges, 1 where the reference's transitive_reduction removes the edge."""
-    from .engine import device_count, transitive_reduce_host
-    if device is None:
-        steps = int(np.diff(off)[heads].sum()) if heads.shape[0] else 0
-        device = steps >= TRANSITIVE_DEVICE_MIN_STEPS and (engine is not None or device_count() > 0)
-    if not device:
-        return transitive_reduce_host(off, heads, weights)
-    return (engine or default_engine()).transitive_reduce(off, heads, weights)
+    from .engine import transitive_reduce_host, use_device
+    if use_device(device, lambda: int(np.diff(off)[heads].sum()) if heads.shape[0] else 0,
+                  TRANSITIVE_DEVICE_MIN_STEPS, engine):
+        return (engine or default_engine()).transitive_reduce(off, heads, weights)
+    return transitive_reduce_host(off, heads, weights)
 
 
 def transitive_reduction(overlap_graph, fuzz=10, engine: Optional[OverlapEngine] = None,
@@ -905,12 +903,11 @@ def transitive_reduction2(graph, engine: Optional[OverlapEngine] = None, device:
     (``ovl_reach_reduce``: blocked Warshall, then one sweep per node) or on one host thread.  ``device=None`` takes
     the host form when no GPU is visible or the graph has fewer than ``REACH_DEVICE_MIN_WORK`` nodes; True / False
     force the choice."""
-    from .engine import device_count, reach_reduce_host
+    from .engine import reach_reduce_host, use_device
     G = graph
     nodes = list(G)
     off, heads = _csr_heads(nodes, G._adj)
-    if device is None:
-        device = len(nodes) >= REACH_DEVICE_MIN_WORK and (engine is not None or device_count() > 0)
+    device = use_device(device, len(nodes), REACH_DEVICE_MIN_WORK, engine)
     reduced = (engine or default_engine()).reach_reduce(off, heads) if device else reach_reduce_host(off, heads)
     H = G.copy()
     idx = np.flatnonzero(reduced)

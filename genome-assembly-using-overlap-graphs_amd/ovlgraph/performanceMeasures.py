@@ -147,12 +147,10 @@ def read_depth(contigs, reads, read_length, match_score=10, mismatch=-1, indel=-
     The alignments and the selection run in native code: ``ovl_read_best`` on the GPU or ``ovl_read_best_host`` on
     one host thread.  ``device=None`` takes the host form when no GPU is visible or the pairs hold fewer than
     ``READ_DEPTH_DEVICE_MIN_CELLS`` cells; True / False force the choice."""
-    from .engine import default_engine, device_count, read_best_host
+    from .engine import default_engine, read_best_host, use_device
     contigs, reads = list(contigs), list(reads)
-    if device is None:
-        cells = sum(len(r) for r in reads) * sum(len(c) for c in contigs)
-        device = cells >= READ_DEPTH_DEVICE_MIN_CELLS and (engine is not None or device_count() > 0)
-    if device:
+    if use_device(device, lambda: sum(len(r) for r in reads) * sum(len(c) for c in contigs),
+                  READ_DEPTH_DEVICE_MIN_CELLS, engine):
         res = (engine or default_engine()).read_best(reads, contigs, read_length, match_score, mismatch, indel)
     else:
         res = read_best_host(reads, contigs, read_length, match_score, mismatch, indel)
