@@ -4,8 +4,8 @@
 // ovl_cand.cpp (candidate lists, resident grid), ovl_local_api.cpp (single alignments), ovl_depth_api.cpp (read
 // depth), ovl_consensus_api.cpp (read pileup and consensus), ovl_consensus_placed_api.cpp (consensus at the layout's
 // placement), ovl_layout_api.cpp (best-successor layout),
-// ovl_spectrum_api.cpp (k-mer spectrum read correction) and the graph stages ovl_reduce_api.cpp /
-// ovl_reach_api.cpp.  What the local-alignment stages share on the host is in ovl_local_host.h; what every stage's
+// ovl_spectrum_api.cpp (k-mer spectrum read correction), ovl_unitigs_api.cpp (the unitig pipeline from the score
+// columns) and the graph stages ovl_reduce_api.cpp / ovl_reach_api.cpp.  What the local-alignment stages share on the host is in ovl_local_host.h; what every stage's
 // call, timing and device state share is in ovl_stage.h (included below, ahead of Dev).
 //
 // A context (ovl_ctx) drives one or more HIP devices from one host thread.  Each
@@ -374,6 +374,7 @@ struct Dev {
     PlacedState pl;
     LayoutState ly;
     SpectrumState sp;
+    UnitigsState ug;
     // host-array pipeline: events per slot and pinned staging (slots x cap pairs x {a, b} / {score, end})
     hipEvent_t ev_k[kSlots] = {};
     int32_t* st_in = nullptr;
@@ -503,5 +504,10 @@ int device_cuts(Dev* d, int64_t lo, int64_t hi, int32_t shards, std::vector<int6
 bool pack_ok(const ovl_ctx* c, const Plan& p, int64_t n_pairs, bool out_pinned, int32_t n_devices);
 int32_t devices_for(const ovl_ctx* c, int64_t n_pairs);
 int32_t devices_used(const ovl_ctx* c, int64_t n_pairs);
+// ovl_reach_api.cpp: the closure and marking launches of ovl_reach.hip over a CSR that is in device memory (a->off,
+// head, order, n_nodes, n_order, words and reduced set by the caller, reduced zeroed; the matrix and the pivot rows are
+// the reach stage's own buffers, grown here), and the marking's column window in words (OVL_REACH_WINDOW)
+int reach_launches(Dev* c, OvlReachArgs* a, bool closure, hipStream_t s);
+int32_t reach_window_words(const Dev* c);
 // ovl_reads.cpp
 int set_reads(ovl_ctx* c, const uint8_t* seqs, const int64_t* offsets, int32_t n_reads, bool sync);

@@ -3,60 +3,11 @@
 // are ovl_graph_check.h's, shared with ovl_reduce_api.cpp.
 #include "ovl_ctx.h"
 #include "ovl_graph_check.h"
+#include "ovl_reach_host.h"
 
 namespace {
 
 constexpr int32_t kReachWindowWords = 64 * kReachAccWords;  // a wavefront's acc: 16,384 columns per window
-
-// rows * words uint64, or false when the size does not fit or cannot be allocated
-bool alloc_matrix(std::vector<uint64_t>& m, int64_t rows, int64_t words) {
-    if (words > 0 && rows > (int64_t)(SIZE_MAX / sizeof(uint64_t)) / words) return false;
-    try {
-        m.assign((size_t)(rows * words), 0);
-    } catch (const std::bad_alloc&) {
-        return false;
-    }
-    return true;
-}
-
-// R[u] = the nodes reachable from u by at least one edge: the adjacency rows, then row-OR Warshall
-void closure_host(const int64_t* off, const int32_t* head, int32_t n, int64_t words, uint64_t* R) {
-    for (int32_t v = 0; v < n; ++v)
-        for (int64_t e = off[v]; e < off[v + 1]; ++e) R[v * words + (head[e] >> 6)] |= uint64_t(1) << (head[e] & 63);
-    for (int32_t k = 0; k < n; ++k) {
-        const uint64_t* rk = R + k * words;
-        const int64_t kw = k >> 6;
-        const uint64_t kb = uint64_t(1) << (k & 63);
-        for (int32_t i = 0; i < n; ++i) {
-            uint64_t* ri = R + i * words;
-            if (!(ri[kw] & kb) || i == k) continue;
-            for (int64_t j = 0; j < words; ++j) ri[j] |= rk[j];
-        }
-    }
-}
-
-// the positional rule over the closure: acc = OR of R[u] over the successors seen so far
-int64_t mark_host(const int64_t* off, const int32_t* head, int32_t n, int64_t words, const uint64_t* R,
-                  uint8_t* reduced) {
-    std::vector<uint64_t> acc((size_t)words);
-    int64_t count = 0;
-    for (int32_t v = 0; v < n; ++v) {
-        const int64_t e0 = off[v], e1 = off[v + 1];
-        if (e1 - e0 < 2) {
-            if (e1 > e0) reduced[e0] = 0;  // a first successor is never removed
-            continue;
-        }
-        std::fill(acc.begin(), acc.end(), 0);
-        for (int64_t e = e0; e < e1; ++e) {
-            const int32_t w = head[e];
-            reduced[e] = (uint8_t)((acc[(size_t)(w >> 6)] >> (w & 63)) & 1u);
-            count += reduced[e];
-            const uint64_t* rw = R + w * words;
-            for (int64_t j = 0; j < words; ++j) acc[(size_t)j] |= rw[j];
-        }
-    }
-    return count;
-}
 
 int32_t pow2_at_least(int32_t x, int32_t cap) {
     int32_t g = 1;
@@ -65,6 +16,32 @@ int32_t pow2_at_least(int32_t x, int32_t cap) {
 }
 
 }  // namespace
+
+int32_t reach_window_words(const Dev* c) {
+    return c->k.reach_window > 0 ? std::min(kReachWindowWords, (c->k.reach_window + 63) / 64) : kReachWindowWords;
+}
+
+int reach_launches(Dev* c, OvlReachArgs* a, bool closure, hipStream_t s) {
+    const int32_t words = a->words;
+    HIPCHK(c, ensure(c->rc.matrix, sizeof(uint64_t) * (size_t)a->n_nodes * (size_t)words));
+    HIPCHK(c, ensure(c->rc.pivot, sizeof(uint64_t) * 64 * (size_t)words));
+    a->matrix = as<uint64_t>(c->rc.matrix);
+    a->pivot = as<uint64_t>(c->rc.pivot);
+    const int32_t row_group = pow2_at_least(words, 64);
+    // the window the marking walks with: never wider than a row, so that rows of up to 64 words take the
+    // one-word-per-lane form (ovl_launch_reach_mark) at the default window too
+    const int32_t mark_window = std::min(words, reach_window_words(c));
+    const int32_t mark_group = pow2_at_least(mark_window, 64);
+    HIPCHK(c, ovl_launch_reach_fill(a, s));
+    if (closure || a->n_order > 0) {
+        for (int32_t K = 0; K < words; ++K) {
+            HIPCHK(c, ovl_launch_reach_pivot(a, K, s));
+            HIPCHK(c, ovl_launch_reach_update(a, K, row_group, s));
+        }
+    }
+    HIPCHK(c, ovl_launch_reach_mark(a, mark_group, mark_window, s));
+    return OVL_OK;
+}
 
 OVL_API int ovl_reach_reduce_host(const int64_t* off, const int32_t* head, int32_t n_nodes, uint8_t* reduced,
                                   int64_t* n_reduced, uint64_t* closure) {
@@ -75,14 +52,14 @@ OVL_API int ovl_reach_reduce_host(const int64_t* off, const int32_t* head, int32
     std::vector<uint64_t> own;
     uint64_t* R = closure;
     if (!R) {
-        if (!alloc_matrix(own, n_nodes, words))
+        if (!reach_alloc_matrix(own, n_nodes, words))
             return fail(none, OVL_E_OOM, "no memory for the %d x %d-bit reachability matrix", n_nodes, n_nodes);
         R = own.data();
     } else {
         std::fill(R, R + (int64_t)n_nodes * words, uint64_t(0));
     }
-    closure_host(off, head, n_nodes, words, R);
-    *n_reduced = mark_host(off, head, n_nodes, words, R, reduced);
+    reach_closure_host(off, head, n_nodes, words, R);
+    *n_reduced = reach_mark_host(off, head, n_nodes, words, R, reduced);
     return OVL_OK;
 }
 
@@ -95,8 +72,7 @@ OVL_API int ovl_reach_reduce(ovl_ctx* ctx, const int64_t* off, const int32_t* he
     if (rc != OVL_OK) return rc;
     const int64_t n_edges = n_nodes > 0 ? off[n_nodes] : 0;
     const int32_t words = (int32_t)(((int64_t)n_nodes + 63) / 64);
-    int32_t window_words = kReachWindowWords;
-    if (c->k.reach_window > 0) window_words = std::min(kReachWindowWords, (c->k.reach_window + 63) / 64);
+    const int32_t window_words = reach_window_words(c);
     call.begin();
     c->rc.last = {words, words, window_words * 64};  // (ceil(n_nodes / 64) pivot blocks: one per word column)
     const size_t matrix_bytes = sizeof(uint64_t) * (size_t)n_nodes * (size_t)words;
@@ -105,15 +81,11 @@ OVL_API int ovl_reach_reduce(ovl_ctx* ctx, const int64_t* off, const int32_t* he
         *n_reduced = 0;
         return OVL_OK;
     }
-    // nodes with at least two out-edges, heaviest (degree x words) first, ties in node order
     std::vector<int32_t> order;
-    for (int32_t v = 0; v < n_nodes; ++v)
-        if (off[v + 1] - off[v] >= 2) order.push_back(v);
-    std::stable_sort(order.begin(), order.end(),
-                     [&](int32_t x, int32_t y) { return off[x + 1] - off[x] > off[y + 1] - off[y]; });
+    reach_mark_order(off, n_nodes, order);
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    HIPCHK(c, ensure(c->rc.matrix, matrix_bytes));
+    HIPCHK(c, ensure(c->rc.matrix, matrix_bytes));  // (ahead of the timed launches; reach_launches finds them made)
     HIPCHK(c, ensure(c->rc.pivot, sizeof(uint64_t) * 64 * (size_t)words));
     HIPCHK(c, ensure(c->rc.off, sizeof(int64_t) * ((size_t)n_nodes + 1)));
     HIPCHK(c, ensure(c->rc.head, sizeof(int32_t) * (size_t)n_edges));
@@ -132,24 +104,11 @@ OVL_API int ovl_reach_reduce(ovl_ctx* ctx, const int64_t* off, const int32_t* he
     a.n_nodes = n_nodes;
     a.n_order = (int32_t)order.size();
     a.words = words;
-    a.matrix = as<uint64_t>(c->rc.matrix);
-    a.pivot = as<uint64_t>(c->rc.pivot);
     a.reduced = as<uint8_t>(c->rc.out);
-    const int32_t row_group = pow2_at_least(words, 64);
-    // the window the marking walks with: never wider than a row, so that rows of up to 64 words take the
-    // one-word-per-lane form (ovl_launch_reach_mark) at the default window too
-    const int32_t mark_window = std::min(words, window_words);
-    const int32_t mark_group = pow2_at_least(mark_window, 64);
     HIPCHK(c, c->rc.timer.arm(ctx->timing));
     HIPCHK(c, c->rc.timer.mark(0, s));
-    HIPCHK(c, ovl_launch_reach_fill(&a, s));
-    if (closure || !order.empty()) {
-        for (int32_t K = 0; K < words; ++K) {
-            HIPCHK(c, ovl_launch_reach_pivot(&a, K, s));
-            HIPCHK(c, ovl_launch_reach_update(&a, K, row_group, s));
-        }
-    }
-    HIPCHK(c, ovl_launch_reach_mark(&a, mark_group, mark_window, s));
+    const int lrc = reach_launches(c, &a, closure != nullptr, s);
+    if (lrc != OVL_OK) return lrc;
     HIPCHK(c, c->rc.timer.mark(1, s));
     HIPCHK(c, hipMemcpyAsync(reduced, c->rc.out.p, (size_t)n_edges, hipMemcpyDeviceToHost, s));
     if (closure) HIPCHK(c, hipMemcpyAsync(closure, c->rc.matrix.p, matrix_bytes, hipMemcpyDeviceToHost, s));

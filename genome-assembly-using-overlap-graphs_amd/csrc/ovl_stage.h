@@ -1,5 +1,5 @@
 // ovl_stage.h — what every stage of the library (seed candidates, batched local alignment, the two graph reductions,
-// read depth, the two consensus forms, layout, read correction) has on the host: a timer for its phases, the scope of
+// read depth, the two consensus forms, layout, read correction, the unitig pipeline) has on the host: a timer for its phases, the scope of
 // one call, and its state on the device it runs on.  Host only and header only.  ovl_ctx.h includes it between the
 // context, which the call scope writes, and Dev, which holds one member per state struct below.
 //
@@ -175,5 +175,22 @@ struct SpectrumState {
     StageTimer<6> timer;
     struct Last {
         double ms[4] = {};  // ovl_last_correct_timing
+    } last;
+};
+
+// unitig pipeline from the score columns (ovl_unitigs_api.cpp; the matrix and the pivot rows are ReachState's,
+// Dev::rc): the call's inputs (ids, first, prev, the self column's index and, per form, the uploaded or scored
+// columns), the per-node block (degrees, offsets, the marking's order, the node facts), the per-edge block (the CSR's
+// columns, the mask, the kept flags and their scan, the kept edges' columns) and the scans' scratch.  Marks: before and
+// after the scoring launches, the edge build, the closure and marking, the node facts and the kept edges
+struct UnitigsState {
+    DevBuf in, node, edge, temp;
+    int64_t kept = -1;  // kept edges in `edge` (ovl_unitigs_edges_copy), -1: none
+    size_t kept_at[4] = {};
+    StageTimer<5> timer;
+    struct Last {
+        int64_t edges = 0, kept = 0;  // ovl_last_unitigs
+        int32_t paths = 0, words = 0;
+        double ms[4] = {};            // ovl_last_unitigs_timing
     } last;
 };

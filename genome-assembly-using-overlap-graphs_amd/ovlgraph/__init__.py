@@ -15,7 +15,8 @@ from .engine import INDEL_DEFAULT, OverlapEngine, default_engine, encode_reads, 
 __all__ = ["OvlError", "OverlapEngine", "default_engine", "encode_reads", "score_reads", "INDEL_DEFAULT",
            "transitive_reduction", "assemble_contigs_string", "transitive_reduction2", "find_unitigs",
            "assemble_contigs", "pileup", "polish_contigs", "pileup_placed", "best_successor_layout", "layout_loop",
-           "assemble_contigs_best_successor", "kmer_spectrum", "solid_threshold", "correct_reads"]
+           "assemble_contigs_best_successor", "kmer_spectrum", "solid_threshold", "correct_reads",
+           "reduced_string_graph", "assemble_contigs_direct"]
 
 
 def __getattr__(name):
@@ -34,6 +35,9 @@ def __getattr__(name):
         from .layout import assemble_contigs_best_successor, layout as best_successor_layout, layout_loop
         return {"best_successor_layout": best_successor_layout, "layout_loop": layout_loop,
                 "assemble_contigs_best_successor": assemble_contigs_best_successor}[name]
+    if name in ("reduced_string_graph", "assemble_contigs_direct"):
+        from . import unitigs
+        return getattr(unitigs, name)
     if name in ("kmer_spectrum", "solid_threshold", "correct_reads"):
         from . import correct
         return getattr(correct, name)

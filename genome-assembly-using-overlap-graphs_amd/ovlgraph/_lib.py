@@ -119,6 +119,16 @@ SIGNATURES = {
     "ovl_kmer_spectrum": (ctypes.c_int, [_P, _P, _P, _i32, _i32, _P, _P, _i64, _pi64]),
     "ovl_correct_reads": (ctypes.c_int, [_P, _P, _P, _i32, _i32, _i32, _P, _P, _P]),
     "ovl_last_correct_timing": (ctypes.c_int, [_P] + [_pf64] * 4),
+    "ovl_unitigs_host": (ctypes.c_int, [_P, _P, _i32, _P, _i32, _P, _P, _P, _P, _P, _P, _P, _P, _pi32, _pi64, _pi64,
+                                        _pi32]),
+    "ovl_unitigs": (ctypes.c_int, [_P, _P, _P, _i32, _P, _i32, _P, _P, _P, _P, _P, _P, _P, _P, _pi32, _pi64, _pi64,
+                                   _pi32]),
+    "ovl_unitigs_candidates": (ctypes.c_int, [_P, _P, _P, _i32, _i32, _i32, _i64, _i32, _P, _P, _P, _P, _pi32, _pi64,
+                                              _pi64, _pi32]),
+    "ovl_unitigs_edges_copy": (ctypes.c_int, [_P, _P, _P, _P, _P]),
+    "ovl_unitigs_walk_host": (ctypes.c_int, [_P, _P, _i32, _P, _P, _pi32, _pi32]),
+    "ovl_last_unitigs": (ctypes.c_int, [_P, _pi64, _pi64, _pi32, _pi32]),
+    "ovl_last_unitigs_timing": (ctypes.c_int, [_P] + [_pf64] * 4),
 }
 
 

@@ -27,11 +27,12 @@ from . import _lib
 from ._lib import OvlError, _ptr, check, read_out
 from .hostmem import pinned_empty
 # (the stage names are also this module's: callers import the host forms and encode_reads from here)
-from .stages import (CORRECT_STATS, LAYOUT_COUNTS, _consensus_call, _correct_call, _layout_call,  # noqa: F401
-                     _layout_outputs, _layout_result, _placed_call, _reach_call, _read_best_call, _spectrum_call,
-                     _transitive_call, consensus_host, consensus_placed_host, correct_reads_host, encode_reads,
-                     kmer_spectrum_host, last_layout_host, layout_host, reach_reduce_host, read_best_host,
-                     transitive_reduce_host)
+from .stages import (CORRECT_STATS, LAYOUT_COUNTS, UNITIGS_COUNTS, _consensus_call, _correct_call,  # noqa: F401
+                     _layout_call, _layout_outputs, _layout_result, _placed_call, _reach_call, _read_best_call,
+                     _spectrum_call, _transitive_call, _unitigs_call, consensus_host, consensus_placed_host,
+                     correct_reads_host, encode_reads, kmer_spectrum_host, last_layout_host, last_unitigs_host,
+                     layout_host, reach_reduce_host, read_best_host, transitive_reduce_host, unitigs_host,
+                     unitigs_walk_host)
 
 INDEL_DEFAULT = -(2 ** 31)  # aligners.py:7 default indel (the report's "-inf", REPORT p.3)
 
@@ -539,6 +540,28 @@ class OverlapEngine:
         """{words_per_row, pivot_blocks, window_bits} of the last ``reach_reduce`` (ovl_last_reach): the bit matrix's
         row width, the closure's pivot blocks of 64 nodes, and the columns the marking holds in registers per pass."""
         return self._get(self._L.ovl_last_reach, ("words_per_row", "pivot_blocks", "window_bits"))
+
+    def unitigs(self, encoded, ids, score, end, self_score=None, self_end=None) -> Dict[str, object]:
+        """The unitig pipeline from host score columns on the GPU (ovl_unitigs; the rule: ``ovlgraph.unitigs``): the
+        paths (``path_off``, ``path_nodes``), the contigs' bytes (``bases``, ``c_off``, ``n_contigs``), the kept edge
+        columns (``tail``, ``head``, ``weight``, ``end_position``), ``n_edges``, ``n_kept``, ``cycle_node`` and the
+        counts of ``last_unitigs``."""
+        return _unitigs_call(self._L.ovl_unitigs, (self._ctx,), self.last_unitigs, encoded, ids,
+                             (score, end, self_score, self_end))
+
+    def unitigs_candidates(self, encoded, ids, match: int = 10, mismatch: int = -1, indel: int = INDEL_DEFAULT,
+                           band: int = -1) -> Dict[str, object]:
+        """``unitigs`` of the raw list ``ids`` over the resident reads (``encoded``: their bytes, for the spelling) and
+        the resident k = 0 candidate list (ovl_unitigs_candidates): the list and the repeated reads' self pairs are
+        scored into device columns; only ``ids``, the per-node arrays and the outputs cross the link."""
+        return _unitigs_call(self._L.ovl_unitigs_candidates, (self._ctx,), self.last_unitigs, encoded, ids, None,
+                             (match, mismatch, indel, band))
+
+    def last_unitigs(self) -> Dict[str, float]:
+        """{edges, kept, paths, words_per_row} of the last ``unitigs`` / ``unitigs_candidates`` (ovl_last_unitigs);
+        with timing on also {score_ms, build_ms, reduce_ms, facts_ms} (ovl_last_unitigs_timing)."""
+        return {**self._get(self._L.ovl_last_unitigs, UNITIGS_COUNTS),
+                **self._get(self._L.ovl_last_unitigs_timing, ("score_ms", "build_ms", "reduce_ms", "facts_ms"))}
 
     # ---------------------------------------------------------------- scoring
     def score_pairs(self, reads: Sequence[str], a_idx, b_idx, match: int = 10, mismatch: int = -1,

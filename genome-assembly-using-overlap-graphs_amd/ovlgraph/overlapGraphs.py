@@ -877,6 +877,19 @@ def assemble_contigs_string(reads, fuzz=5, engine: Optional[OverlapEngine] = Non
 # 17.2 ms).  The constant is the first point from which it won clear of the repetitions' spread.
 REACH_DEVICE_MIN_WORK = 495
 
+# The unitig pipeline from the score columns (ovlgraph/unitigs.py: assemble_contigs_direct, reduced_string_graph) with
+# device=None takes its resident route from this many distinct reads: the crossover_reads of tools/unitigs_probe.py
+# (profiles/unitigs_direct.json, "sweep": the first r of 2,000 PhiX reads of 100 bases, p = 0.01, seed 1, whole call,
+# one MI355X, median (max - min) of five after a warm-up; the host route scores its columns on the GPU too and runs
+# ovl_unitigs_host on one host thread).  Resident / host route, ms: 8 reads 0.360 (0.084) / 0.094 (0.088); 64:
+# 0.384 (0.019) / 0.115 (0.019); 128: 0.433 (0.008) / 0.177 (0.009); 256: 0.535 (0.029) / 0.407 (0.013), the host
+# route still ahead; 384 reads (383 distinct): 0.680 (0.052) / 0.857 (0.018); 512: 0.819 (0.021) / 1.570 (0.181);
+# 1,000: 1.345 (0.050) / 6.82 (0.19); 2,000 (1,950 distinct): 2.44 (0.15) / 37.9 (0.3).  From 383 distinct reads on
+# every point has the resident route ahead by more than the two spreads together; no point between 256 and 383 was
+# measured, so the constant is the upper end of that gap.  The resident route costs about 0.35 ms whatever it holds;
+# the host form's closure grows with n^3 / 64.
+UNITIGS_DEVICE_MIN_WORK = 383
+
 
 def _csr_heads(nodes, adj) -> Tuple[np.ndarray, np.ndarray]:
     """The successor lists as a weightless CSR (node order, adjacency order within a node); no edge attribute is

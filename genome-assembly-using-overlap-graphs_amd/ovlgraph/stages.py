@@ -294,3 +294,79 @@ def correct_reads_host(reads, k: int, min_count: int = 0, encoded=None):
     """``OverlapEngine.correct_reads`` on one host thread (ovl_correct_reads_host): no context, no GPU."""
     buf, offs = encoded if encoded is not None else encode_reads(reads)
     return _correct_call(_lib.load().ovl_correct_reads_host, (), buf, offs, k, min_count)
+
+
+# ---------------------------------------------------------------- unitig pipeline from the score columns
+UNITIGS_COUNTS = ("edges", "kept", "paths", "words_per_row")  # ovl_last_unitigs, in the ABI's order
+UNITIGS_CYCLE = 1  # OVL_UNITIGS_CYCLE: the walk came back to its own path
+
+
+def _unitigs_call(fn, head, last, encoded, ids, columns, scoring=None) -> Dict[str, object]:
+    """One call of ovl_unitigs_host / ovl_unitigs (``columns``: score, end, self_score, self_end over the distinct
+    reads ``encoded``) or ovl_unitigs_candidates (``columns`` None, ``scoring``: match, mismatch, indel, band; the
+    reads and the k = 0 list are resident), then the kept edge columns by ovl_unitigs_edges_copy; ``last()`` reads
+    the counts that go with the result.  ``cycle_node`` is -1, or the node at which the walk came back to its own
+    path: the paths and contigs are then absent."""
+    buf, offs = encoded
+    n = offs.shape[0] - 1
+    ids = np.ascontiguousarray(ids, dtype=np.int32)
+    if ids.ndim != 1:
+        raise OvlError(-1, "unitigs: ids must be a 1-D array")
+    path_off = np.zeros(n + 1, dtype=np.int64)
+    path_nodes = np.zeros(max(n, 1), dtype=np.int32)
+    bases = np.zeros(max(int(offs[-1] - offs[0]), 1), dtype=np.uint8)
+    c_off = np.zeros(n + 1, dtype=np.int64)
+    nc, cyc = ctypes.c_int32(0), ctypes.c_int32(-1)
+    n_edges, n_kept = ctypes.c_int64(0), ctypes.c_int64(0)
+    outs = (_ptr(path_off), _ptr(path_nodes), _ptr(bases), _ptr(c_off), ctypes.byref(nc), ctypes.byref(n_edges),
+            ctypes.byref(n_kept), ctypes.byref(cyc))
+    if columns is not None:
+        cols = [None if x is None else np.ascontiguousarray(x, dtype=np.int32) for x in columns]
+        if any(x.shape != (n * (n - 1),) for x in cols[:2]) or any(x is not None and x.shape != (n,) for x in cols[2:]):
+            raise OvlError(-1, "unitigs: score and end hold n (n - 1) entries, the self columns n")
+        rc = fn(*head, _ptr(buf), _ptr(offs), n, _ptr(ids), ids.shape[0], *[_opt(x) for x in cols], *outs)
+    else:
+        first = buf[int(offs[0]):]
+        rc = fn(*head, _ptr(first) if first.shape[0] else _ptr(buf), _ptr(ids), ids.shape[0],
+                *[int(v) for v in scoring], *outs)
+    if rc != UNITIGS_CYCLE:
+        check(rc, _ctx_of(head))
+    kept = int(n_kept.value)
+    edges = [np.zeros(max(kept, 1), dtype=np.int32) for _ in range(4)]
+    check(_lib.load().ovl_unitigs_edges_copy(_ctx_of(head), *[_ptr(e) for e in edges]), _ctx_of(head))
+    res: Dict[str, object] = dict(zip(("tail", "head", "weight", "end_position"), (e[:kept] for e in edges)))
+    res.update(n_edges=int(n_edges.value), n_kept=kept, cycle_node=int(cyc.value) if rc == UNITIGS_CYCLE else -1)
+    if rc != UNITIGS_CYCLE:
+        k = nc.value
+        res.update(n_contigs=k, path_off=path_off[: k + 1], path_nodes=path_nodes[:n], c_off=c_off[: k + 1],
+                   bases=bases[: int(c_off[k])])
+    res.update(last())
+    return res
+
+
+def last_unitigs_host() -> Dict[str, int]:
+    """{edges, kept, paths, words_per_row} of this thread's last ``unitigs_host`` (ovl_last_unitigs without a
+    context)."""
+    return dict(zip(UNITIGS_COUNTS, read_out(_lib.load().ovl_last_unitigs, None)))
+
+
+def unitigs_host(encoded, ids, score, end, self_score=None, self_end=None) -> Dict[str, object]:
+    """``OverlapEngine.unitigs`` on one host thread (ovl_unitigs_host): no context, no GPU."""
+    return _unitigs_call(_lib.load().ovl_unitigs_host, (), last_unitigs_host, encoded, ids,
+                         (score, end, self_score, self_end))
+
+
+def unitigs_walk_host(off, heads):
+    """find_unitigs' walk over a CSR graph (ovl_unitigs_walk_host): ``(path_off, path_nodes, -1)``, or
+    ``(None, None, node)`` when the walk from a node comes back to its own path at ``node``."""
+    off, heads, _ = _csr_arrays(off, heads)
+    n = off.shape[0] - 1
+    path_off = np.zeros(n + 1, dtype=np.int64)
+    path_nodes = np.zeros(max(n, 1), dtype=np.int32)
+    n_paths, cyc = ctypes.c_int32(0), ctypes.c_int32(-1)
+    rc = _lib.load().ovl_unitigs_walk_host(_ptr(off), _ptr(heads), n, _ptr(path_off), _ptr(path_nodes),
+                                           ctypes.byref(n_paths), ctypes.byref(cyc))
+    if rc == UNITIGS_CYCLE:
+        return None, None, int(cyc.value)
+    check(rc)
+    return path_off[: n_paths.value + 1], path_nodes[:n], -1

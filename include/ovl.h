@@ -671,6 +671,80 @@ int ovl_correct_reads(ovl_ctx* ctx, const uint8_t* seqs, const int64_t* offsets,
 int ovl_last_correct_timing(const ovl_ctx* ctx, double* keys_ms, double* sort_ms, double* count_ms,
                             double* correct_ms);
 
+/*
+ * The unitig pipeline from the score columns: construct_string_graph, transitive_reduction2 and find_unitigs
+ * (overlapGraphs.py:332-412) without a graph object.
+ *
+ *   Inputs: the raw reads R[0 .. n_raw) as ids[j], the distinct read of R[j]; the n_reads distinct reads d, numbered by
+ *   first occurrence (so ids[j] is at most one more than every id before it, and every distinct read occurs); the
+ *   columns score / end over the n (n - 1) ordered pairs of distinct reads in ovl_candidates(k = 0) order, pair (x, y)
+ *   at x (n - 1) + y - (y > x); and the self columns self_score[x] / self_end[x], the pair (x, x), read only for a
+ *   read with at least two copies (both may be NULL when there is none).  first[x] is the first raw position of x,
+ *   prev[j] the previous raw position holding ids[j], or -1.
+ *   1. String graph.  Nodes are d in order.  The successor list of x is produced by j = first[x] + 1 .. n_raw - 1
+ *      ascending: position j yields ids[j] iff prev[j] <= first[x] (j is that read's first occurrence after first[x])
+ *      and score(x, ids[j]) > 0.  The edge carries weight = score and end_position = end.  That is the insertion order
+ *      of the reference's loop over combinations(R, 2); a self-loop (x, x) appears when x has a second copy.
+ *   2. Reduction.  ovl_reach_reduce's rule on that CSR.  The kept edges in CSR order are the reduced graph, added
+ *      tail-major in node order (the predecessor order of DiGraph.copy()).
+ *   3. Walk.  From every node not yet on a path, in node order, the path goes on while its last node has exactly one
+ *      kept out-edge and one kept in-edge and that edge's head is on no earlier path; a head with several predecessors
+ *      is still appended, and ends the path.  When the head is on the path itself -- a cycle of non-branching nodes,
+ *      where the reference never returns -- the call returns OVL_UNITIGS_CYCLE (1, not an error) with the node in
+ *      *cycle_node; only *n_edges, *n_kept and the kept edge columns are then valid.
+ *   4. Spelling.  A path's contig is its first read followed by read[v][end_position:] for every further node v.
+ *
+ * Outputs, each of which may be NULL but n_contigs: path_off (n_reads + 1 int64, *n_contigs + 1 written), path_nodes
+ * (n_reads int32: every node lies on exactly one path), bases (at most sum len bytes) with c_off (n_reads + 1 int64),
+ * *n_edges (the string graph's edges), *n_kept, *cycle_node (-1 without a cycle).  The kept edge columns (tail, head,
+ * weight, end_position; *n_kept int32 each, any may be NULL) are fetched by ovl_unitigs_edges_copy from the context's
+ * last device call or, with ctx NULL, from the calling thread's last ovl_unitigs_host.
+ * Every argument is checked before anything is launched or written: OVL_E_ARG for null pointers (n_contigs; offsets
+ * with reads; ids with raw reads; a column with pairs; a self column with a repeated read; seqs with bases to spell),
+ * negative counts, offsets that decrease, n_raw < n_reads and ids not numbered by first occurrence; OVL_E_INDEX for an
+ * id outside [0, n_reads); OVL_E_UNSUPPORTED for n_reads^2 >= 2^31 or sum len >= 2^31, and from the device forms when
+ * columns, CSR (sized for the most edges the raw list allows) and matrix do not fit the device's free memory: nothing
+ * is chunked.
+ *
+ * ovl_unitigs_host: the rule on one host thread, with no context and no GPU.
+ * ovl_unitigs: uploads ids and the columns and runs ovl_unitigs.hip on the context's first device: a wavefront per row
+ *   counts the row's edges by ballot, a scan gives the offsets, the same walk writes the CSR in ascending j; then
+ *   ovl_reach.hip's closure and marking on the resident CSR; then a lane per edge counts the kept in- and out-degrees
+ *   and stores the sole successor, and a scan compacts the kept edges.  The walk and the spelling run on the host from
+ *   16 bytes per node.  Device memory: 8 bytes per ordered pair, 41 per edge, 44 per node, 8 per raw read and the
+ *   n x ceil(n / 64) x 8-byte matrix.
+ * ovl_unitigs_candidates: the same on the resident reads and the resident ovl_candidates(k = 0) list, scored into
+ *   device columns by the launches of ovl_score_device (the self pairs of repeated reads in a second short list); only
+ *   ids, the per-node arrays and the outputs cross the link.  seqs: the resident reads' bytes, read 0 first, needed
+ *   only to spell bases.  OVL_E_STATE without resident reads or without a candidate list; OVL_E_ARG when the list is
+ *   not the k = 0 list of these reads (its length is not n (n - 1)).
+ * ovl_unitigs_walk_host: step 3 alone over a CSR without repeated heads (ovl_reach_reduce's checks): the paths, or
+ *   OVL_UNITIGS_CYCLE and *cycle_node.
+ * ovl_last_unitigs: of the context's last device call -- or, with ctx NULL, the thread's last ovl_unitigs_host -- the
+ *   edges, the kept edges, the paths and the matrix's words per row.  ovl_last_unitigs_timing (timing on): device time
+ *   in ms of the scoring launches (0 for ovl_unitigs), the edge build (degrees, scan, CSR; the host's wait for the
+ *   offsets lies inside it), the closure and marking, and the node facts with the kept edges.
+ */
+#define OVL_UNITIGS_CYCLE 1
+int ovl_unitigs_host(const uint8_t* seqs, const int64_t* offsets, int32_t n_reads, const int32_t* ids, int32_t n_raw,
+                     const int32_t* score, const int32_t* end, const int32_t* self_score, const int32_t* self_end,
+                     int64_t* path_off, int32_t* path_nodes, uint8_t* bases, int64_t* c_off, int32_t* n_contigs,
+                     int64_t* n_edges, int64_t* n_kept, int32_t* cycle_node);
+int ovl_unitigs(ovl_ctx* ctx, const uint8_t* seqs, const int64_t* offsets, int32_t n_reads, const int32_t* ids,
+                int32_t n_raw, const int32_t* score, const int32_t* end, const int32_t* self_score,
+                const int32_t* self_end, int64_t* path_off, int32_t* path_nodes, uint8_t* bases, int64_t* c_off,
+                int32_t* n_contigs, int64_t* n_edges, int64_t* n_kept, int32_t* cycle_node);
+int ovl_unitigs_candidates(ovl_ctx* ctx, const uint8_t* seqs, const int32_t* ids, int32_t n_raw, int32_t match,
+                           int32_t mismatch, int64_t indel, int32_t band, int64_t* path_off, int32_t* path_nodes,
+                           uint8_t* bases, int64_t* c_off, int32_t* n_contigs, int64_t* n_edges, int64_t* n_kept,
+                           int32_t* cycle_node);
+int ovl_unitigs_edges_copy(const ovl_ctx* ctx, int32_t* tail, int32_t* head, int32_t* weight, int32_t* end);
+int ovl_unitigs_walk_host(const int64_t* off, const int32_t* head, int32_t n_nodes, int64_t* path_off,
+                          int32_t* path_nodes, int32_t* n_paths, int32_t* cycle_node);
+int ovl_last_unitigs(const ovl_ctx* ctx, int64_t* edges, int64_t* kept, int32_t* paths, int32_t* words_per_row);
+int ovl_last_unitigs_timing(const ovl_ctx* ctx, double* score_ms, double* build_ms, double* reduce_ms,
+                            double* facts_ms);
+
 #ifdef __cplusplus
 }
 #endif
