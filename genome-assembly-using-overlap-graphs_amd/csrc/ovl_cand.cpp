@@ -234,9 +234,11 @@ OVL_API int ovl_candidates_copy(ovl_ctx* ctx, int32_t* a_idx, int32_t* b_idx) {
     DeviceGuard guard;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t bytes = (size_t)c->cand_n * sizeof(int32_t);
+    StreamDrain drain(c->stream);
     HIPCHK(c, hipMemcpyAsync(a_idx, c->cand_a.p, bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(b_idx, c->cand_b.p, bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    drain.armed = false;
     return OVL_OK;
 }
 

@@ -119,6 +119,16 @@ OVL_API int ovl_consensus(ovl_ctx* ctx, const uint8_t* reads, const int64_t* r_o
     const uint8_t* ref = contigs + c_off[0];
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
+    // what the copies below read or fill, ahead of the drain
+    int64_t host_other = 0;
+    std::vector<LocalBatchQuery> batch;
+    std::vector<int32_t> single;
+    std::vector<OvlLocalBatchRecord> res;
+    std::vector<int64_t> hits;
+    std::vector<int8_t> ops;
+    LocalBatchRun run;  // (local_batch_launch returns with its blob's copy in flight)
+    unsigned long long lb_ctr[2] = {0, 0}, ctr[3] = {0, 0, 0};
+    StreamDrain drain(s);
     HIPCHK(c, ensure(c->cs.ref, (size_t)total));
     HIPCHK(c, ensure(c->cs.counts, sizeof(int32_t) * 6 * (size_t)total));
     HIPCHK(c, ensure(c->cs.called, (size_t)total));
@@ -130,12 +140,6 @@ OVL_API int ovl_consensus(ovl_ctx* ctx, const uint8_t* reads, const int64_t* r_o
     unsigned long long* d_ctr = as<unsigned long long>(c->cs.ctr);  // {n_other, n_changed, bad ops}, pileup's counter
     uint32_t* d_take = reinterpret_cast<uint32_t*>(d_ctr + 3);
 
-    int64_t host_other = 0;
-    std::vector<LocalBatchQuery> batch;
-    std::vector<int32_t> single;
-    std::vector<OvlLocalBatchRecord> res;
-    std::vector<int64_t> hits;
-    std::vector<int8_t> ops;
     for (int32_t r0 = 0; r0 < n_reads;) {
         // a chunk of reads: what the ops budget holds (and no more reads than the test knob allows)
         int32_t r1 = r0;
@@ -161,7 +165,6 @@ OVL_API int ovl_consensus(ovl_ctx* ctx, const uint8_t* reads, const int64_t* r_o
             ++r1;
         }
         if (!batch.empty()) {
-            LocalBatchRun run;
             HIPCHK(c, c->cs.timer.mark(0, s));
             const int rl = local_batch_launch(ctx, c, reads, r_off, batch, nullptr, (int32_t)total,
                                               as<uint8_t>(c->cs.ref), true, match, mismatch, (int32_t)indel, &run);
@@ -182,7 +185,6 @@ OVL_API int ovl_consensus(ovl_ctx* ctx, const uint8_t* reads, const int64_t* r_o
             HIPCHK(c, c->cs.timer.mark(2, s));
             // the records come back (score and columns for aln, the op counts); the ops stay where they are
             res.resize((size_t)run.nb);
-            unsigned long long lb_ctr[2] = {0, 0};
             HIPCHK(c, hipMemcpyAsync(res.data(), c->lb.out.p, res.size() * sizeof(res[0]), hipMemcpyDeviceToHost, s));
             HIPCHK(c, hipMemcpyAsync(lb_ctr, c->lb.ctr.p, sizeof(lb_ctr), hipMemcpyDeviceToHost, s));
             HIPCHK(c, hipStreamSynchronize(s));
@@ -243,13 +245,13 @@ OVL_API int ovl_consensus(ovl_ctx* ctx, const uint8_t* reads, const int64_t* r_o
     HIPCHK(c, ovl_launch_consensus_vote(as<uint8_t>(c->cs.ref), as<int32_t>(c->cs.counts), total, min_depth,
                                         as<uint8_t>(c->cs.called), d_ctr, s));
     HIPCHK(c, c->cs.timer.mark(3, s));
-    unsigned long long ctr[3] = {0, 0, 0};
     HIPCHK(c, hipMemcpyAsync(called, c->cs.called.p, (size_t)total, hipMemcpyDeviceToHost, s));
     if (counts)
         HIPCHK(c, hipMemcpyAsync(counts, c->cs.counts.p, sizeof(int32_t) * 6 * (size_t)total, hipMemcpyDeviceToHost,
                                  s));
     HIPCHK(c, hipMemcpyAsync(ctr, c->cs.ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
+    drain.armed = false;
     last.ms[2] = c->cs.timer.ms(0, 3);
     if (ctr[2])
         return fail(c, OVL_E_INTERNAL, "consensus: %llu ops of the walks fell outside their alignments", ctr[2]);

@@ -258,6 +258,8 @@ OVL_API int ovl_consensus_placed(ovl_ctx* ctx, const uint8_t* reads, const int64
     const size_t o_q = items.size() * sizeof(OvlPlacedItem);
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
+    unsigned long long ctr[5] = {0, 0, 0, 0, 0};
+    StreamDrain drain(s);
     HIPCHK(c, ensure(c->cs.ref, (size_t)total));
     HIPCHK(c, ensure(c->cs.counts, sizeof(int32_t) * 6 * (size_t)total));
     HIPCHK(c, ensure(c->cs.called, (size_t)total));
@@ -289,7 +291,6 @@ OVL_API int ovl_consensus_placed(ovl_ctx* ctx, const uint8_t* reads, const int64
     p.aln = as<int32_t>(c->pl.aln);
     p.ctr = d_ctr;
 
-    unsigned long long ctr[5] = {0, 0, 0, 0, 0};
     int32_t done = 0;
     for (;;) {
         HIPCHK(c, hipMemsetAsync(c->cs.counts.p, 0, sizeof(int32_t) * 6 * (size_t)total, s));
@@ -324,6 +325,7 @@ OVL_API int ovl_consensus_placed(ovl_ctx* ctx, const uint8_t* reads, const int64
     if (aln && n_reads > 0)
         HIPCHK(c, hipMemcpyAsync(aln, c->pl.aln.p, sizeof(int32_t) * 3 * (size_t)n_reads, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
+    drain.armed = false;
     *n_other = (int64_t)ctr[0];
     *n_changed = (int64_t)ctr[1];
     *rounds_done = done;

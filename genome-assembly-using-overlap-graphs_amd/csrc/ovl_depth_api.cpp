@@ -190,8 +190,11 @@ OVL_API int ovl_read_best(ovl_ctx* ctx, const uint8_t* reads, const int64_t* r_o
         chunk = std::min<int64_t>(chunk, (words * 32));
         const size_t tile_half = up16(sizeof(int32_t) * (size_t)pitch * (size_t)chunk);
         const size_t res_bytes = sizeof(int32_t) * (size_t)pitch;
+        std::vector<int32_t> h_tile, res(4 * (size_t)pitch);
+        std::vector<uint32_t> h_bits(tie_bits ? (size_t)nl * (size_t)words : 0);
         HIPCHK(c, hipSetDevice(c->device));
         hipStream_t s = c->stream;
+        StreamDrain drain(s);
         HIPCHK(c, ensure(c->rb.in, blob.size()));
         HIPCHK(c, ensure(c->rb.tile, 2 * tile_half));
         HIPCHK(c, ensure(c->rb.res, 4 * res_bytes));
@@ -220,7 +223,6 @@ OVL_API int ovl_read_best(ovl_ctx* ctx, const uint8_t* reads, const int64_t* r_o
         const int32_t groups = (int32_t)(pitch / 64);
         HIPCHK(c, c->rb.timer.arm(ctx->timing));
         HIPCHK(c, c->rb.timer.mark(0, s));
-        std::vector<int32_t> h_tile;
         for (int64_t lo = 0; lo < C; lo += chunk) {
             a.c_lo = (int32_t)lo;
             a.c_hi = (int32_t)std::min<int64_t>(C, lo + chunk);
@@ -244,13 +246,12 @@ OVL_API int ovl_read_best(ovl_ctx* ctx, const uint8_t* reads, const int64_t* r_o
             }
         }
         HIPCHK(c, c->rb.timer.mark(1, s));
-        std::vector<int32_t> res(4 * (size_t)pitch);
-        std::vector<uint32_t> h_bits(tie_bits ? (size_t)nl * (size_t)words : 0);
         HIPCHK(c, hipMemcpyAsync(res.data(), c->rb.res.p, 4 * res_bytes, hipMemcpyDeviceToHost, s));
         if (tie_bits)
             HIPCHK(c, hipMemcpyAsync(h_bits.data(), c->rb.bits.p, h_bits.size() * sizeof(uint32_t),
                                      hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipStreamSynchronize(s));
+        drain.armed = false;
         kernel_ms = c->rb.timer.ms(0, 1);
         for (int32_t k = 0; k < nl; ++k) {
             const int32_t r = lane[(size_t)k];

@@ -6,6 +6,29 @@
 #include "ovl_ctx.h"
 #include "ovl_layout.h"
 
+// The per-read block of the device forms.  The scan's two arrays share the minimum keys' memory (the doubling is over
+// when the scan runs).  (Not in the namespace below: tests/c/stage_block_check.cpp carves it without a device.)
+void lay_layout_work(Carve& w, OvlLayoutArgs& g, int32_t n, int32_t levels) {
+    const size_t N = (size_t)std::max(n, 1);
+    g.best = w.take<unsigned long long>(N);
+    g.mk[0] = w.take<unsigned long long>(N);
+    g.mk[1] = w.take<unsigned long long>(N);
+    g.scan_in = reinterpret_cast<int64_t*>(g.mk[0]);
+    g.scan_out = reinterpret_cast<int64_t*>(g.mk[1]);
+    g.headkey = w.take<unsigned long long>(N);
+    g.c_off = w.take<int64_t>(N + 1);
+    g.link = w.take<int32_t>(N);
+    g.succ = w.take<int32_t>(N);
+    g.tail[0] = w.take<uint32_t>(N);
+    g.tail[1] = w.take<uint32_t>(N);
+    g.contig = w.take<int32_t>(N);
+    g.offset = w.take<int32_t>(N);
+    g.jump = w.take<int32_t>(N * ((size_t)levels + 1));
+    g.on_path = w.take<uint8_t>(N);
+    g.on_cycle = w.take<uint8_t>(N);
+    g.ctr = w.take<unsigned long long>(8);
+}
+
 namespace {
 
 thread_local LayoutState::Last g_host_stats;  // ovl_last_layout(NULL): this thread's last ovl_layout_host
@@ -38,40 +61,6 @@ int check_layout(const C* c, const uint8_t* seqs, const int64_t* offsets, int32_
     return OVL_OK;
 }
 
-inline size_t al256(size_t x) { return (x + 255) & ~size_t(255); }
-
-// The per-read block of the device forms: where each table starts, and the block's bytes.  The scan's two arrays
-// share the minimum keys' memory (the doubling is over when the scan runs).
-struct WorkPlan {
-    size_t best, mk0, mk1, headkey, c_off, link, succ, tail0, tail1, contig, offset, jump, on_path, on_cycle, ctr,
-        bytes;
-    WorkPlan(int32_t n, int32_t levels) {
-        const size_t N = (size_t)std::max(n, 1);
-        size_t at = 0;
-        auto take = [&](size_t b) {
-            const size_t o = at;
-            at = al256(at + b);
-            return o;
-        };
-        best = take(8 * N);
-        mk0 = take(8 * N);
-        mk1 = take(8 * N);
-        headkey = take(8 * N);
-        c_off = take(8 * (N + 1));
-        link = take(4 * N);
-        succ = take(4 * N);
-        tail0 = take(4 * N);
-        tail1 = take(4 * N);
-        contig = take(4 * N);
-        offset = take(4 * N);
-        jump = take(4 * N * ((size_t)levels + 1));
-        on_path = take(N);
-        on_cycle = take(N);
-        ctr = take(64);
-        bytes = at;
-    }
-};
-
 // What the device routine works on: the reads and the columns, already in device memory.
 struct DeviceColumns {
     int32_t n = 0;
@@ -83,6 +72,24 @@ struct DeviceColumns {
     const int32_t *a = nullptr, *b = nullptr, *score = nullptr, *end = nullptr;
 };
 
+// ovl_layout's upload block: lengths, offsets from the first read's, the bytes (when contigs are spelled), the columns
+void lay_upload(Carve& b, DeviceColumns& d, size_t N, size_t seq_bytes, size_t E) {
+    d.len = b.take<int32_t>(N);
+    d.off = b.take<int64_t>(N + 1);
+    d.seqs = b.take<uint8_t>(seq_bytes);
+    d.a = b.take<int32_t>(E);
+    d.b = b.take<int32_t>(E);
+    d.score = b.take<int32_t>(E);
+    d.end = b.take<int32_t>(E);
+}
+
+// ovl_layout_candidates' block: the score and end columns, which the scorer fills, and the code table
+void lay_scored(Carve& b, DeviceColumns& d, size_t E) {
+    d.score = b.take<int32_t>(E);
+    d.end = b.take<int32_t>(E);
+    d.table = b.take<uint8_t>(256);
+}
+
 struct Outputs {
     int32_t *succ, *link, *contig, *offset;
     uint8_t *on_path, *bases;
@@ -90,25 +97,15 @@ struct Outputs {
     int32_t* n_contigs;
 };
 
-// Device bytes the two forms need beside their inputs: the per-read block, the contigs' bytes and the scan's scratch.
-int work_bytes(Dev* c, int32_t n, int64_t total, bool spell, size_t* bytes, size_t* temp) {
-    const WorkPlan w(n, ovl_layout_levels(n));
+// The fits check of the two forms: their inputs, the per-read block, the contigs' bytes and the scan's scratch (*temp).
+int layout_fits(Dev* c, size_t in_bytes, int32_t n, int64_t total, bool spell, size_t* temp) {
+    Carve w;
+    OvlLayoutArgs g{};
+    lay_layout_work(w, g, n, ovl_layout_levels(n));
     *temp = 0;
     if (n > 0) HIPCHK(c, ovl_layout_scan_bytes(n, temp));
-    *bytes = w.bytes + (spell ? (size_t)total : 0) + *temp;
-    return OVL_OK;
-}
-
-// OVL_E_UNSUPPORTED when `need` bytes of layout buffers exceed what the device has free plus what those buffers
-// already hold
-int check_fits(Dev* c, size_t need) {
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
-    const size_t held = c->ly.in.bytes + c->ly.work.bytes + c->ly.bases.bytes + c->ly.temp.bytes;
-    if (need > free_b + held)
-        return fail(c, OVL_E_UNSUPPORTED, "layout: %zu bytes of columns and tables do not fit the device (%zu free)",
-                    need, free_b + held);
-    return OVL_OK;
+    return check_fits(c, "layout", "columns and tables", in_bytes + w.at + (spell ? (size_t)total : 0) + *temp,
+                      {&c->ly.in, &c->ly.work, &c->ly.bases, &c->ly.temp});
 }
 
 // From the link kernel to the outputs, on c->stream; the timer's marks are recorded from mark 1 on (the caller armed it
@@ -119,12 +116,14 @@ int run_layout(Dev* c, const DeviceColumns& in, int32_t min_score, int32_t min_o
     const int32_t n = in.n;
     const int32_t levels = ovl_layout_levels(n);
     c->ly.last.levels = levels;
-    const WorkPlan w(n, levels);
-    HIPCHK(c, ensure(c->ly.work, w.bytes));
+    OvlLayoutArgs g{};
+    Carve size;
+    lay_layout_work(size, g, n, levels);
+    HIPCHK(c, ensure(c->ly.work, size.at));
     if (temp) HIPCHK(c, ensure(c->ly.temp, temp));
     if (o.bases && in.total > 0) HIPCHK(c, ensure(c->ly.bases, (size_t)in.total));
-    char* base = as<char>(c->ly.work);
-    OvlLayoutArgs g{};
+    Carve w(c->ly.work.p);
+    lay_layout_work(w, g, n, levels);
     g.n = n;
     g.levels = levels;
     g.n_pairs = in.n_pairs;
@@ -135,23 +134,6 @@ int run_layout(Dev* c, const DeviceColumns& in, int32_t min_score, int32_t min_o
     g.end = in.end;
     g.min_score = min_score;
     g.min_overlap = min_overlap;
-    g.best = reinterpret_cast<unsigned long long*>(base + w.best);
-    g.mk[0] = reinterpret_cast<unsigned long long*>(base + w.mk0);
-    g.mk[1] = reinterpret_cast<unsigned long long*>(base + w.mk1);
-    g.scan_in = reinterpret_cast<int64_t*>(base + w.mk0);
-    g.scan_out = reinterpret_cast<int64_t*>(base + w.mk1);
-    g.headkey = reinterpret_cast<unsigned long long*>(base + w.headkey);
-    g.c_off = reinterpret_cast<int64_t*>(base + w.c_off);
-    g.link = reinterpret_cast<int32_t*>(base + w.link);
-    g.succ = reinterpret_cast<int32_t*>(base + w.succ);
-    g.tail[0] = reinterpret_cast<uint32_t*>(base + w.tail0);
-    g.tail[1] = reinterpret_cast<uint32_t*>(base + w.tail1);
-    g.contig = reinterpret_cast<int32_t*>(base + w.contig);
-    g.offset = reinterpret_cast<int32_t*>(base + w.offset);
-    g.jump = reinterpret_cast<int32_t*>(base + w.jump);
-    g.on_path = reinterpret_cast<uint8_t*>(base + w.on_path);
-    g.on_cycle = reinterpret_cast<uint8_t*>(base + w.on_cycle);
-    g.ctr = reinterpret_cast<unsigned long long*>(base + w.ctr);
     g.seqs = in.seqs;
     g.off = in.off;
     g.table = in.table;
@@ -211,18 +193,6 @@ int finish(StageCall& call, int rc) {
     call.done(ms[0] + ms[1] + ms[2] + ms[3]);
     return rc;
 }
-
-// From the first copy enqueued to the return: whichever way a device call leaves, the stream is drained before the
-// host memory its copies read or write (the call's own vectors, the caller's columns and outputs) can go away.
-// Declared after the vectors, so it goes first.
-struct StreamDrain {
-    hipStream_t s;
-    bool armed = true;
-    explicit StreamDrain(hipStream_t stream) : s(stream) {}
-    ~StreamDrain() {
-        if (armed) (void)hipStreamSynchronize(s);
-    }
-};
 
 }  // namespace
 
@@ -354,15 +324,16 @@ OVL_API int ovl_layout(ovl_ctx* ctx, const uint8_t* seqs, const int64_t* offsets
                           &total);
     if (rc != OVL_OK) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    // the upload block: lengths, offsets from the first read's, the bytes (when contigs are spelled), the columns
     const size_t N = (size_t)std::max(n_reads, 1), E = (size_t)n_pairs;
     const bool spell = bases && total > 0;
-    const size_t o_len = 0, o_off = al256(4 * N), o_seq = al256(o_off + 8 * (N + 1)),
-                 o_a = al256(o_seq + (spell ? (size_t)total : 0)), o_b = al256(o_a + 4 * E), o_s = al256(o_b + 4 * E),
-                 o_e = al256(o_s + 4 * E), in_bytes = al256(o_e + 4 * E);
-    size_t work = 0, temp = 0;
-    if ((rc = work_bytes(c, n_reads, total, spell, &work, &temp)) != OVL_OK) return rc;
-    if ((rc = check_fits(c, in_bytes + work)) != OVL_OK) return rc;
+    DeviceColumns d;
+    d.n = n_reads;
+    d.n_pairs = n_pairs;
+    d.total = total;
+    Carve size;
+    lay_upload(size, d, N, spell ? (size_t)total : 0, E);
+    size_t temp = 0;
+    if ((rc = layout_fits(c, size.at, n_reads, total, spell, &temp)) != OVL_OK) return rc;
     call.begin();
     c->ly.last = {};
     std::vector<int32_t> h_len(N, 0);
@@ -372,32 +343,23 @@ OVL_API int ovl_layout(ovl_ctx* ctx, const uint8_t* seqs, const int64_t* offsets
         h_off[(size_t)r + 1] = offsets[r + 1] - offsets[0];
     }
     hipStream_t s = c->stream;
-    HIPCHK(c, ensure(c->ly.in, in_bytes));
+    HIPCHK(c, ensure(c->ly.in, size.at));
     HIPCHK(c, c->ly.timer.arm(ctx->timing));
-    char* in = as<char>(c->ly.in);
+    Carve in(c->ly.in.p);
+    lay_upload(in, d, N, spell ? (size_t)total : 0, E);
     StreamDrain drain(s);
-    HIPCHK(c, hipMemcpyAsync(in + o_len, h_len.data(), 4 * N, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(in + o_off, h_off.data(), 8 * (N + 1), hipMemcpyHostToDevice, s));
-    if (spell) HIPCHK(c, hipMemcpyAsync(in + o_seq, seqs + offsets[0], (size_t)total, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(writable(d.len), h_len.data(), 4 * N, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(writable(d.off), h_off.data(), 8 * (N + 1), hipMemcpyHostToDevice, s));
+    if (spell)
+        HIPCHK(c, hipMemcpyAsync(writable(d.seqs), seqs + offsets[0], (size_t)total, hipMemcpyHostToDevice, s));
     if (E > 0) {
-        HIPCHK(c, hipMemcpyAsync(in + o_a, a, 4 * E, hipMemcpyHostToDevice, s));
-        HIPCHK(c, hipMemcpyAsync(in + o_b, b, 4 * E, hipMemcpyHostToDevice, s));
-        HIPCHK(c, hipMemcpyAsync(in + o_s, score, 4 * E, hipMemcpyHostToDevice, s));
-        HIPCHK(c, hipMemcpyAsync(in + o_e, end, 4 * E, hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipMemcpyAsync(writable(d.a), a, 4 * E, hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipMemcpyAsync(writable(d.b), b, 4 * E, hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipMemcpyAsync(writable(d.score), score, 4 * E, hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipMemcpyAsync(writable(d.end), end, 4 * E, hipMemcpyHostToDevice, s));
     }
     HIPCHK(c, c->ly.timer.mark(0, s));  // after the uploads; nothing is scored here
     HIPCHK(c, c->ly.timer.mark(1, s));
-    DeviceColumns d;
-    d.n = n_reads;
-    d.n_pairs = n_pairs;
-    d.total = total;
-    d.len = reinterpret_cast<const int32_t*>(in + o_len);
-    d.off = reinterpret_cast<const int64_t*>(in + o_off);
-    d.seqs = reinterpret_cast<const uint8_t*>(in + o_seq);
-    d.a = reinterpret_cast<const int32_t*>(in + o_a);
-    d.b = reinterpret_cast<const int32_t*>(in + o_b);
-    d.score = reinterpret_cast<const int32_t*>(in + o_s);
-    d.end = reinterpret_cast<const int32_t*>(in + o_e);
     rc = run_layout(c, d, min_score, min_overlap, temp,
                     Outputs{succ, link, contig, offset, on_path, bases, c_off, n_contigs});
     drain.armed = rc != OVL_OK;  // (a successful run_layout ends with the stream synchronised)
@@ -426,26 +388,6 @@ OVL_API int ovl_layout_candidates(ovl_ctx* ctx, int32_t match, int32_t mismatch,
     HIPCHK(c, hipSetDevice(c->device));
     const size_t E = (size_t)n_pairs;
     const bool spell = bases && total > 0;
-    const size_t o_s = 0, o_e = al256(4 * E), o_t = al256(o_e + 4 * E), in_bytes = al256(o_t + 256);
-    size_t work = 0, temp = 0;
-    if ((rc = work_bytes(c, n_reads, total, spell, &work, &temp)) != OVL_OK) return rc;
-    if ((rc = check_fits(c, in_bytes + work)) != OVL_OK) return rc;
-    call.begin();
-    c->ly.last = {};
-    hipStream_t s = c->stream;
-    HIPCHK(c, ensure(c->ly.in, in_bytes));
-    char* in = as<char>(c->ly.in);
-    StreamDrain drain(s);
-    // the resident reads are symbol codes: code k is the k-th byte value of the read set
-    HIPCHK(c, hipMemcpyAsync(in + o_t, ctx->hreads.inv, 256, hipMemcpyHostToDevice, s));
-    HIPCHK(c, c->ly.timer.arm(ctx->timing));
-    HIPCHK(c, c->ly.timer.mark(0, s));
-    if (n_pairs > 0) {
-        rc = launch_score(c, p, as<int32_t>(c->cand_a), as<int32_t>(c->cand_b), n_pairs, match, mismatch, indel,
-                          reinterpret_cast<int32_t*>(in + o_s), reinterpret_cast<int32_t*>(in + o_e), s);
-        if (rc != OVL_OK) return rc;
-    }
-    HIPCHK(c, c->ly.timer.mark(1, s));
     DeviceColumns d;
     d.n = n_reads;
     d.n_pairs = n_pairs;
@@ -453,11 +395,28 @@ OVL_API int ovl_layout_candidates(ovl_ctx* ctx, int32_t match, int32_t mismatch,
     d.len = as<int32_t>(c->len);
     d.off = as<int64_t>(c->off);
     d.seqs = as<uint8_t>(c->codes);
-    d.table = reinterpret_cast<const uint8_t*>(in + o_t);
     d.a = as<int32_t>(c->cand_a);
     d.b = as<int32_t>(c->cand_b);
-    d.score = reinterpret_cast<const int32_t*>(in + o_s);
-    d.end = reinterpret_cast<const int32_t*>(in + o_e);
+    Carve size;
+    lay_scored(size, d, E);
+    size_t temp = 0;
+    if ((rc = layout_fits(c, size.at, n_reads, total, spell, &temp)) != OVL_OK) return rc;
+    call.begin();
+    c->ly.last = {};
+    hipStream_t s = c->stream;
+    HIPCHK(c, ensure(c->ly.in, size.at));
+    Carve in(c->ly.in.p);
+    lay_scored(in, d, E);
+    StreamDrain drain(s);
+    // the resident reads are symbol codes: code k is the k-th byte value of the read set
+    HIPCHK(c, hipMemcpyAsync(writable(d.table), ctx->hreads.inv, 256, hipMemcpyHostToDevice, s));
+    HIPCHK(c, c->ly.timer.arm(ctx->timing));
+    HIPCHK(c, c->ly.timer.mark(0, s));
+    if (n_pairs > 0) {
+        rc = launch_score(c, p, d.a, d.b, n_pairs, match, mismatch, indel, writable(d.score), writable(d.end), s);
+        if (rc != OVL_OK) return rc;
+    }
+    HIPCHK(c, c->ly.timer.mark(1, s));
     rc = run_layout(c, d, min_score, min_overlap, temp,
                     Outputs{succ, link, contig, offset, on_path, bases, c_off, n_contigs});
     drain.armed = rc != OVL_OK;

@@ -21,7 +21,8 @@ OVL_API int ovl_align_one(ovl_ctx* ctx, int32_t a, int32_t b, int32_t match, int
     HIPCHK(c, hipMemcpy(offs[1], as<int64_t>(c->off) + b, 2 * sizeof(int64_t), hipMemcpyDeviceToHost));
     const int64_t n = offs[0][1] - offs[0][0], m = offs[1][1] - offs[1][0];
     const size_t cells = (size_t)(n + 1) * (size_t)(m + 1);
-    int32_t idx[2] = {a, b};
+    int32_t idx[2] = {a, b}, res[2];
+    StreamDrain drain(c->stream);
     HIPCHK(c, ensure(c->a, sizeof(int32_t) * 2));
     HIPCHK(c, ensure(c->score, sizeof(int32_t) * 2));
     if (traceback) {
@@ -51,10 +52,10 @@ OVL_API int ovl_align_one(ovl_ctx* ctx, int32_t a, int32_t b, int32_t match, int
     g.wide = !(indel > INT32_MIN && M < (int64_t(1) << 31) && (2 * L + 1) * M < (int64_t(1) << 31));
     g.band = -1;
     HIPCHK(c, ovl_launch_dp(&g, c->stream));
-    int32_t res[2];
     HIPCHK(c, hipMemcpyAsync(res, c->score.p, sizeof(res), hipMemcpyDeviceToHost, c->stream));
     if (traceback) HIPCHK(c, hipMemcpyAsync(traceback, c->tb.p, cells, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    drain.armed = false;
     *out_score = res[0];
     *out_end = res[1];
     return OVL_OK;
@@ -100,6 +101,9 @@ OVL_API int ovl_local_align(ovl_ctx* ctx, const uint8_t* query, int32_t n, const
     }
     HIPCHK(c, ensure(c->l_best, 16));
     if (ops) HIPCHK(c, ensure(c->l_tb, tb_bytes));
+    unsigned long long key = 0;
+    uint32_t flag = 0;
+    StreamDrain drain(s);
     HIPCHK(c, hipMemcpyAsync(c->l_q.p, query, (size_t)n, hipMemcpyHostToDevice, s));
     HIPCHK(c, hipMemcpyAsync(c->l_r.p, ref, (size_t)m, hipMemcpyHostToDevice, s));
     HIPCHK(c, hipMemsetAsync(c->l_best.p, 0, 16, s));
@@ -110,11 +114,10 @@ OVL_API int ovl_local_align(ovl_ctx* ctx, const uint8_t* query, int32_t n, const
     HIPCHK(c, ovl_launch_local(as<uint8_t>(c->l_q), n, as<uint8_t>(c->l_r), m, match, mismatch, indel, wide,
                                as<uint64_t>(c->l_row), ops ? as<int8_t>(c->l_tb) : nullptr,
                                as<unsigned long long>(c->l_best), as<uint32_t>(c->err_flag), blocks, c->l_epoch, s));
-    unsigned long long key = 0;
-    uint32_t flag = 0;
     HIPCHK(c, hipMemcpyAsync(&key, c->l_best.p, sizeof(key), hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipMemcpyAsync(&flag, c->err_flag.p, sizeof(flag), hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
+    drain.armed = false;  // (the table's corner below goes into the device's own pinned buffer)
     if (flag) {
         HIPCHK(c, hipMemset(c->err_flag.p, 0, sizeof(uint32_t)));
         return fail(c, OVL_E_HIP, "local alignment: a row hand-off timed out (flag %u)", flag);
@@ -304,6 +307,10 @@ OVL_API int ovl_local_align_batch(ovl_ctx* ctx, const uint8_t* queries, const in
     }
     if (!batch.empty()) {
         LocalBatchRun run;
+        std::vector<OvlLocalBatchRecord> res(batch.size());
+        std::vector<int8_t> packed;
+        unsigned long long ctr[2] = {0, 0};
+        StreamDrain drain(c->stream);  // (local_batch_launch returns with the blob's copy in flight)
         // |indel| < 2^30 here: wider scorings went to `single`
         const int rl = local_batch_launch(ctx, c, queries, q_off, batch, reference, ref_len, nullptr, ops != nullptr,
                                           match, mismatch, (int32_t)indel, &run);
@@ -311,8 +318,6 @@ OVL_API int ovl_local_align_batch(ovl_ctx* ctx, const uint8_t* queries, const in
         hipStream_t s = c->stream;
         const int32_t nb = run.nb;
         const int64_t nm_sum = run.nm_sum;
-        std::vector<OvlLocalBatchRecord> res((size_t)nb);
-        unsigned long long ctr[2] = {0, 0};
         HIPCHK(c, hipMemcpyAsync(res.data(), c->lb.out.p, res.size() * sizeof(res[0]), hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipMemcpyAsync(ctr, c->lb.ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipStreamSynchronize(s));
@@ -321,11 +326,12 @@ OVL_API int ovl_local_align_batch(ovl_ctx* ctx, const uint8_t* queries, const in
         if (total > (unsigned long long)nm_sum)
             return fail(c, OVL_E_INTERNAL, "batched local alignment: %llu ops for a capacity of %lld", total,
                         (long long)nm_sum);
-        std::vector<int8_t> packed((size_t)total);
+        packed.resize((size_t)total);
         if (total) {
             HIPCHK(c, hipMemcpyAsync(packed.data(), c->lb.ops.p, (size_t)total, hipMemcpyDeviceToHost, s));
             HIPCHK(c, hipStreamSynchronize(s));
         }
+        drain.armed = false;
         for (int32_t b = 0; b < nb; ++b) {
             const int32_t k = batch[b].k;
             const OvlLocalBatchRecord& o = res[(size_t)b];

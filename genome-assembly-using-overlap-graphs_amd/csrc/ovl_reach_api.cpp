@@ -85,6 +85,7 @@ OVL_API int ovl_reach_reduce(ovl_ctx* ctx, const int64_t* off, const int32_t* he
     reach_mark_order(off, n_nodes, order);
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
+    StreamDrain drain(s);
     HIPCHK(c, ensure(c->rc.matrix, matrix_bytes));  // (ahead of the timed launches; reach_launches finds them made)
     HIPCHK(c, ensure(c->rc.pivot, sizeof(uint64_t) * 64 * (size_t)words));
     HIPCHK(c, ensure(c->rc.off, sizeof(int64_t) * ((size_t)n_nodes + 1)));
@@ -113,6 +114,7 @@ OVL_API int ovl_reach_reduce(ovl_ctx* ctx, const int64_t* off, const int32_t* he
     HIPCHK(c, hipMemcpyAsync(reduced, c->rc.out.p, (size_t)n_edges, hipMemcpyDeviceToHost, s));
     if (closure) HIPCHK(c, hipMemcpyAsync(closure, c->rc.matrix.p, matrix_bytes, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
+    drain.armed = false;
     int64_t count = 0;
     for (int64_t e = 0; e < n_edges; ++e) count += reduced[e];
     *n_reduced = count;

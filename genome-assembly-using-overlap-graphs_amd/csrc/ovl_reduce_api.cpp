@@ -79,6 +79,7 @@ OVL_API int ovl_transitive_reduce(ovl_ctx* ctx, const int64_t* off, const int32_
     while (group < 64 && group * kReduceLoads < mean) group *= 2;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
+    StreamDrain drain(s);
     HIPCHK(c, ensure(c->tr.off, sizeof(int64_t) * ((size_t)n_nodes + 1)));
     HIPCHK(c, ensure(c->tr.edge, sizeof(int2) * (size_t)n_edges));
     HIPCHK(c, ensure(c->tr.order, sizeof(int32_t) * order.size()));
@@ -106,6 +107,7 @@ OVL_API int ovl_transitive_reduce(ovl_ctx* ctx, const int64_t* off, const int32_
     HIPCHK(c, c->tr.timer.mark(1, s));
     HIPCHK(c, hipMemcpyAsync(reduced, c->tr.out.p, (size_t)n_edges, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
+    drain.armed = false;
     int64_t count = 0;
     for (int64_t e = 0; e < n_edges; ++e) count += reduced[e];
     *n_reduced = count;

@@ -5,6 +5,33 @@
 #include "ovl_ctx.h"
 #include "ovl_spectrum.h"
 
+// The call's upload: the reads' offsets from the first read's, their windows' offsets, the bytes.  (This block and the
+// next are not in the namespace below: tests/c/stage_block_check.cpp carves them without a device.)
+void lay_spectrum_in(Carve& b, OvlSpectrumArgs& g, int32_t n_reads, int64_t total) {
+    const size_t N = (size_t)std::max(n_reads, 1);
+    g.off = b.take<int64_t>(N + 1);
+    g.woff = b.take<int64_t>(N + 1);
+    g.seqs = b.take<uint8_t>((size_t)std::max<int64_t>(total, 1));
+}
+
+// The tables beside the upload; returns the last, the sort's and the scan's scratch.
+void* lay_spectrum_work(Carve& w, OvlSpectrumArgs& g, int32_t n_reads, int64_t n_win, int64_t total, size_t temp_bytes,
+                        bool correct) {
+    const size_t W = (size_t)std::max<int64_t>(n_win, 1), N = (size_t)std::max(n_reads, 1);
+    g.keys = w.take<uint64_t>(W + 1);  // the windows' keys; after the sort, the spectrum's keys
+    g.spec_keys = g.keys;              // (the scatter reads `sorted`: the unsorted keys are done with)
+    g.sorted = w.take<uint64_t>(W);
+    g.flag = w.take<int32_t>(W);
+    g.pos = w.take<int32_t>(W);
+    g.starts = w.take<int32_t>(W + 2);
+    g.spec_counts = w.take<int32_t>(W + 1);
+    g.hist = w.take<uint32_t>((size_t)kSpecHistBins);
+    g.ctr = w.take<unsigned long long>(8);
+    g.out = w.take<uint8_t>(correct ? (size_t)std::max<int64_t>(total, 1) : 1);
+    g.changed = w.take<int32_t>(correct ? N : 1);
+    return w.take<char>(temp_bytes);
+}
+
 namespace {
 
 constexpr int64_t kSpecMax = int64_t(1) << 31;
@@ -101,40 +128,6 @@ int32_t threshold_of_hist(const uint32_t* h, int32_t bins, int32_t most) {
     }
 }
 
-inline size_t al256(size_t x) { return (x + 255) & ~size_t(255); }
-
-// The device block beside the upload: where each table starts, and its bytes.
-struct WorkPlan {
-    size_t keys, sorted, flag, pos, starts, counts, hist, ctr, out, changed, temp, bytes;
-    WorkPlan(int32_t n_reads, int64_t n_win, int64_t total, size_t temp_bytes, bool correct) {
-        const size_t W = (size_t)std::max<int64_t>(n_win, 1), N = (size_t)std::max(n_reads, 1);
-        size_t at = 0;
-        auto take = [&](size_t b) {
-            const size_t o = at;
-            at = al256(at + b);
-            return o;
-        };
-        keys = take(8 * (W + 1));  // the windows' keys; after the sort, the spectrum's keys
-        sorted = take(8 * W);
-        flag = take(4 * W);
-        pos = take(4 * W);
-        starts = take(4 * (W + 2));
-        counts = take(4 * (W + 1));
-        hist = take(4 * (size_t)kSpecHistBins);
-        ctr = take(64);
-        out = take(correct ? (size_t)std::max<int64_t>(total, 1) : 1);
-        changed = take(correct ? 4 * N : 4);
-        temp = take(temp_bytes);
-        bytes = at;
-    }
-};
-
-struct StreamDrain {
-    hipStream_t s;
-    explicit StreamDrain(hipStream_t stream) : s(stream) {}
-    ~StreamDrain() { (void)hipStreamSynchronize(s); }
-};
-
 // Uploads the reads and runs the key, sort and count passes: on return the stream is synchronised, g describes the
 // spectrum in device memory (n_distinct, spec_keys, spec_counts, hist) and ctr holds the device's counters.
 int device_spectrum(ovl_ctx* ctx, Dev* c, const char* what, const uint8_t* seqs, const int64_t* offsets,
@@ -145,50 +138,34 @@ int device_spectrum(ovl_ctx* ctx, Dev* c, const char* what, const uint8_t* seqs,
     const size_t N = (size_t)std::max(n_reads, 1);
     size_t temp = 0;
     if (n_win > 0) HIPCHK(c, ovl_spectrum_temp_bytes(n_win, k, &temp));
-    const WorkPlan w(n_reads, n_win, total, temp, correct);
-    const size_t o_off = 0, o_woff = al256(8 * (N + 1)), o_seq = al256(o_woff + 8 * (N + 1)),
-                 in_bytes = al256(o_seq + (size_t)std::max<int64_t>(total, 1));
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
-    if (in_bytes + w.bytes > free_b + c->sp.in.bytes + c->sp.work.bytes)
-        return fail(c, OVL_E_UNSUPPORTED, "%s: %zu bytes of keys and tables do not fit the device (%zu free)", what,
-                    in_bytes + w.bytes, free_b + c->sp.in.bytes + c->sp.work.bytes);
+    *g = OvlSpectrumArgs{};
+    Carve in_size, work_size;
+    lay_spectrum_in(in_size, *g, n_reads, total);
+    lay_spectrum_work(work_size, *g, n_reads, n_win, total, temp, correct);
+    const int rc = check_fits(c, what, "keys and tables", in_size.at + work_size.at, {&c->sp.in, &c->sp.work});
+    if (rc != OVL_OK) return rc;
     std::vector<int64_t> h_off(N + 1, 0), h_woff(N + 1, 0);
     for (int32_t r = 0; r < n_reads; ++r) {
         h_off[(size_t)r + 1] = offsets[r + 1] - offsets[0];
         h_woff[(size_t)r + 1] = h_woff[(size_t)r] + std::max<int64_t>(offsets[r + 1] - offsets[r] - k + 1, 0);
     }
-    HIPCHK(c, ensure(c->sp.in, in_bytes));
-    HIPCHK(c, ensure(c->sp.work, w.bytes));
+    HIPCHK(c, ensure(c->sp.in, in_size.at));
+    HIPCHK(c, ensure(c->sp.work, work_size.at));
     HIPCHK(c, c->sp.timer.arm(ctx->timing));
-    char* in = as<char>(c->sp.in);
-    char* base = as<char>(c->sp.work);
+    Carve in(c->sp.in.p), work(c->sp.work.p);
+    lay_spectrum_in(in, *g, n_reads, total);
+    void* d_temp = lay_spectrum_work(work, *g, n_reads, n_win, total, temp, correct);
     StreamDrain drain(s);  // the copies read this call's vectors: drained whichever way the routine leaves
-    HIPCHK(c, hipMemcpyAsync(in + o_off, h_off.data(), 8 * (N + 1), hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(in + o_woff, h_woff.data(), 8 * (N + 1), hipMemcpyHostToDevice, s));
-    if (total > 0) HIPCHK(c, hipMemcpyAsync(in + o_seq, seqs + offsets[0], (size_t)total, hipMemcpyHostToDevice, s));
-    *g = OvlSpectrumArgs{};
+    HIPCHK(c, hipMemcpyAsync(writable(g->off), h_off.data(), 8 * (N + 1), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(writable(g->woff), h_woff.data(), 8 * (N + 1), hipMemcpyHostToDevice, s));
+    if (total > 0)
+        HIPCHK(c, hipMemcpyAsync(writable(g->seqs), seqs + offsets[0], (size_t)total, hipMemcpyHostToDevice, s));
     g->n_reads = n_reads;
     g->k = k;
     g->max_win = std::max(max_win, 1);
     g->ballot = c->k.spec_ballot;
     g->bins = c->k.spec_bins ? c->k.spec_bins : kSpecHistBins;
     g->n_win = n_win;
-    g->seqs = reinterpret_cast<const uint8_t*>(in + o_seq);
-    g->off = reinterpret_cast<const int64_t*>(in + o_off);
-    g->woff = reinterpret_cast<const int64_t*>(in + o_woff);
-    g->keys = reinterpret_cast<uint64_t*>(base + w.keys);
-    g->spec_keys = g->keys;  // the scatter reads `sorted`: the unsorted keys are done with
-    g->sorted = reinterpret_cast<uint64_t*>(base + w.sorted);
-    g->flag = reinterpret_cast<int32_t*>(base + w.flag);
-    g->pos = reinterpret_cast<int32_t*>(base + w.pos);
-    g->starts = reinterpret_cast<int32_t*>(base + w.starts);
-    g->spec_counts = reinterpret_cast<int32_t*>(base + w.counts);
-    g->hist = reinterpret_cast<uint32_t*>(base + w.hist);
-    g->ctr = reinterpret_cast<unsigned long long*>(base + w.ctr);
-    g->out = reinterpret_cast<uint8_t*>(base + w.out);
-    g->changed = reinterpret_cast<int32_t*>(base + w.changed);
-    void* d_temp = base + w.temp;
     HIPCHK(c, hipMemsetAsync(g->ctr, 0, 64, s));
     HIPCHK(c, hipMemsetAsync(g->hist, 0, 4 * (size_t)kSpecHistBins, s));
     HIPCHK(c, c->sp.timer.mark(0, s));
@@ -205,6 +182,7 @@ int device_spectrum(ovl_ctx* ctx, Dev* c, const char* what, const uint8_t* seqs,
     HIPCHK(c, c->sp.timer.mark(3, s));
     HIPCHK(c, hipMemcpyAsync(ctr, g->ctr, 64, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
+    drain.armed = false;
     // the key, sort and count passes' times (the count pass's includes the host's wait for the number of distinct
     // keys); ovl_last_timing has them from here, so that a call refused further on still reports them
     double* ms = c->sp.last.ms;
@@ -397,6 +375,7 @@ OVL_API int ovl_correct_reads(ovl_ctx* ctx, const uint8_t* seqs, const int64_t* 
         HIPCHK(c, hipMemcpyAsync(out_seqs + offsets[0], g.out, (size_t)total, hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipMemcpyAsync(out_changed, g.changed, 4 * (size_t)n_reads, hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipStreamSynchronize(s));
+        drain.armed = false;
         c->sp.last.ms[3] = c->sp.timer.ms(4, 5);
     } else {  // no read has a window: nothing to decide
         if (total > 0) memmove(out_seqs + offsets[0], seqs + offsets[0], (size_t)total);

@@ -12,6 +12,8 @@
 //     HIPCHK(c, st.timer.arm(ctx->timing));
 //     HIPCHK(c, st.timer.mark(0, s));  launch;  HIPCHK(c, st.timer.mark(1, s));  ... synchronise ...
 //     return call.done(st.timer.ms(0, 1));
+// Tables that share a buffer: one lay_*(Carve&, args) per block, run without a base to size it, then over the buffer.
+// Copies from or into host memory: a StreamDrain declared after that memory, disarmed after the last synchronise.
 #pragma once
 
 // The events of a stage's phases.  Made by the first call that has timing on, destroyed with the device.  With timing
@@ -71,6 +73,57 @@ int sync_devices(Ctx* ctx, int rc, const char* what) {
         if (rc == OVL_OK && e != hipSuccess) rc = fail(ctx, OVL_E_HIP, "%s: %s", what, hipGetErrorString(e));
     }
     return rc;
+}
+
+// From a call's first copy enqueued to its return: whichever way the call leaves, the stream is drained before the
+// host memory its copies read or write (the call's own vectors, the caller's arrays) can go away.  Declared in the
+// frame that owns that memory and after it, so it goes first; disarmed at the successful return, just after the call's
+// own last synchronise.
+struct StreamDrain {
+    hipStream_t s;
+    bool armed = true;
+    explicit StreamDrain(hipStream_t stream) : s(stream) {}
+    StreamDrain(const StreamDrain&) = delete;
+    StreamDrain& operator=(const StreamDrain&) = delete;
+    ~StreamDrain() {
+        if (armed) (void)hipStreamSynchronize(s);
+    }
+};
+
+inline size_t al256(size_t x) { return (x + 255) & ~size_t(255); }
+
+// A block of device tables laid out one after the other, each on a 256-byte boundary.  Without a base it sizes: take
+// returns NULL and only `at`, the block's bytes so far, moves.  With a buffer's address it places.
+struct Carve {
+    char* base = nullptr;
+    size_t at = 0;
+    Carve() = default;
+    explicit Carve(void* buffer) : base(static_cast<char*>(buffer)) {}
+    template <typename T>
+    T* take(size_t count) {
+        const size_t o = at;
+        at = al256(at + sizeof(T) * count);
+        return base ? static_cast<T*>(static_cast<void*>(base + o)) : nullptr;
+    }
+    // where a placed table starts in the block
+    size_t offset_of(const void* table) const { return (size_t)(static_cast<const char*>(table) - base); }
+};
+
+// A table the kernels only read (const in their argument struct), for the call that owns its block and fills it.
+template <typename T>
+T* writable(const T* p) { return const_cast<T*>(p); }
+
+// OVL_E_UNSUPPORTED when `need` bytes of a stage's buffers exceed what the device has free plus what those buffers
+// (`held`) hold already; `what` names the bytes in the message.
+inline int check_fits(const Dev* c, const char* stage, const char* what, size_t need,
+                      std::initializer_list<const DevBuf*> held) {
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
+    for (const DevBuf* b : held) free_b += b->bytes;
+    if (need > free_b)
+        return fail(c, OVL_E_UNSUPPORTED, "%s: %zu bytes of %s do not fit the device (%zu free)", stage, need, what,
+                    free_b);
+    return OVL_OK;
 }
 
 // ----------------------------------------------------------------------------- the stages' states
@@ -155,8 +208,9 @@ struct PlacedState {
 };
 
 // layout (ovl_layout_api.cpp): the call's inputs (ovl_layout: lengths, offsets, bytes and the four columns;
-// ovl_layout_candidates: the score and end columns and the code table), the per-read block (WorkPlan), the contigs'
-// bytes and the scan's scratch.  Marks: before and after the scoring launches, the link kernel, the forest, the spelling
+// ovl_layout_candidates: the score and end columns and the code table), the per-read block (lay_layout_work), the
+// contigs' bytes and the scan's scratch.  Marks: before and after the scoring launches, the link kernel, the forest,
+// the spelling
 struct LayoutState {
     DevBuf in, work, bases, temp;
     StageTimer<5> timer;
@@ -167,9 +221,9 @@ struct LayoutState {
     } last;
 };
 
-// read correction (ovl_spectrum_api.cpp): the call's upload (offsets, window offsets, bytes) and its tables (WorkPlan:
-// keys, sorted keys, head flags and their scan, run starts, counts, histogram, counters, outputs).  Marks: before the
-// keys, after them, the sort, the count pass; around the correction
+// read correction (ovl_spectrum_api.cpp): the call's upload (offsets, window offsets, bytes) and its tables
+// (lay_spectrum_work: keys, sorted keys, head flags and their scan, run starts, counts, histogram, counters, outputs).
+// Marks: before the keys, after them, the sort, the count pass; around the correction
 struct SpectrumState {
     DevBuf in, work;
     StageTimer<6> timer;
@@ -186,7 +240,7 @@ struct SpectrumState {
 struct UnitigsState {
     DevBuf in, node, edge, temp;
     int64_t kept = -1;  // kept edges in `edge` (ovl_unitigs_edges_copy), -1: none
-    size_t kept_at[4] = {};
+    const int32_t* kept_at[4] = {};  // their columns, placed
     StageTimer<5> timer;
     struct Last {
         int64_t edges = 0, kept = 0;  // ovl_last_unitigs

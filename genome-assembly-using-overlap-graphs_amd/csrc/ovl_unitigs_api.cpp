@@ -9,6 +9,52 @@
 #include "ovl_reach_host.h"
 #include "ovl_unitigs.h"
 
+// The device blocks of a call.  (Not in the namespace below: tests/c/stage_block_check.cpp carves them without a
+// device.)  The input block: the raw list's tables, then the reads with a second copy (n_sx of them: the candidate
+// form scores their self pairs; returned), the self columns (n_self entries each) and the score columns.
+int32_t* lay_unitigs_in(Carve& b, OvlUnitigArgs& g, int32_t n, int32_t n_raw, size_t n_sx, size_t n_self) {
+    const size_t N = (size_t)n, P = N > 0 ? N * (N - 1) : 0;
+    g.ids = b.take<int32_t>((size_t)n_raw);
+    g.prev = b.take<int32_t>((size_t)n_raw);
+    g.first = b.take<int32_t>(N);
+    g.self_ix = b.take<int32_t>(N);
+    int32_t* sx = b.take<int32_t>(n_sx);
+    g.self_score = b.take<int32_t>(n_self);
+    g.self_end = b.take<int32_t>(n_self);
+    g.score = b.take<int32_t>(P);
+    g.end = b.take<int32_t>(P);
+    return sx;
+}
+
+// The per-node block: degrees, offsets, the marking's order (returned), the node facts
+int32_t* lay_unitigs_node(Carve& b, OvlUnitigArgs& g, int32_t n) {
+    const size_t N = (size_t)n;
+    g.deg = b.take<int64_t>(N + 1);
+    g.off = b.take<int64_t>(N + 1);
+    int32_t* order = b.take<int32_t>(N);
+    g.outdeg = b.take<int32_t>(N);
+    g.indeg = b.take<int32_t>(N);
+    g.nxt = b.take<int32_t>(N);
+    g.nend = b.take<int32_t>(N);
+    return order;
+}
+
+// The per-edge block: the CSR's columns, the mask, the kept flags and their scan, the kept edges' columns
+void lay_unitigs_edge(Carve& b, OvlUnitigArgs& g, int64_t n_edges) {
+    const size_t E = (size_t)n_edges;
+    g.tail = b.take<int32_t>(E);
+    g.head = b.take<int32_t>(E);
+    g.weight = b.take<int32_t>(E);
+    g.eend = b.take<int32_t>(E);
+    g.reduced = b.take<uint8_t>(E);
+    g.keep = b.take<int32_t>(E + 1);
+    g.pos = b.take<int32_t>(E + 1);
+    g.k_tail = b.take<int32_t>(E);
+    g.k_head = b.take<int32_t>(E);
+    g.k_weight = b.take<int32_t>(E);
+    g.k_end = b.take<int32_t>(E);
+}
+
 namespace {
 
 constexpr int64_t kUnitigsMax = int64_t(1) << 31;
@@ -157,70 +203,41 @@ int finish_unitigs(const uint8_t* seqs, const int64_t* offsets, int32_t n, const
     return OVL_OK;
 }
 
-inline size_t al256(size_t x) { return (x + 255) & ~size_t(255); }
-
-// A block of device tables laid out one after the other, each 256-byte aligned.
-struct Block {
-    size_t at = 0;
-    size_t take(size_t bytes) {
-        const size_t o = at;
-        at = al256(at + bytes);
-        return o;
-    }
-};
-
-// From the first copy enqueued to the return: whichever way a device call leaves, the stream is drained before the
-// host memory its copies read or write can go away.  Declared after the vectors, so it goes first.
-struct StreamDrain {
-    hipStream_t s;
-    explicit StreamDrain(hipStream_t stream) : s(stream) {}
-    ~StreamDrain() { (void)hipStreamSynchronize(s); }
-};
-
-// Device bytes of a call with n nodes, `cols` bytes of inputs and at most max_edges edges: the per-node block, the
-// per-edge block (41 bytes per edge), the matrix and the pivot rows
-size_t device_bytes(int32_t n, size_t cols, int64_t max_edges) {
+// The fits check of a call with n nodes, in_bytes of inputs and at most max_edges edges: the per-node block, the
+// per-edge block and the scans' scratch at that many edges, the matrix and the pivot rows
+int unitigs_fits(Dev* c, size_t in_bytes, int32_t n, int64_t max_edges) {
+    Carve nb, eb;
+    OvlUnitigArgs g{};
+    lay_unitigs_node(nb, g, n);
+    lay_unitigs_edge(eb, g, max_edges);
+    size_t temp = 0;
+    HIPCHK(c, ovl_unitigs_scan_bytes(max_edges + 1, &temp));
     const size_t N = (size_t)std::max(n, 1), words = (N + 63) / 64;
-    return cols + 44 * N + 4096 + 41 * (size_t)max_edges + 8 * N * words + 8 * 64 * words;
-}
-
-int check_fits(Dev* c, size_t need) {
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
-    const size_t held = c->ug.in.bytes + c->ug.node.bytes + c->ug.edge.bytes + c->ug.temp.bytes + c->rc.matrix.bytes +
-                        c->rc.pivot.bytes;
-    if (need > free_b + held)
-        return fail(c, OVL_E_UNSUPPORTED, "unitigs: %zu bytes of columns, CSR and matrix do not fit the device (%zu free)",
-                    need, free_b + held);
-    return OVL_OK;
+    return check_fits(c, "unitigs", "columns, CSR and matrix",
+                      in_bytes + nb.at + eb.at + temp + 8 * N * words + 8 * 64 * words,
+                      {&c->ug.in, &c->ug.node, &c->ug.edge, &c->ug.temp, &c->rc.matrix, &c->rc.pivot});
 }
 
 // From the degree kernel to the outputs, on c->stream.  g holds the inputs' device addresses; the timer is armed and
-// marks 0 and 1 are recorded.  On return the stream is synchronised.
+// marks 0 and 1 are recorded.  On return the stream is drained, whichever way the routine leaves.
 int run_unitigs(Dev* c, OvlUnitigArgs g, const uint8_t* seqs, const int64_t* offsets, const Outputs& o) {
     hipStream_t s = c->stream;
     const int32_t n = g.n;
     const size_t N = (size_t)n;
     UnitigsState& st = c->ug;
     st.kept = -1;
-    Block nb;
-    const size_t o_deg = nb.take(8 * (N + 1)), o_off = nb.take(8 * (N + 1)), o_order = nb.take(4 * N),
-                 o_outdeg = nb.take(4 * N), o_indeg = nb.take(4 * N), o_nxt = nb.take(4 * N), o_nend = nb.take(4 * N);
-    HIPCHK(c, ensure(st.node, nb.at));
-    char* node = as<char>(st.node);
-    g.deg = reinterpret_cast<int64_t*>(node + o_deg);
-    g.off = reinterpret_cast<int64_t*>(node + o_off);
-    g.outdeg = reinterpret_cast<int32_t*>(node + o_outdeg);
-    g.indeg = reinterpret_cast<int32_t*>(node + o_indeg);
-    g.nxt = reinterpret_cast<int32_t*>(node + o_nxt);
-    g.nend = reinterpret_cast<int32_t*>(node + o_nend);
-    size_t temp = 0;
-    HIPCHK(c, ovl_unitigs_scan_bytes((int64_t)n + 1, &temp));
-    HIPCHK(c, ensure(st.temp, temp));
     std::vector<int64_t> h_off(N + 1, 0);
     std::vector<int32_t> order, facts(4 * N, 0);
     int32_t n_kept32 = 0;
     StreamDrain drain(s);
+    Carve node_size;
+    lay_unitigs_node(node_size, g, n);
+    HIPCHK(c, ensure(st.node, node_size.at));
+    Carve nb(st.node.p);
+    int32_t* d_order = lay_unitigs_node(nb, g, n);
+    size_t temp = 0;
+    HIPCHK(c, ovl_unitigs_scan_bytes((int64_t)n + 1, &temp));
+    HIPCHK(c, ensure(st.temp, temp));
     HIPCHK(c, hipMemsetAsync(g.deg, 0, 8 * (N + 1), s));
     HIPCHK(c, ovl_launch_unitigs_degree(&g, s));
     HIPCHK(c, ovl_launch_unitigs_offsets(&g, st.temp.p, st.temp.bytes, s));
@@ -230,26 +247,13 @@ int run_unitigs(Dev* c, OvlUnitigArgs g, const uint8_t* seqs, const int64_t* off
     if (E < 0 || E >= kUnitigsMax || E > (int64_t)n * n)
         return fail(c, OVL_E_INTERNAL, "unitigs: %lld edges from %d nodes", (long long)E, n);
     g.n_edges = E;
-    const size_t Ez = (size_t)E;
-    Block eb;
-    const size_t o_tail = eb.take(4 * Ez), o_head = eb.take(4 * Ez), o_w = eb.take(4 * Ez), o_e = eb.take(4 * Ez),
-                 o_red = eb.take(Ez), o_keep = eb.take(4 * (Ez + 1)), o_pos = eb.take(4 * (Ez + 1)),
-                 o_kt = eb.take(4 * Ez), o_kh = eb.take(4 * Ez), o_kw = eb.take(4 * Ez), o_ke = eb.take(4 * Ez);
-    HIPCHK(c, ensure(st.edge, eb.at));
+    Carve edge_size;
+    lay_unitigs_edge(edge_size, g, E);
+    HIPCHK(c, ensure(st.edge, edge_size.at));
     HIPCHK(c, ovl_unitigs_scan_bytes(E + 1, &temp));
     HIPCHK(c, ensure(st.temp, temp));
-    char* edge = as<char>(st.edge);
-    g.tail = reinterpret_cast<int32_t*>(edge + o_tail);
-    g.head = reinterpret_cast<int32_t*>(edge + o_head);
-    g.weight = reinterpret_cast<int32_t*>(edge + o_w);
-    g.eend = reinterpret_cast<int32_t*>(edge + o_e);
-    g.reduced = reinterpret_cast<uint8_t*>(edge + o_red);
-    g.keep = reinterpret_cast<int32_t*>(edge + o_keep);
-    g.pos = reinterpret_cast<int32_t*>(edge + o_pos);
-    g.k_tail = reinterpret_cast<int32_t*>(edge + o_kt);
-    g.k_head = reinterpret_cast<int32_t*>(edge + o_kh);
-    g.k_weight = reinterpret_cast<int32_t*>(edge + o_kw);
-    g.k_end = reinterpret_cast<int32_t*>(edge + o_ke);
+    Carve eb(st.edge.p);
+    lay_unitigs_edge(eb, g, E);
     HIPCHK(c, ovl_launch_unitigs_fill(&g, s));
     HIPCHK(c, st.timer.mark(2, s));
     const int32_t words = (int32_t)((N + 63) / 64);
@@ -258,12 +262,12 @@ int run_unitigs(Dev* c, OvlUnitigArgs g, const uint8_t* seqs, const int64_t* off
         // the marking's order from the downloaded offsets: 8 bytes per node, the one synchronisation above
         reach_mark_order(h_off.data(), n, order);
         if (!order.empty())
-            HIPCHK(c, hipMemcpyAsync(node + o_order, order.data(), 4 * order.size(), hipMemcpyHostToDevice, s));
-        HIPCHK(c, hipMemsetAsync(g.reduced, 0, Ez, s));  // (nodes with one out-edge keep it)
+            HIPCHK(c, hipMemcpyAsync(d_order, order.data(), 4 * order.size(), hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipMemsetAsync(g.reduced, 0, (size_t)E, s));  // (nodes with one out-edge keep it)
         OvlReachArgs a{};
         a.off = g.off;
         a.head = g.head;
-        a.order = reinterpret_cast<const int32_t*>(node + o_order);
+        a.order = d_order;
         a.n_nodes = n;
         a.n_order = (int32_t)order.size();
         a.words = words;
@@ -272,8 +276,9 @@ int run_unitigs(Dev* c, OvlUnitigArgs g, const uint8_t* seqs, const int64_t* off
         if (rc != OVL_OK) return rc;
     }
     HIPCHK(c, st.timer.mark(3, s));
-    HIPCHK(c, hipMemsetAsync(g.outdeg, 0, o_nxt - o_outdeg, s));
-    HIPCHK(c, hipMemsetAsync(g.nxt, 0xFF, nb.at - o_nxt, s));
+    // the node facts start as {outdeg, indeg} = 0 and {nxt, nend} = -1, each pair with its padding in one fill
+    HIPCHK(c, hipMemsetAsync(g.outdeg, 0, nb.offset_of(g.nxt) - nb.offset_of(g.outdeg), s));
+    HIPCHK(c, hipMemsetAsync(g.nxt, 0xFF, nb.at - nb.offset_of(g.nxt), s));
     HIPCHK(c, ovl_launch_unitigs_facts(&g, s));
     HIPCHK(c, ovl_launch_unitigs_kept(&g, st.temp.p, st.temp.bytes, s));
     HIPCHK(c, st.timer.mark(4, s));
@@ -282,46 +287,29 @@ int run_unitigs(Dev* c, OvlUnitigArgs g, const uint8_t* seqs, const int64_t* off
         HIPCHK(c, hipMemcpyAsync(facts.data() + (size_t)i * N, d_fact[i], 4 * N, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipMemcpyAsync(&n_kept32, g.pos + E, 4, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
+    drain.armed = false;
     if (n_kept32 < 0 || n_kept32 > E)
         return fail(c, OVL_E_INTERNAL, "unitigs: %d kept edges of %lld", n_kept32, (long long)E);
     st.kept = n_kept32;
-    st.kept_at[0] = o_kt;
-    st.kept_at[1] = o_kh;
-    st.kept_at[2] = o_kw;
-    st.kept_at[3] = o_ke;
+    const int32_t* kept_at[4] = {g.k_tail, g.k_head, g.k_weight, g.k_end};
+    std::copy(kept_at, kept_at + 4, st.kept_at);
     for (int i = 0; i < 4; ++i) st.last.ms[i] = st.timer.ms(i, i + 1);
     return finish_unitigs(seqs, offsets, n, facts.data(), facts.data() + N, facts.data() + 2 * N, facts.data() + 3 * N, E,
                           n_kept32, o, &st.last);
 }
 
-// the raw list's tables at the head of the input block: ids, prev, first, self_ix
-struct RawPlan {
-    size_t ids, prev, first, self_ix;
-    RawPlan(Block& b, int32_t n, int32_t n_raw) {
-        ids = b.take(4 * (size_t)n_raw);
-        prev = b.take(4 * (size_t)n_raw);
-        first = b.take(4 * (size_t)n);
-        self_ix = b.take(4 * (size_t)n);
-    }
-};
-
-int upload_raw(Dev* c, char* in, const RawPlan& r, const int32_t* ids, int32_t n_raw, const RawFacts& f,
-               const std::vector<int32_t>& self_ix, OvlUnitigArgs* g, hipStream_t s) {
-    const size_t n = f.first.size();
+// the raw list's tables into the placed input block
+int upload_raw(Dev* c, const OvlUnitigArgs& g, const int32_t* ids, const RawFacts& f,
+               const std::vector<int32_t>& self_ix, hipStream_t s) {
+    const size_t n = (size_t)g.n, n_raw = (size_t)g.n_raw;
     if (n_raw > 0) {
-        HIPCHK(c, hipMemcpyAsync(in + r.ids, ids, 4 * (size_t)n_raw, hipMemcpyHostToDevice, s));
-        HIPCHK(c, hipMemcpyAsync(in + r.prev, f.prev.data(), 4 * (size_t)n_raw, hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipMemcpyAsync(writable(g.ids), ids, 4 * n_raw, hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipMemcpyAsync(writable(g.prev), f.prev.data(), 4 * n_raw, hipMemcpyHostToDevice, s));
     }
     if (n > 0) {
-        HIPCHK(c, hipMemcpyAsync(in + r.first, f.first.data(), 4 * n, hipMemcpyHostToDevice, s));
-        HIPCHK(c, hipMemcpyAsync(in + r.self_ix, self_ix.data(), 4 * n, hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipMemcpyAsync(writable(g.first), f.first.data(), 4 * n, hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipMemcpyAsync(writable(g.self_ix), self_ix.data(), 4 * n, hipMemcpyHostToDevice, s));
     }
-    g->n = (int32_t)n;
-    g->n_raw = n_raw;
-    g->ids = reinterpret_cast<const int32_t*>(in + r.ids);
-    g->prev = reinterpret_cast<const int32_t*>(in + r.prev);
-    g->first = reinterpret_cast<const int32_t*>(in + r.first);
-    g->self_ix = reinterpret_cast<const int32_t*>(in + r.self_ix);
     return OVL_OK;
 }
 
@@ -465,11 +453,12 @@ OVL_API int ovl_unitigs(ovl_ctx* ctx, const uint8_t* seqs, const int64_t* offset
     HIPCHK(c, hipSetDevice(c->device));
     const size_t N = (size_t)n_reads, P = N > 0 ? N * (N - 1) : 0;
     const bool self = !f.self.empty();
-    Block b;
-    const RawPlan raw(b, n_reads, n_raw);
-    const size_t o_ss = b.take(self ? 4 * N : 0), o_se = b.take(self ? 4 * N : 0), o_s = b.take(4 * P),
-                 o_e = b.take(4 * P);
-    if ((rc = check_fits(c, device_bytes(n_reads, b.at, f.max_edges))) != OVL_OK) return rc;
+    OvlUnitigArgs g{};
+    g.n = n_reads;
+    g.n_raw = n_raw;
+    Carve size;
+    lay_unitigs_in(size, g, n_reads, n_raw, 0, self ? N : 0);
+    if ((rc = unitigs_fits(c, size.at, n_reads, f.max_edges)) != OVL_OK) return rc;
     call.begin();
     c->ug.last = {};
     c->ug.kept = -1;
@@ -477,27 +466,24 @@ OVL_API int ovl_unitigs(ovl_ctx* ctx, const uint8_t* seqs, const int64_t* offset
     std::vector<int32_t> self_ix(N, -1);
     for (int32_t x : f.self) self_ix[(size_t)x] = x;
     hipStream_t s = c->stream;
-    HIPCHK(c, ensure(c->ug.in, b.at));
+    HIPCHK(c, ensure(c->ug.in, size.at));
     HIPCHK(c, c->ug.timer.arm(ctx->timing));
-    char* in = as<char>(c->ug.in);
-    OvlUnitigArgs g{};
+    Carve in(c->ug.in.p);
+    lay_unitigs_in(in, g, n_reads, n_raw, 0, self ? N : 0);
     StreamDrain drain(s);
-    if ((rc = upload_raw(c, in, raw, ids, n_raw, f, self_ix, &g, s)) != OVL_OK) return rc;
+    if ((rc = upload_raw(c, g, ids, f, self_ix, s)) != OVL_OK) return rc;
     if (self) {
-        HIPCHK(c, hipMemcpyAsync(in + o_ss, self_score, 4 * N, hipMemcpyHostToDevice, s));
-        HIPCHK(c, hipMemcpyAsync(in + o_se, self_end, 4 * N, hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipMemcpyAsync(writable(g.self_score), self_score, 4 * N, hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipMemcpyAsync(writable(g.self_end), self_end, 4 * N, hipMemcpyHostToDevice, s));
     }
     if (P > 0) {
-        HIPCHK(c, hipMemcpyAsync(in + o_s, score, 4 * P, hipMemcpyHostToDevice, s));
-        HIPCHK(c, hipMemcpyAsync(in + o_e, end, 4 * P, hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipMemcpyAsync(writable(g.score), score, 4 * P, hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipMemcpyAsync(writable(g.end), end, 4 * P, hipMemcpyHostToDevice, s));
     }
     HIPCHK(c, c->ug.timer.mark(0, s));  // after the uploads; nothing is scored here
     HIPCHK(c, c->ug.timer.mark(1, s));
-    g.self_score = reinterpret_cast<const int32_t*>(in + o_ss);
-    g.self_end = reinterpret_cast<const int32_t*>(in + o_se);
-    g.score = reinterpret_cast<const int32_t*>(in + o_s);
-    g.end = reinterpret_cast<const int32_t*>(in + o_e);
     rc = run_unitigs(c, g, seqs, offsets, o);
+    drain.armed = false;     // (run_unitigs drains the stream whichever way it leaves)
     c->ug.last.ms[0] = 0.0;  // (two marks with nothing between them)
     return finish(call, rc);
 }
@@ -525,11 +511,12 @@ OVL_API int ovl_unitigs_candidates(ovl_ctx* ctx, const uint8_t* seqs, const int3
     if ((rc = check_scoring_args(ctx, match, mismatch, indel, band, &p)) != OVL_OK) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t M = f.self.size();
-    Block b;
-    const RawPlan raw(b, n_reads, n_raw);
-    const size_t o_sx = b.take(4 * M), o_ss = b.take(4 * M), o_se = b.take(4 * M), o_s = b.take(4 * P),
-                 o_e = b.take(4 * P);
-    if ((rc = check_fits(c, device_bytes(n_reads, b.at, f.max_edges))) != OVL_OK) return rc;
+    OvlUnitigArgs g{};
+    g.n = n_reads;
+    g.n_raw = n_raw;
+    Carve size;
+    lay_unitigs_in(size, g, n_reads, n_raw, M, M);
+    if ((rc = unitigs_fits(c, size.at, n_reads, f.max_edges)) != OVL_OK) return rc;
     call.begin();
     c->ug.last = {};
     c->ug.kept = -1;
@@ -537,31 +524,28 @@ OVL_API int ovl_unitigs_candidates(ovl_ctx* ctx, const uint8_t* seqs, const int3
     std::vector<int32_t> self_ix(N, -1);
     for (size_t k = 0; k < M; ++k) self_ix[(size_t)f.self[k]] = (int32_t)k;
     hipStream_t s = c->stream;
-    HIPCHK(c, ensure(c->ug.in, b.at));
+    HIPCHK(c, ensure(c->ug.in, size.at));
     HIPCHK(c, c->ug.timer.arm(ctx->timing));
-    char* in = as<char>(c->ug.in);
-    OvlUnitigArgs g{};
+    Carve in(c->ug.in.p);
+    int32_t* d_sx = lay_unitigs_in(in, g, n_reads, n_raw, M, M);
     StreamDrain drain(s);
-    if ((rc = upload_raw(c, in, raw, ids, n_raw, f, self_ix, &g, s)) != OVL_OK) return rc;
-    if (M > 0) HIPCHK(c, hipMemcpyAsync(in + o_sx, f.self.data(), 4 * M, hipMemcpyHostToDevice, s));
+    if ((rc = upload_raw(c, g, ids, f, self_ix, s)) != OVL_OK) return rc;
+    if (M > 0) HIPCHK(c, hipMemcpyAsync(d_sx, f.self.data(), 4 * M, hipMemcpyHostToDevice, s));
     HIPCHK(c, c->ug.timer.mark(0, s));
-    int32_t* d_sx = reinterpret_cast<int32_t*>(in + o_sx);
     if (P > 0) {
         rc = launch_score(c, p, as<int32_t>(c->cand_a), as<int32_t>(c->cand_b), (int64_t)P, match, mismatch, indel,
-                          reinterpret_cast<int32_t*>(in + o_s), reinterpret_cast<int32_t*>(in + o_e), s);
+                          writable(g.score), writable(g.end), s);
         if (rc != OVL_OK) return rc;
     }
     if (M > 0) {  // the self pairs of the reads with a second copy, by the same scorer
-        rc = launch_score(c, p, d_sx, d_sx, (int64_t)M, match, mismatch, indel, reinterpret_cast<int32_t*>(in + o_ss),
-                          reinterpret_cast<int32_t*>(in + o_se), s);
+        rc = launch_score(c, p, d_sx, d_sx, (int64_t)M, match, mismatch, indel, writable(g.self_score),
+                          writable(g.self_end), s);
         if (rc != OVL_OK) return rc;
     }
     HIPCHK(c, c->ug.timer.mark(1, s));
-    g.self_score = reinterpret_cast<const int32_t*>(in + o_ss);
-    g.self_end = reinterpret_cast<const int32_t*>(in + o_se);
-    g.score = reinterpret_cast<const int32_t*>(in + o_s);
-    g.end = reinterpret_cast<const int32_t*>(in + o_e);
-    return finish(call, run_unitigs(c, g, seqs, offsets, o));
+    rc = run_unitigs(c, g, seqs, offsets, o);
+    drain.armed = false;  // (run_unitigs drains the stream whichever way it leaves)
+    return finish(call, rc);
 }
 
 OVL_API int ovl_unitigs_edges_copy(const ovl_ctx* ctx, int32_t* tail, int32_t* head, int32_t* weight, int32_t* end) {
@@ -577,11 +561,13 @@ OVL_API int ovl_unitigs_edges_copy(const ovl_ctx* ctx, int32_t* tail, int32_t* h
     if (c->ug.kept == 0) return OVL_OK;
     DeviceGuard guard;
     HIPCHK(c, hipSetDevice(c->device));
+    StreamDrain drain(c->stream);
     for (int i = 0; i < 4; ++i)
         if (out[i])
-            HIPCHK(c, hipMemcpyAsync(out[i], as<char>(c->ug.edge) + c->ug.kept_at[i], 4 * (size_t)c->ug.kept,
-                                     hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(out[i], c->ug.kept_at[i], 4 * (size_t)c->ug.kept, hipMemcpyDeviceToHost,
+                                     c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    drain.armed = false;
     return OVL_OK;
 }
 

@@ -22,6 +22,11 @@ def _reads(rng, n, lo=4, hi=12):
     return ["".join(rng.choice("ACGT") for _ in range(rng.randint(lo, hi))) for _ in range(n)]
 
 
+def random_reads(n, seed, lo=16, hi=24):
+    """n random ACGT reads of lo to hi bases."""
+    return _reads(random.Random(seed), n, lo, hi)
+
+
 def _case(name, reads, pairs, min_score=1, min_overlap=1, expect=None):
     cols = [[p[k] for p in pairs] for k in range(4)]
     return Case(name, reads, *cols, min_score, min_overlap, expect or {})

@@ -42,6 +42,24 @@ def test_device_form_equals_the_host_form(engine, host_results, case):
     _check_case(engine, host_results, case)
 
 
+def test_blocks_regrown_and_reused_equal_the_host_form():
+    """3 reads, then 70 (past one wavefront), then the 3 again, on one fresh engine: the upload and the tables are laid
+    out in new buffers, in regrown ones and inside buffers larger than they need.  With k = 4 and the rule's threshold
+    the 3 reads change 5 bases; with k = 5 and min_count 2 the 70 reads change 59 and tie at 21 (the host form)."""
+    from layout_cases import random_reads
+    from ovlgraph import OverlapEngine
+    from ovlgraph.correct import correct_reads, kmer_spectrum
+    small, big = random_reads(3, 20261021), random_reads(70, 20261022)
+    with OverlapEngine(0) as eng:
+        for reads in (small, big, small):
+            for k, min_count in ((4, "auto"), (5, 2)):
+                what = (len(reads), k)
+                assert_same_spectrum(kmer_spectrum(reads, k, engine=eng, form="device"),
+                                     kmer_spectrum(reads, k, form="host"), what)
+                assert_same(correct_reads(reads, k, min_count, engine=eng, form="device"),
+                            correct_reads(reads, k, min_count, form="host"), what)
+
+
 def test_three_slot_context_equals_the_host_form(host_results, monkeypatch):
     from ovlgraph import OverlapEngine
     monkeypatch.setenv("OVL_SHARE_DEVICES", "1")

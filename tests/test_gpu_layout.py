@@ -10,7 +10,8 @@ empty inputs.  The host results are computed once per module and shared."""
 import numpy as np
 import pytest
 
-from layout_cases import CASES, COUNTS, RawCall, assert_expect, assert_same, bad_calls, case_args, with_contigs
+from layout_cases import (CASES, COUNTS, RawCall, assert_expect, assert_same, bad_calls, case_args, random_reads,
+                          with_contigs)
 
 pytestmark = pytest.mark.gpu
 
@@ -37,6 +38,25 @@ def test_device_form_equals_the_host_form(engine, host_results, case):
     assert np.array_equal(got["c_off"], host_results[case.name]["c_off"])
     n = len(case.reads)
     assert got["levels"] == (0 if n <= 1 else (n - 1).bit_length())
+
+
+def test_blocks_regrown_and_reused_equal_the_host_form():
+    """3 reads, then 70 (past one wavefront), then the 3 again, on one fresh engine: the upload and the per-read block
+    are laid out in new buffers, in regrown ones and inside buffers larger than they need."""
+    import random
+    from ovlgraph import OverlapEngine
+    from ovlgraph.engine import layout_host
+    calls = []
+    for n in (3, 70):
+        g = random.Random(20261021 + n)
+        pairs = [(g.randrange(n), g.randrange(n), g.randint(0, 5), g.randint(0, 13)) for _ in range(10 * n)]
+        cols = [np.asarray([p[k] for p in pairs], np.int32) for k in range(4)]
+        calls.append((random_reads(n, 20261021 + n), *cols, 1, 1))
+    with OverlapEngine(0) as eng:
+        for args in (calls[0], calls[1], calls[0]):
+            got, want = with_contigs(eng.layout(*args)), with_contigs(layout_host(*args))
+            assert_same(got, want, len(args[0]))
+            assert np.array_equal(got["c_off"], want["c_off"]) and want["links"] > 0
 
 
 def test_plain_link_kernel_equals_the_runs_form(host_results, monkeypatch):

@@ -131,6 +131,22 @@ def test_a_larger_call_then_a_smaller_one(engine, raw_lists):
                            raw_lists[small][1], small)
 
 
+def test_blocks_regrown_and_reused_equal_the_host_form():
+    """3 reads, then 70 (past one wavefront; two words per matrix row), then the 3 again, on one fresh engine and
+    through both device calls: the input, node and edge blocks are laid out in new buffers, in regrown ones and inside
+    buffers larger than they need."""
+    from layout_cases import random_reads
+    from ovlgraph import OverlapEngine
+    from ovlgraph.unitigs import _run
+    small, big = random_reads(3, 20261021), random_reads(70, 20261022)
+    with OverlapEngine(0) as eng:
+        for raw in (small, big, small):
+            want = _run(raw, eng, None, False, None)[1]
+            assert want["n_edges"] > 0
+            assert_same_result(_run(raw, eng, None, True, None)[1], want, (len(raw), "ovl_unitigs_candidates"))
+            assert_same_result(_run(raw, eng, engine_scorer(eng), True, None)[1], want, (len(raw), "ovl_unitigs"))
+
+
 def test_several_marking_windows_per_node(raw_lists, monkeypatch):
     from ovlgraph import OverlapEngine
     from ovlgraph.unitigs import _run

@@ -281,6 +281,15 @@ def test_host_check_program_under_sanitizers():
     assert os.path.exists(os.path.join(CSRC, "..", "build", "unitigs_host_check"))
 
 
+def test_stage_block_check_program_under_sanitizers():
+    """The carver of ovl_stage.h and the device blocks of the layout, the read correction and this pipeline, sized and
+    then placed over host memory, as a stand-alone program under the same two sanitizers."""
+    import subprocess
+    from ovlgraph._lib import CSRC
+    out = subprocess.run(["make", "-s", "-C", CSRC, "stage-block-check"], capture_output=True, text=True)
+    assert out.returncode == 0 and "stage_block_check: ok" in out.stdout, out.stdout + out.stderr
+
+
 def test_exported_from_package():
     import ovlgraph
     from ovlgraph import unitigs
