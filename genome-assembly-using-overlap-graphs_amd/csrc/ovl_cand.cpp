@@ -296,14 +296,10 @@ int resident_call(ovl_ctx* ctx, int64_t lo, int64_t hi, int32_t match, int32_t m
             const int r = ensure_heavy(d);
             if (r != OVL_OK) return r;
         }
-        const int64_t t0 = lo / 64, t1 = t0 + (hi - lo + 63) / 64;
-        const auto k0 = std::lower_bound(d->h_heavy.begin(), d->h_heavy.end(), t0);
-        const auto k1 = std::lower_bound(d->h_heavy.begin(), d->h_heavy.end(), t1);
-        if (k1 > k0) {
-            rc_.heavy_ids = as<int32_t>(d->heavy_ids) + (k0 - d->h_heavy.begin());
-            rc_.heavy_n = (int64_t)(k1 - k0);
-            rc_.tile_base = t0;
-        }
+        const HeavyWindow w = heavy_window(d, lo, hi - lo);
+        rc_.heavy_ids = w.ids;
+        rc_.heavy_n = w.count;
+        rc_.tile_base = w.tile_base;
     }
     ResidentReads rd;
     rd.sfx = as<uint32_t>(d->sfx);
@@ -395,31 +391,12 @@ OVL_API int ovl_score_candidates_range(ovl_ctx* ctx, int64_t lo, int64_t hi, int
         if (rc != kResidentFellBack) return rc;
     }
     quiet(ctx);
-    const size_t bytes = sizeof(int32_t) * (size_t)(hi - lo);
-    Call C;
-    C.plan = &p;
-    C.match = match;
-    C.mismatch = mismatch;
-    C.indel = indel;
-    C.out_s = out_score;
-    C.out_e = out_end;
-    C.out_base = lo;
-    C.out_pinned = host_pinned(out_score, bytes) && host_pinned(out_end, bytes);
-    C.timing = ctx->timing != 0;
-    const int32_t S = devices_used(ctx, hi - lo);
-    C.pack = pack_ok(ctx, p, hi - lo, C.out_pinned, S);
+    int32_t S = 1;
+    const Call C = make_call(ctx, p, {match, mismatch, indel}, nullptr, nullptr, hi - lo, out_score, out_end, lo, &S);
     std::vector<int64_t> cuts;
     rc = device_cuts(d0, lo, hi, S, cuts);
     if (rc != OVL_OK) return rc;
-    std::vector<Job> jobs((size_t)S);
-    for (int32_t r = 0; r < S; ++r) {
-        Job& J = jobs[(size_t)r];
-        J.d = ctx->devs[(size_t)r];
-        J.lo = cuts[(size_t)r];
-        J.hi = cuts[(size_t)r + 1];
-        J.dev_a = as<int32_t>(J.d->cand_a);
-        J.dev_b = as<int32_t>(J.d->cand_b);
-    }
+    std::vector<Job> jobs = jobs_from_cuts(ctx, cuts, true);
     return run_pipeline(ctx, C, jobs);
 }
 

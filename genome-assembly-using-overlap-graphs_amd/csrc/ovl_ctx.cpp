@@ -185,7 +185,6 @@ hipError_t init_dev(Dev* d) {
     if (e != hipSuccess) return e;
     e = ensure(d->err_flag, 16);
     if (e != hipSuccess) return e;
-    d->cur_flag = as<uint32_t>(d->err_flag);
     return hipMemset(d->err_flag.p, 0, 16);
 }
 

@@ -64,6 +64,7 @@
 #include "ovl_worker.h"
 #include "ovl_digest.h"
 #include "ovl_score_range.h"
+#include "ovl_pair_layout.h"
 
 #define OVL_API extern "C" __attribute__((visibility("default")))
 
@@ -384,13 +385,9 @@ struct Dev {
     int64_t st_cap = 0;
     uint32_t* h_flag = nullptr;      // pinned error flag of host-array calls (the kernels store into it)
     uint32_t* h_flag_dev = nullptr;  // its device address
-    uint32_t* cur_flag = nullptr;    // the flag the next launches write: err_flag (device calls) or h_flag_dev
-    int32_t out_mode = 0;            // result sink of the next ungapped launches (OvlUngappedArgs::host_out):
-                                     // 0 HBM, 1 host-mapped int32 arrays, 2 host-mapped packed uint16
     std::vector<hipEvent_t> t_ev;  // timing: kernel start/end per chunk (recorded on the stream around the launch)
     std::vector<hipEvent_t> k_ev;  // timing: the same recorded by an ungapped launch itself (kernel start / end)
-    hipEvent_t kev_start = nullptr, kev_stop = nullptr;  // the next ungapped launch records these (then cleared)
-    // compact host pair lists (encode_chunk): pinned encoding buffer (8 bytes per pair + slack), its device
+    // compact host pair lists (encode_chunk): pinned encoding buffer (PairLayout::job_bytes), its device
     // address, a decode event per chunk, and the encoded bytes of the last call
     char* cp_host = nullptr;
     char* cp_dev = nullptr;
@@ -398,10 +395,6 @@ struct Dev {
     DevBuf cp_hbm;  // the in-place encoding's chunks copied into HBM (same layout as cp_host)
     std::vector<hipEvent_t> dec_ev;
     int64_t cp_link = 0;
-    // the next ungapped launch reads its pair list in the host encoding (OvlUngappedArgs::ix_*), or null
-    const uint16_t* ix_b16 = nullptr;
-    const uint8_t* ix_d8 = nullptr;
-    const int32_t* ix_base = nullptr;
     ResidentGrid res;  // the resident scoring grid (ovl_resident.h), launched by the first call that uses it
     std::unique_ptr<DevWorker> worker;  // multi-device contexts: this device's host thread (run_pipeline)
 };
@@ -416,10 +409,25 @@ struct Plan {
     bool seed_wide = true;
 };
 
+// What a scoring launch takes (launch_score): the scores, the pair list and the result arrays as the device addresses
+// them, and in LaunchIo everything else that differs between callers.  A default LaunchIo is a device call's: results
+// into HBM, the device's own error flag, int32 pair arrays, no kernel timing.
+struct Scoring { int32_t match = 0, mismatch = 0; int64_t indel = 0; };
+struct PairList { const int32_t* a = nullptr; const int32_t* b = nullptr; int64_t n = 0; };
+struct ScoreOut { int32_t* score = nullptr; int32_t* end = nullptr; };
+struct LaunchIo {
+    int32_t sink = 0;           // results (OvlUngappedArgs::host_out): 0 HBM, 1 host-mapped int32, 2 host-mapped packed
+    uint32_t* flag = nullptr;   // the error flag the kernels write; null: the device's err_flag
+    const uint16_t* ix_b16 = nullptr;  // non-null: the pair list in the host encoding, read in place instead of
+    const uint8_t* ix_d8 = nullptr;    // PairList's arrays (OvlUngappedArgs::ix_*; only a launch that ix_launch admits)
+    const int32_t* ix_base = nullptr;
+    hipEvent_t kev_start = nullptr, kev_stop = nullptr;  // timing: uniform_kernel records these itself, once
+    bool timed = false;         // out: it did (else the caller times the launch on the stream)
+};
+
 struct Call {
     const Plan* plan = nullptr;
-    int32_t match = 0, mismatch = 0;
-    int64_t indel = 0;
+    Scoring sc;
     const int32_t* h_a = nullptr;  // host pair list (global indexing), or null: device lists per job
     const int32_t* h_b = nullptr;
     bool in_pinned = false;
@@ -442,7 +450,6 @@ struct Job {
     std::vector<int64_t> cb; // chunk k: pairs [cb[k], cb[k + 1]) of the range (local indexing)
     int64_t nchunks = 0;
     int64_t n_packed = 0;    // C.pack: the first n_packed chunks are packed and staged
-    int64_t st_in_cap = 0, st_out_cap = 0;
     const int32_t* dev_a = nullptr;  // device pair list (global indexing) when the call has no host list
     const int32_t* dev_b = nullptr;
     int32_t* ka = nullptr;  // device copies of the host list (local indexing)
@@ -453,10 +460,11 @@ struct Job {
     int32_t* d_end = nullptr;
     std::vector<uint8_t> ixk;    // C.compact: chunk k's list is read in place by uniform_kernel (encode_chunk)
     std::vector<uint8_t> kexact; // timing: chunk k's kernel recorded its own start / end (k_ev)
-    std::vector<uint8_t> om;     // chunk k's result sink (OvlUngappedArgs::host_out): 1 int32, 2 packed
-    std::vector<uint8_t> slot;   // chunk k's staging slot: k % kSlots
     int64_t drained = 0;         // chunks [0, drained) are drained (run_pipeline)
 };
+
+inline int32_t chunk_sink(const Job& J, int64_t k) { return k < J.n_packed ? 2 : 1; }  // LaunchIo::sink of chunk k
+inline int chunk_slot(const Job&, int64_t k) { return (int)(k % kSlots); }              // its staging slot
 
 // OVL_TRACE_PIPE=1 (diagnostics): one stderr line per host-array call with the microsecond offsets of its
 // pipeline events (s setup, i<k> chunk k issued, w<k> its results ready on the host side, d<k> drained,
@@ -491,15 +499,22 @@ void free_staging(int32_t*& p);
 hipError_t alloc_staging(int32_t*& p, int32_t*& p_dev, int64_t cap);
 bool host_pinned(const void* p, size_t bytes);
 // ovl_plan.cpp
-int launch_score(Dev* c, const Plan& pl, const int32_t* d_a, const int32_t* d_b, int64_t n_pairs,
-                 int32_t match, int32_t mismatch, int64_t indel, int32_t* d_score, int32_t* d_end,
+int launch_score(Dev* c, const Plan& pl, const PairList& pairs, const Scoring& sc, const ScoreOut& out, LaunchIo& io,
                  hipStream_t s);
 int ensure_heavy(Dev* c);
+struct HeavyWindow {
+    const int32_t* ids = nullptr;  // device address of the window's ascending tile ids
+    int64_t count = 0, tile_base = 0;
+};
+HeavyWindow heavy_window(const Dev* c, int64_t lo, int64_t n_pairs);
 bool ix_launch(const Dev* c, int64_t n_pairs);
 int check_scoring_args(ovl_ctx* c, int32_t match, int32_t mismatch, int64_t indel, int32_t band, Plan* p);
 // ovl_pipeline.cpp
 void host_copy(void* dst, const void* src, size_t bytes);
 int run_pipeline(ovl_ctx* c, const Call& C, std::vector<Job>& jobs);
+Call make_call(ovl_ctx* c, const Plan& p, const Scoring& sc, const int32_t* h_a, const int32_t* h_b, int64_t n_pairs,
+               int32_t* out_s, int32_t* out_e, int64_t out_base, int32_t* n_devices);
+std::vector<Job> jobs_from_cuts(ovl_ctx* c, const std::vector<int64_t>& cuts, bool resident_list);
 int device_cuts(Dev* d, int64_t lo, int64_t hi, int32_t shards, std::vector<int64_t>& cuts);
 bool pack_ok(const ovl_ctx* c, const Plan& p, int64_t n_pairs, bool out_pinned, int32_t n_devices);
 int32_t devices_for(const ovl_ctx* c, int64_t n_pairs);

@@ -413,7 +413,9 @@ OVL_API int ovl_layout_candidates(ovl_ctx* ctx, int32_t match, int32_t mismatch,
     HIPCHK(c, c->ly.timer.arm(ctx->timing));
     HIPCHK(c, c->ly.timer.mark(0, s));
     if (n_pairs > 0) {
-        rc = launch_score(c, p, d.a, d.b, n_pairs, match, mismatch, indel, writable(d.score), writable(d.end), s);
+        LaunchIo io;
+        rc = launch_score(c, p, {d.a, d.b, n_pairs}, {match, mismatch, indel}, {writable(d.score), writable(d.end)}, io,
+                          s);
         if (rc != OVL_OK) return rc;
     }
     HIPCHK(c, c->ly.timer.mark(1, s));

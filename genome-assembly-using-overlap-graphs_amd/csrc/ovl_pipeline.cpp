@@ -26,14 +26,11 @@ hipError_t wait_event(const Dev* d, hipEvent_t ev) {
     }
 }
 
-// Pairs per pipeline chunk.  Measured on MI355X (tools/pipe_ab.py, profiles/r02_pipe_ab_*.json): every
-// chunk's D2H copy costs ~0.1 ms of fixed overhead, which is more than the kernel time a chunk hides, so
-// copies of pinned arrays run as one chunk; only pageable arrays, which go through pinned staging slots,
-// are cut into chunks (the slot size): 512 K pairs, the kernels reading and storing the staging slots
-// themselves (the host copy of chunk k+1 overlaps the kernel of chunk k).
-// Direct kernel stores into pinned arrays need no chunks at all.  Packed results (pack_ok) are expanded
-// on the host chunk by chunk while the next chunk is scored: 1 M pairs (tools/host_paths_ab.py at the
-// target point: 128 K 0.53 ms, 256 K 0.38, 512 K 0.30, 1 M 0.25, one chunk 0.29).
+// Pairs per pipeline chunk.  Direct kernel stores into pinned arrays need no chunks (a chunk's fixed cost, ~0.1 ms as
+// a D2H copy, is more than the kernel time it hides: tools/pipe_ab.py, profiles/r02_pipe_ab_*.json); pageable arrays go
+// through the pinned staging slots in chunks of the slot size, 512 K pairs (the host copy of chunk k + 1 overlaps the
+// kernel of chunk k).  Packed results (pack_ok) are expanded on the host chunk by chunk while the next chunk is scored,
+// 1 M pairs (tools/host_paths_ab.py, target point: 128 K 0.53 ms, 256 K 0.38, 512 K 0.30, 1 M 0.25, one chunk 0.29).
 int64_t pick_chunk(const Dev* d, int64_t n, bool staged, bool pack) {
     if (d->k.pipe_chunk > 0) return d->k.pipe_chunk;
     const int64_t cap = int64_t(1) << (pack ? 20 : 19);
@@ -42,6 +39,15 @@ int64_t pick_chunk(const Dev* d, int64_t n, bool staged, bool pack) {
 
 // Chunk k's results go through the staging slots (pageable caller arrays, or a packed chunk).
 bool chunk_staged(const Call& C, const Job& J, int64_t k) { return !C.out_pinned || (C.pack && k < J.n_packed); }
+
+// The live direct share of the device's packed calls into pinned arrays: one for compact host pair lists
+double& pack_share(const Call& C, Dev* d) { return C.compact ? d->pack_pct_h : d->pack_pct; }
+
+// Chunk k of a compact host pair list in the encoding buffer
+PairLayout chunk_layout(const Job& J, int64_t k) {
+    const int64_t off = J.cb[(size_t)k];
+    return PairLayout(off, k, J.cb[(size_t)k + 1] - off, J.d->n_reads <= 65535 ? 2 : 4);
+}
 
 int setup_job(const Call& C, Job& J) {
     Dev* d = J.d;
@@ -55,7 +61,7 @@ int setup_job(const Call& C, Job& J) {
     // packed calls: the packed share in equal chunks of <= J.chunk, then (pinned arrays) the direct share
     int64_t packed = 0;
     if (C.pack) {
-        double& share = C.compact ? d->pack_pct_h : d->pack_pct;
+        double& share = pack_share(C, d);
         if (share < 0.0) share = C.compact ? 2.0 * d->k.pack_direct_pct : d->k.pack_direct_pct;
         const int64_t pct = d->k.pack_adapt ? (int64_t)(share + 0.5) : d->k.pack_direct_pct;
         packed = C.out_pinned ? (n - n * pct / 100) & ~int64_t(63) : n;
@@ -74,22 +80,16 @@ int setup_job(const Call& C, Job& J) {
         J.cb.push_back(o);
     }
     J.nchunks = (int64_t)J.cb.size() - 1;
-    // sinks: packed chunks 2 bytes per pair; the rest int32
-    J.om.assign((size_t)J.nchunks, 1);
     J.drained = 0;
-    for (int64_t k = 0; k < J.n_packed; ++k) J.om[(size_t)k] = 2;
-    J.slot.resize((size_t)J.nchunks);
-    for (int64_t k = 0; k < J.nchunks; ++k) J.slot[(size_t)k] = (uint8_t)(k % kSlots);
     for (int64_t k = 0; k < J.nchunks; ++k) J.chunk = std::max(J.chunk, J.cb[(size_t)k + 1] - J.cb[(size_t)k]);
     const size_t bytes = sizeof(int32_t) * (size_t)n;
     if (C.compact) {
-        // decoded pair list in HBM, the pinned encoding buffer (chunk k at align16(8 * cb[k] + 32 * k)) and
-        // the chunks' decode events
+        // decoded pair list in HBM, the pinned encoding buffer (chunk k: chunk_layout) and the chunks' decode events
         HIPCHK(d, ensure(d->a, bytes));
         HIPCHK(d, ensure(d->b, bytes));
         J.ka = as<int32_t>(d->a);
         J.kb = as<int32_t>(d->b);
-        const size_t need = 8 * (size_t)n + 32 * (size_t)J.nchunks + 64;
+        const size_t need = PairLayout::job_bytes(n, J.nchunks);
         if (d->cp_bytes < need) {
             if (d->cp_host) (void)hipHostFree(d->cp_host);
             d->cp_host = d->cp_dev = nullptr;
@@ -176,11 +176,10 @@ int encode_chunk(const Call& C, Job& J, int64_t k, const std::function<int()>& p
     const int32_t* A = C.h_a + g;
     const int32_t* B = C.h_b + g;
     const int32_t nr = d->n_reads;
-    const int wd = nr <= 65535 ? 2 : 4;
-    const size_t base = (8 * (size_t)off + 32 * (size_t)k + 15) & ~size_t(15);
-    char* hb = d->cp_host + base;                  // b area
-    const size_t b_bytes = ((size_t)n * wd + 15) & ~size_t(15);
-    char* ha = hb + b_bytes;                       // a area: tile deltas + bases, runs, or a like b
+    const PairLayout lay = chunk_layout(J, k);
+    const int wd = (int)lay.width;
+    char* hb = d->cp_host + lay.base();            // b area
+    char* ha = d->cp_host + lay.a();               // a area: tile deltas + bases, runs, or a like b
     CopyPool& pool = CopyPool::get();
     const std::vector<size_t> parts = pool.cut((size_t)n, size_t(1) << 15);
     static const ovl_encode::Fns enc = ovl_encode::pick(nullptr);  // the widest this CPU runs
@@ -197,8 +196,8 @@ int encode_chunk(const Call& C, Job& J, int64_t k, const std::function<int()>& p
                        : C.plan->key64 ? 4 : !ix_launch(d, n) ? 5 : 0;
     if (g_trace && ix_why) g_trace->mark('x', ix_why);
     if (ix_why == 0) {
-        uint8_t* d8 = reinterpret_cast<uint8_t*>(ha);
-        int32_t* tb = reinterpret_cast<int32_t*>(ha + (((size_t)n + 15) & ~size_t(15)));
+        uint8_t* d8 = reinterpret_cast<uint8_t*>(d->cp_host + lay.d8());
+        int32_t* tb = reinterpret_cast<int32_t*>(d->cp_host + lay.tile_bases());
         std::vector<uint8_t> bad(parts.size(), 0);
         pool.parallel_parts(
             parts,
@@ -212,7 +211,7 @@ int encode_chunk(const Call& C, Job& J, int64_t k, const std::function<int()>& p
         if (std::find(bad.begin(), bad.end(), 1) == bad.end()) {
             J.ixk[(size_t)k] = 1;  // (issue_chunk copies the chunk into HBM and launches on it)
             if (g_trace) g_trace->mark('e', k);
-            d->cp_link += 3 * (int64_t)n + 4 * ((n + 63) / 64);
+            d->cp_link += lay.ix_link();
             return OVL_OK;
         }
     }
@@ -244,8 +243,8 @@ int encode_chunk(const Call& C, Job& J, int64_t k, const std::function<int()>& p
         R += (int64_t)pv[i].size();
     }
     runs = runs && 8 * R + 4 < n * wd;
-    int32_t* vals = reinterpret_cast<int32_t*>(ha);
-    int32_t* starts = vals + ((R + 3) & ~int64_t(3));  // 16-byte aligned
+    int32_t* vals = reinterpret_cast<int32_t*>(d->cp_host + lay.run_values());
+    int32_t* starts = reinterpret_cast<int32_t*>(d->cp_host + lay.run_starts(R));
     if (runs) {
         int64_t r = 0;
         for (size_t i = 0; i + 1 < parts.size(); ++i) {
@@ -266,18 +265,16 @@ int encode_chunk(const Call& C, Job& J, int64_t k, const std::function<int()>& p
     if (runs) starts[R] = (int32_t)n;
     if (g_trace) g_trace->mark('e', k);
     // decode on the second stream (host-mapped reads) into this chunk's slice of the HBM list
-    char* db = d->cp_dev + base;
-    char* da = db + b_bytes;
     HIPCHK(d, hipSetDevice(d->device));
-    HIPCHK(d, ovl_launch_widen(db, wd, n, J.kb + off, d->s_in));
+    HIPCHK(d, ovl_launch_widen(d->cp_dev + lay.base(), wd, n, J.kb + off, d->s_in));
     if (runs) {
-        HIPCHK(d, ovl_launch_runs(reinterpret_cast<int32_t*>(da), reinterpret_cast<int32_t*>(da) + ((R + 3) & ~int64_t(3)),
-                                  R, J.ka + off, d->s_in));
+        HIPCHK(d, ovl_launch_runs(reinterpret_cast<int32_t*>(d->cp_dev + lay.run_values()),
+                                  reinterpret_cast<int32_t*>(d->cp_dev + lay.run_starts(R)), R, J.ka + off, d->s_in));
     } else {
-        HIPCHK(d, ovl_launch_widen(da, wd, n, J.ka + off, d->s_in));
+        HIPCHK(d, ovl_launch_widen(d->cp_dev + lay.a(), wd, n, J.ka + off, d->s_in));
     }
     HIPCHK(d, hipEventRecord(d->dec_ev[(size_t)k], d->s_in));
-    d->cp_link += (int64_t)n * wd + (runs ? 8 * R + 4 : (int64_t)n * wd);
+    d->cp_link += lay.decoded_link(runs, R);
     return OVL_OK;
 }
 
@@ -292,27 +289,28 @@ int issue_chunk(const Call& C, Job& J, int64_t k) {
     const int64_t n = J.cb[(size_t)k + 1] - off;
     const bool staged_out = chunk_staged(C, J, k);
     const size_t nb = sizeof(int32_t) * (size_t)n;
-    const int slot = J.slot[(size_t)k];
+    const int slot = chunk_slot(J, k);
     const size_t so = (size_t)slot * 2 * (size_t)d->st_cap;
     const bool staged_in = C.h_a && !C.in_pinned && !C.compact;
     // the slot's previous user, chunk k - kSlots, must be done (its staged results were drained already)
     if (staged_in && k >= kSlots && !chunk_staged(C, J, k - kSlots)) HIPCHK(d, wait_event(d, d->ev_k[slot]));
     const int32_t* ka;
     const int32_t* kb;
+    LaunchIo io;
+    io.sink = chunk_sink(J, k);
+    io.flag = d->h_flag_dev;
     if (C.compact && J.ixk[(size_t)k]) {
         // read in place by uniform_kernel from its HBM copy (encode_chunk's layout of chunk k), copied by the
         // copy engine on the second stream
-        const size_t base = (8 * (size_t)off + 32 * (size_t)k + 15) & ~size_t(15);
-        const size_t b_bytes = ((size_t)n * 2 + 15) & ~size_t(15);
-        const size_t bytes = b_bytes + (((size_t)n + 15) & ~size_t(15)) + 4 * (size_t)((n + 63) / 64);
-        HIPCHK(d, hipMemcpyAsync(as<char>(d->cp_hbm) + base, d->cp_host + base, bytes, hipMemcpyHostToDevice,
+        const PairLayout lay = chunk_layout(J, k);
+        char* hbm = as<char>(d->cp_hbm);
+        HIPCHK(d, hipMemcpyAsync(hbm + lay.base(), d->cp_host + lay.base(), lay.ix_bytes(), hipMemcpyHostToDevice,
                                  d->s_in));
         HIPCHK(d, hipEventRecord(d->dec_ev[(size_t)k], d->s_in));
         HIPCHK(d, hipStreamWaitEvent(d->stream, d->dec_ev[(size_t)k], 0));
-        const char* hbm = as<char>(d->cp_hbm) + base;
-        d->ix_b16 = reinterpret_cast<const uint16_t*>(hbm);
-        d->ix_d8 = reinterpret_cast<const uint8_t*>(hbm + b_bytes);
-        d->ix_base = reinterpret_cast<const int32_t*>(hbm + b_bytes + (((size_t)n + 15) & ~size_t(15)));
+        io.ix_b16 = reinterpret_cast<const uint16_t*>(hbm + lay.base());
+        io.ix_d8 = reinterpret_cast<const uint8_t*>(hbm + lay.d8());
+        io.ix_base = reinterpret_cast<const int32_t*>(hbm + lay.tile_bases());
         ka = kb = nullptr;
     } else if (C.compact) {
         // decoded into HBM by encode_chunk's kernels on the second stream
@@ -335,21 +333,16 @@ int issue_chunk(const Call& C, Job& J, int64_t k) {
     }
     int32_t* os = staged_out ? d->st_out_dev + so : J.d_score + off;
     int32_t* oe = staged_out ? d->st_out_dev + so + d->st_cap : J.d_end + off;
-    d->out_mode = J.om[(size_t)k];
     hipStream_t ks = d->stream;
     if (C.timing) {
         HIPCHK(d, hipEventRecord(d->t_ev[2 * k], ks));
         if (C.plan->kernel == OVL_KERNEL_UNGAPPED) {  // (a chunk of one ungapped launch: time the kernel itself)
-            d->kev_start = d->k_ev[2 * k];
-            d->kev_stop = d->k_ev[2 * k + 1];
+            io.kev_start = d->k_ev[2 * k];
+            io.kev_stop = d->k_ev[2 * k + 1];
         }
     }
-    int rc = launch_score(d, *C.plan, ka, kb, n, C.match, C.mismatch, C.indel, os, oe, ks);
-    if (C.timing) J.kexact[(size_t)k] = d->kev_start == nullptr && C.plan->kernel == OVL_KERNEL_UNGAPPED;
-    d->kev_start = d->kev_stop = nullptr;
-    d->ix_b16 = nullptr;
-    d->ix_d8 = nullptr;
-    d->ix_base = nullptr;
+    int rc = launch_score(d, *C.plan, {ka, kb, n}, C.sc, {os, oe}, io, ks);
+    if (C.timing) J.kexact[(size_t)k] = io.timed;
     if (rc != OVL_OK) return rc;
     if (C.timing) HIPCHK(d, hipEventRecord(d->t_ev[2 * k + 1], ks));
     if (staged_in || staged_out) HIPCHK(d, hipEventRecord(d->ev_k[slot], ks));
@@ -365,7 +358,7 @@ int drain_chunk(const Call& C, Job& J, int64_t k) {
     const int64_t off = J.cb[(size_t)k];
     const int64_t g = J.lo + off;
     const int64_t n = J.cb[(size_t)k + 1] - off;
-    const int slot = J.slot[(size_t)k];
+    const int slot = chunk_slot(J, k);
     HIPCHK(d, wait_event(d, d->ev_k[slot]));
     if (g_trace) g_trace->mark('w', k);
     struct Drained {
@@ -377,7 +370,7 @@ int drain_chunk(const Call& C, Job& J, int64_t k) {
     const int32_t* ss = d->st_out + (size_t)slot * 2 * (size_t)d->st_cap;
     if (C.pack) {
         host_expand(C.out_s + (g - C.out_base), C.out_e + (g - C.out_base), reinterpret_cast<const uint16_t*>(ss),
-                    ss + d->st_cap, C.match, C.mismatch, true, (size_t)n, kExpandPart);
+                    ss + d->st_cap, C.sc.match, C.sc.mismatch, true, (size_t)n, kExpandPart);
         return OVL_OK;
     }
     host_copy(C.out_s + (g - C.out_base), ss, sizeof(int32_t) * (size_t)n);
@@ -391,25 +384,6 @@ void quiesce(std::vector<Job>& jobs) {
         for (hipStream_t s : {J.d->stream, J.d->s_in}) (void)hipStreamSynchronize(s);
     }
 }
-
-// Host-array calls: the kernels flag a bad pair index by storing into the device's pinned host flag, which
-// the host reads after the call's synchronisation (no flag copy behind the results).
-struct HostFlag {
-    std::vector<Job>& jobs;
-    HostFlag(std::vector<Job>& j, int32_t out_mode) : jobs(j) {
-        for (Job& J : jobs) {
-            *(volatile uint32_t*)J.d->h_flag = 0;
-            J.d->cur_flag = J.d->h_flag_dev;
-            J.d->out_mode = out_mode;
-        }
-    }
-    ~HostFlag() {
-        for (Job& J : jobs) {
-            J.d->cur_flag = as<uint32_t>(J.d->err_flag);
-            J.d->out_mode = 0;
-        }
-    }
-};
 
 // One device's share of a host-array call: its chunks issued and drained in order.  A compact pair list (one device)
 // has chunk k issued by this thread while the pool encodes chunk k + 1; staged chunks are drained kSlots - 1
@@ -481,7 +455,9 @@ int run_pipeline(ovl_ctx* c, const Call& C, std::vector<Job>& jobs) {
         ~Unset() { g_trace = nullptr; }
     } unset;
     int rc = OVL_OK;
-    HostFlag host_flag(jobs, 1);  // (each chunk sets its own sink: issue_chunk)
+    // the kernels flag a bad pair index by storing into the device's pinned host flag (issue_chunk passes it), which
+    // the host reads after the call's synchronisation (no flag copy behind the results)
+    for (Job& J : jobs) *(volatile uint32_t*)J.d->h_flag = 0;
     if (jobs.size() == 1) {
         rc = run_job(C, jobs[0], false);
     } else {
@@ -525,13 +501,12 @@ int run_pipeline(ovl_ctx* c, const Call& C, std::vector<Job>& jobs) {
         if (!C.pack || !C.out_pinned || J.n_packed >= J.nchunks || !d->k.pack_adapt) continue;
         const auto tw = std::chrono::steady_clock::now();
         const hipError_t q = hipEventQuery(d->ev_last);
+        double& share = pack_share(C, d);
         if (q == hipSuccess) {
-            double& share = C.compact ? d->pack_pct_h : d->pack_pct;
             share = std::min(C.compact ? 80.0 : 50.0, share + 1.0);
         } else if (q == hipErrorNotReady) {
             HIPCHK(c, wait_event(d, d->ev_last));
             const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tw).count();
-            double& share = C.compact ? d->pack_pct_h : d->pack_pct;
             if (us > kShareWaitUs) share = std::max(2.0, share - 1.0);
         }
     }
@@ -558,8 +533,8 @@ int run_pipeline(ovl_ctx* c, const Call& C, std::vector<Job>& jobs) {
                 const hipEvent_t* ev = exact ? &d->k_ev[2 * (size_t)k] : &d->t_ev[2 * (size_t)k];
                 if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) s += ms;
                 // the chunk's result sink (issue_chunk): packed staging, or int32 into host memory
-                const int32_t sink = J.om[(size_t)k];
-                c->t_launches.push_back({d->device, sink, J.cb[(size_t)k + 1] - J.cb[(size_t)k], (double)ms});
+                const int64_t n = J.cb[(size_t)k + 1] - J.cb[(size_t)k];
+                c->t_launches.push_back({d->device, chunk_sink(J, k), n, (double)ms});
             }
             kms = std::max(kms, s);
         }
@@ -647,6 +622,44 @@ int32_t devices_used(const ovl_ctx* c, int64_t n_pairs) {
     return c->shared_slots ? (int32_t)c->devs.size() : devices_for(c, n_pairs);
 }
 
+// The Call of a host-array scoring call over n_pairs pairs -- a host pair list (h_a, h_b), or null: the resident list
+// from out_base -- and in *n_devices the devices it uses.
+Call make_call(ovl_ctx* c, const Plan& p, const Scoring& sc, const int32_t* h_a, const int32_t* h_b, int64_t n_pairs,
+               int32_t* out_s, int32_t* out_e, int64_t out_base, int32_t* n_devices) {
+    const size_t bytes = sizeof(int32_t) * (size_t)n_pairs;
+    const int32_t S = *n_devices = devices_used(c, n_pairs);
+    Call C;
+    C.plan = &p;
+    C.sc = sc;
+    C.h_a = h_a;
+    C.h_b = h_b;
+    C.in_pinned = h_a && host_pinned(h_a, bytes) && host_pinned(h_b, bytes);
+    C.out_s = out_s;
+    C.out_e = out_e;
+    C.out_base = out_base;
+    C.out_pinned = host_pinned(out_s, bytes) && host_pinned(out_e, bytes);
+    C.timing = c->timing != 0;
+    C.pack = pack_ok(c, p, n_pairs, C.out_pinned, S);
+    C.compact = h_a && S == 1 && c->devs[0]->k.compact && n_pairs >= kCompactMin;
+    return C;
+}
+
+// One job per device from the shard bounds; `resident_list`: each over its device's resident candidate list
+std::vector<Job> jobs_from_cuts(ovl_ctx* c, const std::vector<int64_t>& cuts, bool resident_list) {
+    std::vector<Job> jobs(cuts.size() - 1);
+    for (size_t r = 0; r < jobs.size(); ++r) {
+        Job& J = jobs[r];
+        J.d = c->devs[r];
+        J.lo = cuts[r];
+        J.hi = cuts[r + 1];
+        if (resident_list) {
+            J.dev_a = as<int32_t>(J.d->cand_a);
+            J.dev_b = as<int32_t>(J.d->cand_b);
+        }
+    }
+    return jobs;
+}
+
 OVL_API int ovl_score_host(ovl_ctx* c, const int32_t* a_idx, const int32_t* b_idx, int64_t n_pairs, int32_t match,
                            int32_t mismatch, int64_t indel, int32_t band, int32_t* out_score, int32_t* out_end) {
     if (!c) return fail((ovl_ctx*)nullptr, OVL_E_ARG, "ctx is NULL");
@@ -660,29 +673,9 @@ OVL_API int ovl_score_host(ovl_ctx* c, const int32_t* a_idx, const int32_t* b_id
     if (n_pairs == 0) return OVL_OK;
     if (c->devs[0]->n_reads == 0) return fail(c, OVL_E_INDEX, "pairs given but the read set is empty");
     DeviceGuard guard;
-    const size_t bytes = sizeof(int32_t) * (size_t)n_pairs;
-    Call C;
-    C.plan = &p;
-    C.match = match;
-    C.mismatch = mismatch;
-    C.indel = indel;
-    C.h_a = a_idx;
-    C.h_b = b_idx;
-    C.in_pinned = host_pinned(a_idx, bytes) && host_pinned(b_idx, bytes);
-    C.out_s = out_score;
-    C.out_e = out_end;
-    C.out_pinned = host_pinned(out_score, bytes) && host_pinned(out_end, bytes);
-    C.timing = c->timing != 0;
-    const int32_t S = devices_used(c, n_pairs);
-    C.pack = pack_ok(c, p, n_pairs, C.out_pinned, S);
-    C.compact = S == 1 && c->devs[0]->k.compact && n_pairs >= kCompactMin;
-    const std::vector<int64_t> cuts = host_cuts(c, a_idx, b_idx, n_pairs, S);
-    std::vector<Job> jobs((size_t)S);
-    for (int32_t r = 0; r < S; ++r) {
-        jobs[(size_t)r].d = c->devs[(size_t)r];
-        jobs[(size_t)r].lo = cuts[(size_t)r];
-        jobs[(size_t)r].hi = cuts[(size_t)r + 1];
-    }
+    int32_t S = 1;
+    const Call C = make_call(c, p, {match, mismatch, indel}, a_idx, b_idx, n_pairs, out_score, out_end, 0, &S);
+    std::vector<Job> jobs = jobs_from_cuts(c, host_cuts(c, a_idx, b_idx, n_pairs, S), false);
     return run_pipeline(c, C, jobs);
 }
 

@@ -57,10 +57,6 @@ int make_plan_full(const Dev* c, int32_t match, int32_t mismatch, int64_t indel,
     return OVL_OK;
 }
 
-int launch_score_chunk(Dev* c, const Plan& pl, const int32_t* d_a, const int32_t* d_b, int64_t n_pairs,
-                       int32_t match, int32_t mismatch, int64_t indel, int32_t* d_score, int32_t* d_end,
-                       hipStream_t s);
-
 // Per-device scratch (lane_col, seed_*) is shared by every launch of the device.  A launch on stream s
 // first waits for the previous user on another stream; growing a buffer first waits for that user.
 struct ScratchNeed {
@@ -140,12 +136,28 @@ int ensure_heavy(Dev* c) {
     return OVL_OK;
 }
 
+// The heavy tiles among the list tiles of pairs [lo, lo + n_pairs) of the resident list, lo a multiple of 64 (after
+// ensure_heavy); tile_base is the range's first list tile.  All zero when the range has none.
+HeavyWindow heavy_window(const Dev* c, int64_t lo, int64_t n_pairs) {
+    const int64_t t0 = lo / 64, t1 = t0 + (n_pairs + 63) / 64;
+    const auto k0 = std::lower_bound(c->h_heavy.begin(), c->h_heavy.end(), t0);
+    const auto k1 = std::lower_bound(c->h_heavy.begin(), c->h_heavy.end(), t1);
+    HeavyWindow w;
+    if (k1 > k0) w = {reinterpret_cast<const int32_t*>(c->heavy_ids.p) + (k0 - c->h_heavy.begin()), k1 - k0, t0};
+    return w;
+}
+
 namespace {
 
-int launch_score_chunk(Dev* c, const Plan& pl, const int32_t* d_a, const int32_t* d_b, int64_t n_pairs,
-                       int32_t match, int32_t mismatch, int64_t indel, int32_t* d_score, int32_t* d_end,
-                       hipStream_t s) {
+int launch_score_chunk(Dev* c, const Plan& pl, const PairList& pairs, const Scoring& sc, const ScoreOut& out,
+                       LaunchIo& io, hipStream_t s) {
+    const int32_t *const d_a = pairs.a, *const d_b = pairs.b;
+    const int32_t match = sc.match, mismatch = sc.mismatch;
+    const int64_t n_pairs = pairs.n, indel = sc.indel;
     if (n_pairs == 0) return OVL_OK;
+    if (io.ix_b16 && (pl.kernel != OVL_KERNEL_UNGAPPED || pl.key64 || !ix_launch(c, n_pairs)))
+        return fail(c, OVL_E_UNSUPPORTED, "host-encoded pair list on a launch that cannot read it");
+    uint32_t* const flag = io.flag ? io.flag : as<uint32_t>(c->err_flag);
     // ovl_last_score_form: the call's first launch describes itself (a banded launch, not its seed's)
     ScoreForm& f = c->form;
     const bool rec = f.open;
@@ -160,20 +172,14 @@ int launch_score_chunk(Dev* c, const Plan& pl, const int32_t* d_a, const int32_t
         // seed j* into device scratch (the outputs may be host memory), then the banded DP reads it
         const size_t sb = sizeof(int32_t) * (size_t)n_pairs;
         HIPCHK(c, scratch_acquire(c, s, {{&c->seed_s, sb}, {&c->seed_e, sb}}));
-        Plan seed;
-        seed.kernel = pl.seed_kernel;
-        seed.key64 = pl.seed_key64;
-        seed.wide = pl.seed_wide;
-        const int32_t out_mode = c->out_mode;
-        c->out_mode = 0;  // the seeds stay in HBM
-        int rc = launch_score_chunk(c, seed, d_a, d_b, n_pairs, match, mismatch, INT32_MIN, as<int32_t>(c->seed_s),
-                                    as<int32_t>(c->seed_e), s);
-        c->out_mode = out_mode;
+        const Plan seed{pl.seed_kernel, pl.seed_key64, pl.seed_wide};
+        LaunchIo seed_io;  // the seeds stay in HBM, untimed; the call's flag
+        seed_io.flag = flag;
+        int rc = launch_score_chunk(c, seed, pairs, {match, mismatch, INT32_MIN},
+                                    {as<int32_t>(c->seed_s), as<int32_t>(c->seed_e)}, seed_io, s);
         if (rc != OVL_OK) return rc;
         seed_end = as<int32_t>(c->seed_e);
     }
-    if (c->ix_b16 && (pl.kernel != OVL_KERNEL_UNGAPPED || pl.key64 || !ix_launch(c, n_pairs)))
-        return fail(c, OVL_E_UNSUPPORTED, "host-encoded pair list on a launch that cannot read it");
     if (pl.kernel == OVL_KERNEL_UNGAPPED) {
         OvlUngappedArgs g{};
         g.sfx = as<uint32_t>(c->sfx);
@@ -183,51 +189,44 @@ int launch_score_chunk(Dev* c, const Plan& pl, const int32_t* d_a, const int32_t
         g.a_idx = d_a;
         g.b_idx = d_b;
         g.n_pairs = n_pairs;
-        // split a pair's 32 bit shifts over 1, 2 or 4 lanes until the grid has
-        // enough wavefronts to fill every SIMD a few times
         // general kernel: split a pair's bit shifts over 1, 2 or 4 lanes until the grid
         // has enough wavefronts.  Uniform kernel: latency mode (two wavefronts per tile,
         // side pairs beside the sweep) when there is about one tile per wavefront slot.
-        g.rs_log2 = ungapped_rs_log2(c, n_pairs, c->ix_b16 != nullptr);
+        g.rs_log2 = ungapped_rs_log2(c, n_pairs, io.ix_b16 != nullptr);
         // uniform-length fast path (2 bit planes): pairs of two reads of length lmax;
         // uniform_kernel scores the other pairs through its LDS side ring
         g.lw = c->planes == 2 ? c->lmax : 0;
         if (rec) f.rs_log2 = g.rs_log2;
         g.full = as<uint32_t>(c->full);
-        // (timing: this launch records the chunk's kernel events itself, once; issue_chunk checks they were taken)
-        g.ev_start = c->kev_start;
-        g.ev_stop = c->kev_stop;
+        g.ev_start = io.kev_start;
+        g.ev_stop = io.kev_stop;
         g.match = match;
         g.mismatch = mismatch;
-        g.out_score = d_score;
-        g.out_end = d_end;
-        g.err_flag = c->cur_flag;
+        g.out_score = out.score;
+        g.out_end = out.end;
+        g.err_flag = flag;
         g.planes = c->planes;
         g.wmax = c->wmax;
         g.key64 = pl.key64 ? 1 : 0;
         g.max_blocks = (int64_t)c->cu_count * kBlocksPerCu;
-        g.host_out = c->out_mode;
-        g.ix_b16 = c->ix_b16;
-        g.ix_d8 = c->ix_d8;
-        g.ix_base = c->ix_base;
+        g.host_out = io.sink;
+        g.ix_b16 = io.ix_b16;
+        g.ix_d8 = io.ix_d8;
+        g.ix_base = io.ix_base;
         // a throughput-mode launch over (a 64-aligned part of) the resident candidate list: heavy tiles first
         const int32_t* ca = as<int32_t>(c->cand_a);
         if (!g.ix_b16 && g.lw > 0 && g.rs_log2 == 0 && c->cand_n > 0 && d_a >= ca &&
             d_a < ca + c->cand_n && d_b == as<int32_t>(c->cand_b) + (d_a - ca) && (d_a - ca) % 64 == 0) {
             int rc = ensure_heavy(c);
             if (rc != OVL_OK) return rc;
-            const int64_t t0 = (d_a - ca) / 64, t1 = t0 + (n_pairs + 63) / 64;
-            const auto k0 = std::lower_bound(c->h_heavy.begin(), c->h_heavy.end(), t0);
-            const auto k1 = std::lower_bound(c->h_heavy.begin(), c->h_heavy.end(), t1);
-            if (k1 > k0) {
-                g.heavy_ids = as<int32_t>(c->heavy_ids) + (k0 - c->h_heavy.begin());
-                g.heavy_n = (int32_t)(k1 - k0);
-                g.tile_flags = as<uint8_t>(c->tile_flags);
-                g.tile_base = t0;
-            }
+            const HeavyWindow w = heavy_window(c, d_a - ca, n_pairs);
+            g.heavy_ids = w.ids;
+            g.heavy_n = (int32_t)w.count;
+            g.tile_flags = w.count ? as<uint8_t>(c->tile_flags) : nullptr;
+            g.tile_base = w.tile_base;
         }
         HIPCHK(c, ovl_launch_ungapped(&g, s));
-        if (g.ev_start && g.lw > 0) c->kev_start = c->kev_stop = nullptr;  // (uniform_kernel recorded them)
+        io.timed = g.ev_start && g.lw > 0;  // (uniform_kernel recorded the events)
     } else {
         OvlDpArgs g{};
         g.codes = as<uint8_t>(c->codes);
@@ -241,10 +240,10 @@ int launch_score_chunk(Dev* c, const Plan& pl, const int32_t* d_a, const int32_t
         g.match = match;
         g.mismatch = mismatch;
         g.indel = indel;
-        g.out_score = d_score;
-        g.out_end = d_end;
+        g.out_score = out.score;
+        g.out_end = out.end;
         g.tb = nullptr;
-        g.err_flag = c->cur_flag;
+        g.err_flag = flag;
         g.wide = pl.wide ? 1 : 0;
         g.band = pl.kernel == OVL_KERNEL_BANDED ? pl.band : -1;
         g.seed = seed_end;
@@ -286,8 +285,8 @@ int launch_score_chunk(Dev* c, const Plan& pl, const int32_t* d_a, const int32_t
                 OvlDpArgs gs = g;
                 gs.a_idx = d_a + lo;
                 gs.b_idx = d_b + lo;
-                gs.out_score = d_score + lo;
-                gs.out_end = d_end + lo;
+                gs.out_score = out.score + lo;
+                gs.out_end = out.end + lo;
                 gs.n_pairs = std::min(slice, n_pairs - lo);
                 HIPCHK(c, ovl_launch_dp_lane(&gs, &k, s));
             }
@@ -354,15 +353,27 @@ int launch_score_chunk(Dev* c, const Plan& pl, const int32_t* d_a, const int32_t
 
 }  // namespace
 
-// Kernels queue pair indices as int32 (LDS side ring); split huge lists.
-int launch_score(Dev* c, const Plan& pl, const int32_t* d_a, const int32_t* d_b, int64_t n_pairs,
-                 int32_t match, int32_t mismatch, int64_t indel, int32_t* d_score, int32_t* d_end,
+// Kernels queue pair indices as int32 (LDS side ring); split huge lists.  An in-place list advances with its piece
+// (a piece is whole tiles); the kernel events go to the first piece that records them, as a launch records them once.
+int launch_score(Dev* c, const Plan& pl, const PairList& pairs, const Scoring& sc, const ScoreOut& out, LaunchIo& io,
                  hipStream_t s) {
     constexpr int64_t kChunk = int64_t(1) << 30;
-    for (int64_t lo = 0; lo < n_pairs; lo += kChunk) {
-        const int64_t n = std::min(kChunk, n_pairs - lo);
-        int rc = launch_score_chunk(c, pl, d_a + lo, d_b + lo, n, match, mismatch, indel, d_score + lo, d_end + lo, s);
+    io.timed = false;
+    LaunchIo piece = io;
+    for (int64_t lo = 0; lo < pairs.n; lo += kChunk) {
+        const int64_t n = std::min(kChunk, pairs.n - lo);
+        if (io.ix_b16) {
+            piece.ix_b16 = io.ix_b16 + lo;
+            piece.ix_d8 = io.ix_d8 + lo;
+            piece.ix_base = io.ix_base + lo / 64;
+        }
+        const PairList part{pairs.a + lo, pairs.b + lo, n};
+        int rc = launch_score_chunk(c, pl, part, sc, {out.score + lo, out.end + lo}, piece, s);
         if (rc != OVL_OK) return rc;
+        if (piece.timed) {
+            io.timed = true;
+            piece.kev_start = piece.kev_stop = nullptr;
+        }
     }
     return OVL_OK;
 }
@@ -423,7 +434,8 @@ OVL_API int ovl_score_device(ovl_ctx* c, const int32_t* d_a, const int32_t* d_b,
     DeviceGuard guard;
     HIPCHK(c, hipSetDevice(d->device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);  // NULL = the default (null) stream
-    return launch_score(d, p, d_a, d_b, n_pairs, match, mismatch, indel, d_score, d_end, s);
+    LaunchIo io;  // (a device call's: HBM results, the device flag)
+    return launch_score(d, p, {d_a, d_b, n_pairs}, {match, mismatch, indel}, {d_score, d_end}, io, s);
 }
 
 OVL_API int ovl_check_device_errors(ovl_ctx* c) {

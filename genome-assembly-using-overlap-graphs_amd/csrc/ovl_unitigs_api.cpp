@@ -532,14 +532,15 @@ OVL_API int ovl_unitigs_candidates(ovl_ctx* ctx, const uint8_t* seqs, const int3
     if ((rc = upload_raw(c, g, ids, f, self_ix, s)) != OVL_OK) return rc;
     if (M > 0) HIPCHK(c, hipMemcpyAsync(d_sx, f.self.data(), 4 * M, hipMemcpyHostToDevice, s));
     HIPCHK(c, c->ug.timer.mark(0, s));
+    LaunchIo io;
     if (P > 0) {
-        rc = launch_score(c, p, as<int32_t>(c->cand_a), as<int32_t>(c->cand_b), (int64_t)P, match, mismatch, indel,
-                          writable(g.score), writable(g.end), s);
+        rc = launch_score(c, p, {as<int32_t>(c->cand_a), as<int32_t>(c->cand_b), (int64_t)P}, {match, mismatch, indel},
+                          {writable(g.score), writable(g.end)}, io, s);
         if (rc != OVL_OK) return rc;
     }
     if (M > 0) {  // the self pairs of the reads with a second copy, by the same scorer
-        rc = launch_score(c, p, d_sx, d_sx, (int64_t)M, match, mismatch, indel, writable(g.self_score),
-                          writable(g.self_end), s);
+        rc = launch_score(c, p, {d_sx, d_sx, (int64_t)M}, {match, mismatch, indel},
+                          {writable(g.self_score), writable(g.self_end)}, io, s);
         if (rc != OVL_OK) return rc;
     }
     HIPCHK(c, c->ug.timer.mark(1, s));

@@ -23,8 +23,7 @@ extern "C" hipError_t ovl_launch_layout_place(const OvlLayoutArgs*, void*, size_
 extern "C" hipError_t ovl_launch_layout_spell(const OvlLayoutArgs*, int32_t, hipStream_t) {
     return hipErrorNotSupported;
 }
-int launch_score(Dev*, const Plan&, const int32_t*, const int32_t*, int64_t, int32_t, int32_t, int64_t, int32_t*,
-                 int32_t*, hipStream_t) {
+int launch_score(Dev*, const Plan&, const PairList&, const Scoring&, const ScoreOut&, LaunchIo&, hipStream_t) {
     return OVL_E_UNSUPPORTED;
 }
 int check_scoring_args(ovl_ctx*, int32_t, int32_t, int64_t, int32_t, Plan*) { return OVL_E_UNSUPPORTED; }

@@ -36,8 +36,7 @@ STUB(ovl_launch_unitigs_fill, const OvlUnitigArgs*, hipStream_t)
 STUB(ovl_launch_unitigs_facts, const OvlUnitigArgs*, hipStream_t)
 STUB(ovl_launch_unitigs_kept, const OvlUnitigArgs*, void*, size_t, hipStream_t)
 int reach_launches(Dev*, OvlReachArgs*, bool, hipStream_t) { return OVL_E_HIP; }
-int launch_score(Dev*, const Plan&, const int32_t*, const int32_t*, int64_t, int32_t, int32_t, int64_t, int32_t*,
-                 int32_t*, hipStream_t) {
+int launch_score(Dev*, const Plan&, const PairList&, const Scoring&, const ScoreOut&, LaunchIo&, hipStream_t) {
     return OVL_E_HIP;
 }
 int check_scoring_args(ovl_ctx*, int32_t, int32_t, int64_t, int32_t, Plan*) { return OVL_E_HIP; }
