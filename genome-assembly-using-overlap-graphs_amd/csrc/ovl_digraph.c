@@ -48,45 +48,166 @@ static int take(PyObject* obj, Py_buffer* view, Py_ssize_t itemsize, const char*
     return 0;
 }
 
-/* Attribute dicts: a copy of the two-key template with its values set.  On CPython 3.10 a split-table
-   template (PEP 412 key-sharing: an instance __dict__) is copied with its values array, and the two values
-   are written into that array directly (indices iw / ie of the template's key table, found once by
-   attr_slots) instead of two PyDict_SetItem lookups; any other dict takes the SetItem path. */
-static void attr_slots(PyObject* tmpl, PyObject* kw, PyObject* ke, Py_ssize_t* iw, Py_ssize_t* ie) {
-    *iw = *ie = -1;
-#if PY_VERSION_HEX >= 0x030A0000 && PY_VERSION_HEX < 0x030B0000
-    if (((PyDictObject*)tmpl)->ma_values == NULL || PyDict_GET_SIZE(tmpl) != 2) return;
-    Py_ssize_t pos = 0;
-    PyObject *k, *v;
-    while (PyDict_Next(tmpl, &pos, &k, &v)) {  /* (split table: pos - 1 is the slot in ma_values) */
-        if (k == kw) *iw = pos - 1;
-        else if (k == ke) *ie = pos - 1;
+/* Sized allocation: `count` elements, never a zero-byte request (an empty graph still gets valid pointers).
+   NEW / NEW0 hold Python-side state (GIL held); RAW_NEW is for the buffers the helper threads read. */
+static size_t nz(int64_t count) { return count > 0 ? (size_t)count : 1; }
+
+static void* alloc_n(int64_t count, size_t size, int zeroed) {
+    return zeroed ? PyMem_Calloc(nz(count), size) : PyMem_Malloc(nz(count) * size);
+}
+#define NEW(T, count) ((T*)alloc_n((int64_t)(count), sizeof(T), 0))
+#define NEW0(T, count) ((T*)alloc_n((int64_t)(count), sizeof(T), 1))
+#define RAW_NEW(T, count) ((T*)PyMem_RawMalloc(sizeof(T) * nz((int64_t)(count))))
+
+static PyObject* key_weight(void) { return PyUnicode_InternFromString("weight"); }
+
+/* Python ints for edge attributes: one object per distinct value in [kIntLo, kIntHi) (scores <= 10 * l and end
+ * positions <= l for the reads of the benchmark configs), shared by every edge that carries it, instead of two
+ * allocations per pair; values outside the range are created per pair. */
+enum { kIntLo = -4096, kIntHi = 8192 };
+
+static PyObject* int_of(PyObject** cache, long v) {
+    if (v >= kIntLo && v < kIntHi) {
+        PyObject** slot = &cache[v - kIntLo];
+        if (!*slot) *slot = PyLong_FromLong(v);
+        Py_XINCREF(*slot);
+        return *slot;
     }
-    if (*iw < 0 || *ie < 0) *iw = *ie = -1;
-#else
-    (void)tmpl; (void)kw; (void)ke;
-#endif
+    return PyLong_FromLong(v);
 }
 
-static PyObject* new_attr(PyObject* tmpl, PyObject* kw, PyObject* ke, Py_ssize_t iw, Py_ssize_t ie, PyObject* wv,
-                          PyObject* ev) {
-    PyObject* d = PyDict_Copy(tmpl);
+/* The maker of the edges' attribute dicts {"weight": w, "end_position": e}, one per builder call.  A dict is a
+   copy of the two-key template with its values set, cheaper than growing an empty dict by two inserts.  With
+   `shared` (an instance __dict__ holding exactly the two keys, PEP 412 key-sharing) every copy shares the
+   template's key table and owns only its values: 104 instead of 232 bytes per edge, and still an ordinary dict (a
+   key added later converts that one dict).  On CPython 3.10 such a split-table template is copied with its values
+   array, and the two values are written into that array directly (iw / ie: their slots in the template's key
+   table) instead of two PyDict_SetItem lookups; any other dict takes the SetItem path. */
+typedef struct {
+    PyObject *kw, *ke;  /* the interned keys */
+    PyObject* tmpl;
+    Py_ssize_t iw, ie;  /* -1: no direct slots */
+    PyObject** ints;    /* int_of's cache */
+} Attrs;
+
+static void attrs_free(Attrs* A) {
+    if (A->ints)
+        for (int i = 0; i < kIntHi - kIntLo; ++i) Py_XDECREF(A->ints[i]);
+    PyMem_Free(A->ints);
+    Py_XDECREF(A->tmpl);
+    Py_XDECREF(A->kw);
+    Py_XDECREF(A->ke);
+    memset(A, 0, sizeof(*A));
+}
+
+/* `shared` is the template when it is a dict of exactly the two keys, else (NULL and None included) a fresh
+   template is made.  0, or -1 with an exception set (attrs_free is safe either way). */
+static int attrs_init(Attrs* A, PyObject* shared) {
+    memset(A, 0, sizeof(*A));
+    A->iw = A->ie = -1;
+    A->kw = key_weight();
+    A->ke = PyUnicode_InternFromString("end_position");
+    A->ints = NEW0(PyObject*, kIntHi - kIntLo);
+    if (!A->kw || !A->ke || !A->ints) {
+        if (!PyErr_Occurred()) PyErr_NoMemory();
+        return -1;
+    }
+    if (shared && PyDict_Check(shared) && PyDict_GET_SIZE(shared) == 2 && PyDict_Contains(shared, A->kw) == 1 &&
+        PyDict_Contains(shared, A->ke) == 1) {
+        A->tmpl = shared;
+        Py_INCREF(A->tmpl);
+    } else {
+        A->tmpl = PyDict_New();
+        if (!A->tmpl || PyDict_SetItem(A->tmpl, A->kw, Py_None) || PyDict_SetItem(A->tmpl, A->ke, Py_None)) return -1;
+    }
+#if PY_VERSION_HEX >= 0x030A0000 && PY_VERSION_HEX < 0x030B0000
+    if (((PyDictObject*)A->tmpl)->ma_values != NULL) {
+        Py_ssize_t pos = 0;
+        PyObject *k, *v;
+        while (PyDict_Next(A->tmpl, &pos, &k, &v)) {  /* (split table: pos - 1 is the slot in ma_values) */
+            if (k == A->kw) A->iw = pos - 1;
+            else if (k == A->ke) A->ie = pos - 1;
+        }
+        if (A->iw < 0 || A->ie < 0) A->iw = A->ie = -1;
+    }
+#endif
+    return 0;
+}
+
+/* a new attribute dict holding the two ints (the caller keeps its references to them) */
+static PyObject* attrs_dict(const Attrs* A, PyObject* wv, PyObject* ev) {
+    PyObject* d = PyDict_Copy(A->tmpl);
     if (!d) return NULL;
 #if PY_VERSION_HEX >= 0x030A0000 && PY_VERSION_HEX < 0x030B0000
     PyObject** vals = ((PyDictObject*)d)->ma_values;
-    if (iw >= 0 && vals) {
+    if (A->iw >= 0 && vals) {
         Py_INCREF(wv);
-        Py_XSETREF(vals[iw], wv);
+        Py_XSETREF(vals[A->iw], wv);
         Py_INCREF(ev);
-        Py_XSETREF(vals[ie], ev);
+        Py_XSETREF(vals[A->ie], ev);
         return d;
     }
 #endif
-    if (PyDict_SetItem(d, kw, wv) || PyDict_SetItem(d, ke, ev)) {
+    if (PyDict_SetItem(d, A->kw, wv) || PyDict_SetItem(d, A->ke, ev)) {
         Py_DECREF(d);
         return NULL;
     }
     return d;
+}
+
+/* a new attribute dict for one edge's score and end position */
+static PyObject* attrs_edge(const Attrs* A, long score, long end) {
+    PyObject* wv = int_of(A->ints, score);
+    PyObject* ev = int_of(A->ints, end);
+    PyObject* d = wv && ev ? attrs_dict(A, wv, ev) : NULL;
+    Py_XDECREF(wv);
+    Py_XDECREF(ev);
+    return d;
+}
+
+/* The result's node-ordered top-level dicts, with every node's successor and predecessor dict created at its
+   final size (no rehash while it fills); sin / pin borrow those per-node dicts from succ / pred. */
+typedef struct {
+    PyObject *node, *succ, *pred;
+    PyObject **sin, **pin;
+} Tops;
+
+static void tops_free(Tops* T) {
+    PyMem_Free(T->sin);
+    PyMem_Free(T->pin);
+    Py_XDECREF(T->node);
+    Py_XDECREF(T->succ);
+    Py_XDECREF(T->pred);
+    memset(T, 0, sizeof(*T));
+}
+
+static int tops_make(Tops* T, PyObject* names, const int64_t* outdeg, const int64_t* indeg) {
+    const Py_ssize_t n_nodes = PyList_GET_SIZE(names);
+    memset(T, 0, sizeof(*T));
+    T->node = PyDict_New();
+    T->succ = PyDict_New();
+    T->pred = PyDict_New();
+    T->sin = NEW(PyObject*, n_nodes);
+    T->pin = NEW(PyObject*, n_nodes);
+    if (!T->node || !T->succ || !T->pred || !T->sin || !T->pin) {
+        if (!PyErr_Occurred()) PyErr_NoMemory();
+        return -1;
+    }
+    for (Py_ssize_t i = 0; i < n_nodes; ++i) {
+        PyObject* name = PyList_GET_ITEM(names, i);
+        PyObject* x = PyDict_New();
+        PyObject* sd = _PyDict_NewPresized(outdeg[i]);
+        PyObject* pd = _PyDict_NewPresized(indeg[i]);
+        const int bad = !x || !sd || !pd || PyDict_SetItem(T->node, name, x) || PyDict_SetItem(T->succ, name, sd) ||
+                        PyDict_SetItem(T->pred, name, pd);
+        Py_XDECREF(x);
+        Py_XDECREF(sd);
+        Py_XDECREF(pd);
+        if (bad) return -1;
+        T->sin[i] = sd;
+        T->pin[i] = pd;
+    }
+    return 0;
 }
 
 static PyObject* build_impl(PyObject* self, PyObject* args) {
@@ -94,39 +215,27 @@ static PyObject* build_impl(PyObject* self, PyObject* args) {
     PyObject *names, *ou, *ov, *ow, *oe, *shared = NULL;
     if (!PyArg_ParseTuple(args, "O!OOOO|O!", &PyList_Type, &names, &ou, &ov, &ow, &oe, &PyDict_Type, &shared))
         return NULL;
-    Py_buffer bu, bv, bw, be;
-    if (take(ou, &bu, 8, "u") != 0) return NULL;
-    if (take(ov, &bv, 8, "v") != 0) { PyBuffer_Release(&bu); return NULL; }
-    if (take(ow, &bw, 4, "weight") != 0) { PyBuffer_Release(&bu); PyBuffer_Release(&bv); return NULL; }
-    if (take(oe, &be, 4, "end") != 0) {
-        PyBuffer_Release(&bu); PyBuffer_Release(&bv); PyBuffer_Release(&bw);
-        return NULL;
-    }
-    PyObject *node = NULL, *succ = NULL, *pred = NULL, *kw = NULL, *ke = NULL, *tmpl = NULL, *out = NULL;
-    PyObject** sin = NULL;
-    PyObject** pin = NULL;
-    Py_ssize_t* deg = NULL;
+    Py_buffer bu = {0}, bv = {0}, bw = {0}, be = {0};
+    PyObject* out = NULL;
+    Tops T;
+    memset(&T, 0, sizeof(T));
+    Attrs A;
+    memset(&A, 0, sizeof(A));
+    int64_t* deg = NULL;
+    if (take(ou, &bu, 8, "u") || take(ov, &bv, 8, "v") || take(ow, &bw, 4, "weight") || take(oe, &be, 4, "end"))
+        goto done;
     const Py_ssize_t n_nodes = PyList_GET_SIZE(names);
     const Py_ssize_t n = bu.len / 8;
-    if (bv.len / 8 != n || bw.len / 4 != n || be.len / 4 != n) {
-        PyErr_SetString(PyExc_ValueError, "u, v, weight and end must have the same length");
-        goto done;
-    }
-    node = PyDict_New();
-    succ = PyDict_New();
-    pred = PyDict_New();
-    kw = PyUnicode_InternFromString("weight");
-    ke = PyUnicode_InternFromString("end_position");
-    sin = (PyObject**)PyMem_Malloc(sizeof(PyObject*) * (size_t)(n_nodes ? n_nodes : 1));
-    pin = (PyObject**)PyMem_Malloc(sizeof(PyObject*) * (size_t)(n_nodes ? n_nodes : 1));
-    if (!node || !succ || !pred || !kw || !ke || !sin || !pin) { PyErr_NoMemory(); goto done; }
     const int64_t* u = (const int64_t*)bu.buf;
     const int64_t* v = (const int64_t*)bv.buf;
     const int32_t* w = (const int32_t*)bw.buf;
     const int32_t* e = (const int32_t*)be.buf;
-    /* out- and in-degrees first, so every successor / predecessor dict is created at its final size
-       (no rehash while it fills) */
-    deg = (Py_ssize_t*)PyMem_Calloc((size_t)(2 * n_nodes + 1), sizeof(Py_ssize_t));
+    if (bv.len / 8 != n || bw.len / 4 != n || be.len / 4 != n) {
+        PyErr_SetString(PyExc_ValueError, "u, v, weight and end must have the same length");
+        goto done;
+    }
+    /* out- and in-degrees first: the dicts' final sizes */
+    deg = NEW0(int64_t, 2 * n_nodes);
     if (!deg) { PyErr_NoMemory(); goto done; }
     for (Py_ssize_t k = 0; k < n; ++k) {
         if (u[k] < 0 || u[k] >= n_nodes || v[k] < 0 || v[k] >= n_nodes) {
@@ -136,60 +245,23 @@ static PyObject* build_impl(PyObject* self, PyObject* args) {
         ++deg[u[k]];
         ++deg[n_nodes + v[k]];
     }
-    for (Py_ssize_t i = 0; i < n_nodes; ++i) {
-        PyObject* name = PyList_GET_ITEM(names, i);
-        PyObject* a = PyDict_New();
-        PyObject* s = _PyDict_NewPresized(deg[i]);
-        PyObject* p = _PyDict_NewPresized(deg[n_nodes + i]);
-        if (!a || !s || !p || PyDict_SetItem(node, name, a) || PyDict_SetItem(succ, name, s) ||
-            PyDict_SetItem(pred, name, p)) {
-            Py_XDECREF(a); Py_XDECREF(s); Py_XDECREF(p);
-            goto done;
-        }
-        Py_DECREF(a);
-        Py_DECREF(s);
-        Py_DECREF(p);
-        sin[i] = s;  /* borrowed: succ / pred hold the references */
-        pin[i] = p;
-    }
-    /* attribute dicts are copies of one two-key template with the values replaced in place, cheaper than
-       growing an empty dict by two inserts.  With `shared` (an instance __dict__ holding exactly the two keys,
-       PEP 412 key-sharing) every copy shares the template's key table and owns only its values: 104 instead
-       of 232 bytes per edge, and still an ordinary dict (a key added later converts that one dict) */
-    if (shared && PyDict_GET_SIZE(shared) == 2 && PyDict_Contains(shared, kw) == 1 && PyDict_Contains(shared, ke) == 1) {
-        tmpl = shared;
-        Py_INCREF(tmpl);
-    } else {
-        tmpl = PyDict_New();
-        if (!tmpl || PyDict_SetItem(tmpl, kw, Py_None) || PyDict_SetItem(tmpl, ke, Py_None)) goto done;
-    }
+    if (tops_make(&T, names, deg, deg + n_nodes) || attrs_init(&A, shared)) goto done;
     for (Py_ssize_t k = 0; k < n; ++k) {
-        PyObject* d = PyDict_Copy(tmpl);
-        PyObject* wv = PyLong_FromLong(w[k]);
-        PyObject* ev = PyLong_FromLong(e[k]);
-        int bad = !d || !wv || !ev || PyDict_SetItem(d, kw, wv) || PyDict_SetItem(d, ke, ev) ||
-                  PyDict_SetItem(sin[u[k]], PyList_GET_ITEM(names, v[k]), d) ||
-                  PyDict_SetItem(pin[v[k]], PyList_GET_ITEM(names, u[k]), d);
-        Py_XDECREF(wv);
-        Py_XDECREF(ev);
+        PyObject* d = attrs_edge(&A, w[k], e[k]);
+        const int bad = !d || PyDict_SetItem(T.sin[u[k]], PyList_GET_ITEM(names, v[k]), d) ||
+                        PyDict_SetItem(T.pin[v[k]], PyList_GET_ITEM(names, u[k]), d);
         Py_XDECREF(d);
         if (bad) goto done;
     }
-    out = PyTuple_Pack(3, node, succ, pred);
+    out = PyTuple_Pack(3, T.node, T.succ, T.pred);
 done:
-    PyMem_Free(sin);
-    PyMem_Free(pin);
     PyMem_Free(deg);
-    Py_XDECREF(node);
-    Py_XDECREF(succ);
-    Py_XDECREF(pred);
-    Py_XDECREF(tmpl);
-    Py_XDECREF(kw);
-    Py_XDECREF(ke);
-    PyBuffer_Release(&bu);
-    PyBuffer_Release(&bv);
-    PyBuffer_Release(&bw);
-    PyBuffer_Release(&be);
+    tops_free(&T);
+    attrs_free(&A);
+    if (bu.obj) PyBuffer_Release(&bu);
+    if (bv.obj) PyBuffer_Release(&bv);
+    if (bw.obj) PyBuffer_Release(&bw);
+    if (be.obj) PyBuffer_Release(&be);
     return out;
 }
 
@@ -229,9 +301,9 @@ static PyObject* csr(PyObject* self, PyObject* args) {
     if (!PyArg_ParseTuple(args, "O!O!|O", &PyList_Type, &nodes, &PyDict_Type, &adj, &more)) return NULL;
     const Py_ssize_t n_nodes = PyList_GET_SIZE(nodes);
     PyObject *index = NULL, *boff = NULL, *bheads = NULL, *bw = NULL, *kw = NULL, *out = NULL;
-    PyObject** rows = (PyObject**)PyMem_Malloc(sizeof(PyObject*) * (size_t)(n_nodes ? n_nodes : 1));
+    PyObject** rows = NEW(PyObject*, n_nodes);
     index = PyDict_New();
-    kw = PyUnicode_InternFromString("weight");
+    kw = key_weight();
     boff = PyByteArray_FromStringAndSize(NULL, (Py_ssize_t)(8 * (n_nodes + 1)));
     if (!rows || !index || !kw || !boff) { if (!PyErr_Occurred()) PyErr_NoMemory(); goto done; }
     int64_t* off = (int64_t*)PyByteArray_AS_STRING(boff);
@@ -252,8 +324,8 @@ static PyObject* csr(PyObject* self, PyObject* args) {
         off[i + 1] = off[i] + PyDict_GET_SIZE(row);
     }
     const int64_t n_edges = off[n_nodes];
-    bheads = PyByteArray_FromStringAndSize(NULL, (Py_ssize_t)(4 * (n_edges ? n_edges : 1)));
-    bw = PyByteArray_FromStringAndSize(NULL, (Py_ssize_t)(8 * (n_edges ? n_edges : 1)));
+    bheads = PyByteArray_FromStringAndSize(NULL, (Py_ssize_t)(4 * nz(n_edges)));
+    bw = PyByteArray_FromStringAndSize(NULL, (Py_ssize_t)(8 * nz(n_edges)));
     if (!bheads || !bw) goto done;
     int32_t* heads = (int32_t*)PyByteArray_AS_STRING(bheads);
     long long* wts = (long long*)PyByteArray_AS_STRING(bw);
@@ -320,6 +392,48 @@ done:
     return ret;
 }
 
+/* The pair columns of overlap_csr and the two column builders: counts (int32, one per read); a, b, score and end
+   (int32, one per pair; overlap_csr takes no end); the optional keep mask (uint8 per pair, or None). */
+typedef struct {
+    Py_buffer bc, ba, bb, bs, be, bk;
+    Py_ssize_t R, P;  /* reads, pairs */
+    const int32_t *counts, *a, *b, *sc, *en;
+    const uint8_t* keep;  /* NULL: every pair is kept */
+} PairCols;
+
+static void pairs_release(PairCols* Q) {
+    Py_buffer* const all[] = {&Q->bc, &Q->ba, &Q->bb, &Q->bs, &Q->be, &Q->bk};
+    for (int i = 0; i < 6; ++i)
+        if (all[i]->obj) PyBuffer_Release(all[i]);
+}
+
+/* oe NULL: no end column.  0, or -1 with an exception set; pairs_release is due either way. */
+static int pairs_take(PairCols* Q, PyObject* oc, PyObject* oa, PyObject* ob, PyObject* os, PyObject* oe,
+                      PyObject* ok) {
+    memset(Q, 0, sizeof(*Q));
+    if (take(oc, &Q->bc, 4, "counts") || take(oa, &Q->ba, 4, "a") || take(ob, &Q->bb, 4, "b")) return -1;
+    if (Q->ba.len != Q->bb.len) { PyErr_SetString(PyExc_ValueError, "a and b must have the same length"); return -1; }
+    Q->R = Q->bc.len / 4;
+    Q->P = Q->ba.len / 4;
+    if (ok && ok != Py_None) {
+        if (take(ok, &Q->bk, 1, "keep")) return -1;
+        if (Q->bk.len != Q->P) { PyErr_SetString(PyExc_ValueError, "keep must have one entry per pair"); return -1; }
+        Q->keep = (const uint8_t*)Q->bk.buf;
+    }
+    if (take(os, &Q->bs, 4, "score") || (oe && take(oe, &Q->be, 4, "end"))) return -1;
+    if (Q->bs.len != Q->ba.len || (oe && Q->be.len != Q->ba.len)) {
+        PyErr_SetString(PyExc_ValueError, oe ? "score and end must have one entry per pair"
+                                             : "score must have one entry per pair");
+        return -1;
+    }
+    Q->counts = (const int32_t*)Q->bc.buf;
+    Q->a = (const int32_t*)Q->ba.buf;
+    Q->b = (const int32_t*)Q->bb.buf;
+    Q->sc = (const int32_t*)Q->bs.buf;
+    Q->en = (const int32_t*)Q->be.buf;
+    return 0;
+}
+
 /* The CSR layout of the overlap graph from the pair columns.  Pairs are grouped by read a (counting sort,
  * list order kept inside a group); row u = first[r] + c of read r has len rowlen[r] = sum of counts[b[p]] over
  * the group, the same for every copy c; pair p's edges sit at off[u] + pstart[p] + cb.  Returns 0, or -1 with
@@ -345,16 +459,18 @@ static void layout_free(Layout* L) {
     memset(L, 0, sizeof(*L));
 }
 
-static int layout(Layout* L, const int32_t* counts, Py_ssize_t R, const int32_t* a, const int32_t* b, Py_ssize_t P,
-                  const uint8_t* keep) {
+static int layout(Layout* L, const PairCols* Q) {
+    const int32_t *counts = Q->counts, *a = Q->a, *b = Q->b;
+    const uint8_t* keep = Q->keep;
+    const Py_ssize_t R = Q->R, P = Q->P;
     memset(L, 0, sizeof(*L));
     L->R = R;
     L->P = P;
-    L->first = (int64_t*)PyMem_Calloc((size_t)R + 1, sizeof(int64_t));
-    L->goff = (int64_t*)PyMem_Calloc((size_t)R + 1, sizeof(int64_t));
-    L->plist = (int64_t*)PyMem_Malloc(sizeof(int64_t) * (size_t)(P ? P : 1));
-    L->rowlen = (int64_t*)PyMem_Calloc((size_t)(R ? R : 1), sizeof(int64_t));
-    L->pstart = (int64_t*)PyMem_Calloc((size_t)(P ? P : 1), sizeof(int64_t));
+    L->first = NEW0(int64_t, R + 1);
+    L->goff = NEW0(int64_t, R + 1);
+    L->plist = NEW(int64_t, P);
+    L->rowlen = NEW0(int64_t, R);
+    L->pstart = NEW0(int64_t, P);
     if (!L->first || !L->goff || !L->plist || !L->rowlen || !L->pstart) { PyErr_NoMemory(); return -1; }
     for (Py_ssize_t r = 0; r < R; ++r) {
         if (counts[r] < 0) { PyErr_SetString(PyExc_ValueError, "negative copy count"); return -1; }
@@ -370,7 +486,7 @@ static int layout(Layout* L, const int32_t* counts, Py_ssize_t R, const int32_t*
         ++L->goff[a[p] + 1];
     }
     for (Py_ssize_t r = 0; r < R; ++r) L->goff[r + 1] += L->goff[r];
-    int64_t* fill = (int64_t*)PyMem_Malloc(sizeof(int64_t) * (size_t)(R ? R : 1));
+    int64_t* fill = NEW(int64_t, R);
     if (!fill) { PyErr_NoMemory(); return -1; }
     memcpy(fill, L->goff, sizeof(int64_t) * (size_t)R);
     for (Py_ssize_t p = 0; p < P; ++p) {
@@ -381,7 +497,7 @@ static int layout(Layout* L, const int32_t* counts, Py_ssize_t R, const int32_t*
         L->rowlen[r] += counts[b[p]];
     }
     PyMem_Free(fill);
-    L->off = (int64_t*)PyMem_Malloc(sizeof(int64_t) * ((size_t)L->N + 1));
+    L->off = NEW(int64_t, L->N + 1);
     if (!L->off) { PyErr_NoMemory(); return -1; }
     L->off[0] = 0;
     for (Py_ssize_t r = 0; r < R; ++r)
@@ -390,98 +506,47 @@ static int layout(Layout* L, const int32_t* counts, Py_ssize_t R, const int32_t*
     return 0;
 }
 
-/* the columns of overlap_csr / build_overlap: counts, a, b (int32) and the optional keep mask (uint8 or None) */
-typedef struct {
-    Py_buffer c, a, b, k;
-    int has_k;
-} Cols;
-
-static void cols_release(Cols* C) {
-    if (C->c.obj) PyBuffer_Release(&C->c);
-    if (C->a.obj) PyBuffer_Release(&C->a);
-    if (C->b.obj) PyBuffer_Release(&C->b);
-    if (C->has_k && C->k.obj) PyBuffer_Release(&C->k);
-}
-
-static int cols_take(Cols* C, PyObject* oc, PyObject* oa, PyObject* ob, PyObject* ok) {
-    memset(C, 0, sizeof(*C));
-    if (take(oc, &C->c, 4, "counts") || take(oa, &C->a, 4, "a") || take(ob, &C->b, 4, "b")) return -1;
-    if (C->a.len != C->b.len) { PyErr_SetString(PyExc_ValueError, "a and b must have the same length"); return -1; }
-    if (ok && ok != Py_None) {
-        if (take(ok, &C->k, 1, "keep")) return -1;
-        C->has_k = 1;
-        if (C->k.len != C->a.len / 4) { PyErr_SetString(PyExc_ValueError, "keep must have one entry per pair"); return -1; }
-    }
-    return 0;
-}
-
 static PyObject* overlap_csr(PyObject* self, PyObject* args) {
     (void)self;
     PyObject *oc, *oa, *ob, *os, *ok = NULL;
     if (!PyArg_ParseTuple(args, "OOOO|O", &oc, &oa, &ob, &os, &ok)) return NULL;
-    Cols C;
-    Py_buffer bs;
-    memset(&bs, 0, sizeof(bs));
+    PairCols Q;
     Layout L;
     memset(&L, 0, sizeof(L));
     PyObject *boff = NULL, *bh = NULL, *bw = NULL, *out = NULL;
-    if (cols_take(&C, oc, oa, ob, ok) || take(os, &bs, 4, "score")) goto done;
-    if (bs.len != C.a.len) { PyErr_SetString(PyExc_ValueError, "score must have one entry per pair"); goto done; }
-    {
-        const int32_t* counts = (const int32_t*)C.c.buf;
-        const int32_t* a = (const int32_t*)C.a.buf;
-        const int32_t* b = (const int32_t*)C.b.buf;
-        const int32_t* sc = (const int32_t*)bs.buf;
-        if (layout(&L, counts, C.c.len / 4, a, b, C.a.len / 4, C.has_k ? (const uint8_t*)C.k.buf : NULL)) goto done;
-        boff = PyByteArray_FromStringAndSize((const char*)L.off, (Py_ssize_t)(8 * ((size_t)L.N + 1)));
-        bh = PyByteArray_FromStringAndSize(NULL, (Py_ssize_t)(4 * (L.E ? L.E : 1)));
-        bw = PyByteArray_FromStringAndSize(NULL, (Py_ssize_t)(8 * (L.E ? L.E : 1)));
-        if (!boff || !bh || !bw) goto done;
-        int32_t* heads = (int32_t*)PyByteArray_AS_STRING(bh);
-        int64_t* wts = (int64_t*)PyByteArray_AS_STRING(bw);
-        for (Py_ssize_t r = 0; r < L.R; ++r) {
-            if (L.first[r + 1] == L.first[r]) continue;
-            const int64_t u0 = L.first[r];
-            int64_t e = L.off[u0];
-            for (int64_t g = L.goff[r]; g < L.goff[r + 1]; ++g) {
-                const int64_t p = L.plist[g];
-                const int64_t v0 = L.first[b[p]];
-                for (int32_t cb = 0; cb < counts[b[p]]; ++cb, ++e) {
-                    heads[e] = (int32_t)(v0 + cb);
-                    wts[e] = sc[p];
-                }
-            }
-            /* every other copy of read r has the same row */
-            for (int64_t u = u0 + 1; u < L.first[r + 1]; ++u) {
-                memcpy(heads + L.off[u], heads + L.off[u0], sizeof(int32_t) * (size_t)L.rowlen[r]);
-                memcpy(wts + L.off[u], wts + L.off[u0], sizeof(int64_t) * (size_t)L.rowlen[r]);
+    if (pairs_take(&Q, oc, oa, ob, os, NULL, ok) || layout(&L, &Q)) goto done;
+    boff = PyByteArray_FromStringAndSize((const char*)L.off, (Py_ssize_t)(8 * ((size_t)L.N + 1)));
+    bh = PyByteArray_FromStringAndSize(NULL, (Py_ssize_t)(4 * nz(L.E)));
+    bw = PyByteArray_FromStringAndSize(NULL, (Py_ssize_t)(8 * nz(L.E)));
+    if (!boff || !bh || !bw) goto done;
+    int32_t* heads = (int32_t*)PyByteArray_AS_STRING(bh);
+    int64_t* wts = (int64_t*)PyByteArray_AS_STRING(bw);
+    for (Py_ssize_t r = 0; r < L.R; ++r) {
+        if (L.first[r + 1] == L.first[r]) continue;
+        const int64_t u0 = L.first[r];
+        int64_t e = L.off[u0];
+        for (int64_t g = L.goff[r]; g < L.goff[r + 1]; ++g) {
+            const int64_t p = L.plist[g];
+            const int64_t v0 = L.first[Q.b[p]];
+            for (int32_t cb = 0; cb < Q.counts[Q.b[p]]; ++cb, ++e) {
+                heads[e] = (int32_t)(v0 + cb);
+                wts[e] = Q.sc[p];
             }
         }
-        out = PyTuple_Pack(3, boff, bh, bw);
+        /* every other copy of read r has the same row */
+        for (int64_t u = u0 + 1; u < L.first[r + 1]; ++u) {
+            memcpy(heads + L.off[u], heads + L.off[u0], sizeof(int32_t) * (size_t)L.rowlen[r]);
+            memcpy(wts + L.off[u], wts + L.off[u0], sizeof(int64_t) * (size_t)L.rowlen[r]);
+        }
     }
+    out = PyTuple_Pack(3, boff, bh, bw);
 done:
     layout_free(&L);
-    cols_release(&C);
-    if (bs.obj) PyBuffer_Release(&bs);
+    pairs_release(&Q);
     Py_XDECREF(boff);
     Py_XDECREF(bh);
     Py_XDECREF(bw);
     return out;
-}
-
-/* Python ints for edge attributes: one object per distinct value in [kIntLo, kIntHi) (scores <= 10 * l and end
- * positions <= l for the reads of the benchmark configs), shared by every edge that carries it, instead of two
- * allocations per pair; values outside the range are created per pair. */
-enum { kIntLo = -4096, kIntHi = 8192 };
-
-static PyObject* int_of(PyObject** cache, long v) {
-    if (v >= kIntLo && v < kIntHi) {
-        PyObject** slot = &cache[v - kIntLo];
-        if (!*slot) *slot = PyLong_FromLong(v);
-        Py_XINCREF(*slot);
-        return *slot;
-    }
-    return PyLong_FromLong(v);
 }
 
 static PyObject* build_overlap_impl(PyObject* self, PyObject* args) {
@@ -490,140 +555,82 @@ static PyObject* build_overlap_impl(PyObject* self, PyObject* args) {
     if (!PyArg_ParseTuple(args, "O!OOOOO|OOO!", &PyList_Type, &names, &oc, &oa, &ob, &os, &oe, &ok, &oalive,
                           &PyDict_Type, &shared))
         return NULL;
-    Cols C;
-    memset(&C, 0, sizeof(C));
-    Py_buffer bs, be, bal;
-    memset(&bs, 0, sizeof(bs));
-    memset(&be, 0, sizeof(be));
+    PairCols Q;
+    memset(&Q, 0, sizeof(Q));
+    Py_buffer bal;
     memset(&bal, 0, sizeof(bal));
     Layout L;
     memset(&L, 0, sizeof(L));
-    PyObject *node = NULL, *succ = NULL, *pred = NULL, *kw = NULL, *ke = NULL, *tmpl = NULL, *out = NULL;
-    PyObject **sin = NULL, **pin = NULL;
-    PyObject** ints = (PyObject**)PyMem_Calloc((size_t)(kIntHi - kIntLo), sizeof(PyObject*));
+    Tops T;
+    memset(&T, 0, sizeof(T));
+    Attrs A;
+    memset(&A, 0, sizeof(A));
+    PyObject* out = NULL;
     int64_t *dout = NULL, *din = NULL;
-    if (!ints) { PyErr_NoMemory(); goto done; }
-    if (cols_take(&C, oc, oa, ob, ok) || take(os, &bs, 4, "score") || take(oe, &be, 4, "end")) goto done;
-    if (bs.len != C.a.len || be.len != C.a.len) {
-        PyErr_SetString(PyExc_ValueError, "score and end must have one entry per pair");
+    const uint8_t* alive = NULL;
+    if (pairs_take(&Q, oc, oa, ob, os, oe, ok) || layout(&L, &Q)) goto done;
+    if (PyList_GET_SIZE(names) != L.N) {
+        PyErr_Format(PyExc_ValueError, "%zd names for %zd nodes", PyList_GET_SIZE(names), L.N);
         goto done;
     }
-    {
-        const int32_t* counts = (const int32_t*)C.c.buf;
-        const int32_t* a = (const int32_t*)C.a.buf;
-        const int32_t* b = (const int32_t*)C.b.buf;
-        const int32_t* sc = (const int32_t*)bs.buf;
-        const int32_t* en = (const int32_t*)be.buf;
-        const uint8_t* keep = C.has_k ? (const uint8_t*)C.k.buf : NULL;
-        if (layout(&L, counts, C.c.len / 4, a, b, C.a.len / 4, keep)) goto done;
-        const Py_ssize_t n_nodes = PyList_GET_SIZE(names);
-        if (n_nodes != L.N) {
-            PyErr_Format(PyExc_ValueError, "%zd names for %zd nodes", n_nodes, L.N);
-            goto done;
-        }
-        const uint8_t* alive = NULL;
-        if (oalive && oalive != Py_None) {
-            if (take(oalive, &bal, 1, "alive")) goto done;
-            if (bal.len != L.E) { PyErr_SetString(PyExc_ValueError, "alive must have one entry per edge"); goto done; }
-            alive = (const uint8_t*)bal.buf;
-        }
-        /* live degrees: every dict is created at its final size */
-        dout = (int64_t*)PyMem_Calloc((size_t)(L.N ? L.N : 1), sizeof(int64_t));
-        din = (int64_t*)PyMem_Calloc((size_t)(L.N ? L.N : 1), sizeof(int64_t));
-        sin = (PyObject**)PyMem_Malloc(sizeof(PyObject*) * (size_t)(L.N ? L.N : 1));
-        pin = (PyObject**)PyMem_Malloc(sizeof(PyObject*) * (size_t)(L.N ? L.N : 1));
-        if (!dout || !din || !sin || !pin) { PyErr_NoMemory(); goto done; }
-        for (Py_ssize_t g = 0; g < (Py_ssize_t)L.goff[L.R]; ++g) {
-            const int64_t p = L.plist[g];
-            for (int64_t u = L.first[a[p]]; u < L.first[a[p] + 1]; ++u) {
-                const int64_t e0 = L.off[u] + L.pstart[p];
-                for (int32_t cb = 0; cb < counts[b[p]]; ++cb)
-                    if (!alive || alive[e0 + cb]) {
-                        ++dout[u];
-                        ++din[L.first[b[p]] + cb];
-                    }
-            }
-        }
-        node = PyDict_New();
-        succ = PyDict_New();
-        pred = PyDict_New();
-        kw = PyUnicode_InternFromString("weight");
-        ke = PyUnicode_InternFromString("end_position");
-        if (!node || !succ || !pred || !kw || !ke) goto done;
-        for (Py_ssize_t i = 0; i < n_nodes; ++i) {
-            PyObject* name = PyList_GET_ITEM(names, i);
-            PyObject* x = PyDict_New();
-            PyObject* sd = _PyDict_NewPresized(dout[i]);
-            PyObject* pd = _PyDict_NewPresized(din[i]);
-            if (!x || !sd || !pd || PyDict_SetItem(node, name, x) || PyDict_SetItem(succ, name, sd) ||
-                PyDict_SetItem(pred, name, pd)) {
-                Py_XDECREF(x); Py_XDECREF(sd); Py_XDECREF(pd);
-                goto done;
-            }
-            Py_DECREF(x);
-            Py_DECREF(sd);
-            Py_DECREF(pd);
-            sin[i] = sd;
-            pin[i] = pd;
-        }
-        if (shared && PyDict_GET_SIZE(shared) == 2 && PyDict_Contains(shared, kw) == 1 && PyDict_Contains(shared, ke) == 1) {
-            tmpl = shared;
-            Py_INCREF(tmpl);
-        } else {
-            tmpl = PyDict_New();
-            if (!tmpl || PyDict_SetItem(tmpl, kw, Py_None) || PyDict_SetItem(tmpl, ke, Py_None)) goto done;
-        }
-        Py_ssize_t iw, ie;
-        attr_slots(tmpl, kw, ke, &iw, &ie);
-        /* one pass over the edges in global insertion order (pair, copy of a, copy of b: overlapGraphs.py:43-60):
-           each attribute dict goes into its tail's successor dict and its head's predecessor dict while it is
-           still in cache.  A node's successors arrive in that order too, which is its CSR row order. */
-        for (Py_ssize_t p = 0; p < L.P; ++p) {
-            if (keep && !keep[p]) continue;
-            PyObject *wv = NULL, *ev = NULL;
-            const int64_t vb = L.first[b[p]];
-            for (int64_t u = L.first[a[p]]; u < L.first[a[p] + 1]; ++u) {
-                const int64_t e0 = L.off[u] + L.pstart[p];
-                PyObject* un = PyList_GET_ITEM(names, u);
-                for (int32_t cb = 0; cb < counts[b[p]]; ++cb) {
-                    if (alive && !alive[e0 + cb]) continue;
-                    if (!wv) {
-                        wv = int_of(ints, sc[p]);
-                        ev = int_of(ints, en[p]);
-                        if (!wv || !ev) { Py_XDECREF(wv); Py_XDECREF(ev); goto done; }
-                    }
-                    PyObject* d = new_attr(tmpl, kw, ke, iw, ie, wv, ev);
-                    const int bad = !d || PyDict_SetItem(sin[u], PyList_GET_ITEM(names, vb + cb), d) ||
-                                    PyDict_SetItem(pin[vb + cb], un, d);
-                    Py_XDECREF(d);
-                    if (bad) { Py_XDECREF(wv); Py_XDECREF(ev); goto done; }
-                }
-            }
-            Py_XDECREF(wv);
-            Py_XDECREF(ev);
-        }
-        out = PyTuple_Pack(3, node, succ, pred);
+    if (oalive && oalive != Py_None) {
+        if (take(oalive, &bal, 1, "alive")) goto done;
+        if (bal.len != L.E) { PyErr_SetString(PyExc_ValueError, "alive must have one entry per edge"); goto done; }
+        alive = (const uint8_t*)bal.buf;
     }
+    /* live degrees: every dict is created at its final size */
+    dout = NEW0(int64_t, L.N);
+    din = NEW0(int64_t, L.N);
+    if (!dout || !din) { PyErr_NoMemory(); goto done; }
+    for (Py_ssize_t g = 0; g < (Py_ssize_t)L.goff[L.R]; ++g) {
+        const int64_t p = L.plist[g];
+        for (int64_t u = L.first[Q.a[p]]; u < L.first[Q.a[p] + 1]; ++u) {
+            const int64_t e0 = L.off[u] + L.pstart[p];
+            for (int32_t cb = 0; cb < Q.counts[Q.b[p]]; ++cb)
+                if (!alive || alive[e0 + cb]) {
+                    ++dout[u];
+                    ++din[L.first[Q.b[p]] + cb];
+                }
+        }
+    }
+    if (tops_make(&T, names, dout, din) || attrs_init(&A, shared)) goto done;
+    /* one pass over the edges in global insertion order (pair, copy of a, copy of b: overlapGraphs.py:43-60):
+       each attribute dict goes into its tail's successor dict and its head's predecessor dict while it is
+       still in cache.  A node's successors arrive in that order too, which is its CSR row order.  The two ints
+       are made once per pair and shared by all its copies. */
+    for (Py_ssize_t p = 0; p < L.P; ++p) {
+        if (Q.keep && !Q.keep[p]) continue;
+        PyObject *wv = NULL, *ev = NULL;
+        int bad = 0;
+        const int64_t vb = L.first[Q.b[p]];
+        for (int64_t u = L.first[Q.a[p]]; u < L.first[Q.a[p] + 1] && !bad; ++u) {
+            const int64_t e0 = L.off[u] + L.pstart[p];
+            PyObject* un = PyList_GET_ITEM(names, u);
+            for (int32_t cb = 0; cb < Q.counts[Q.b[p]] && !bad; ++cb) {
+                if (alive && !alive[e0 + cb]) continue;
+                if (!wv) {
+                    wv = int_of(A.ints, Q.sc[p]);
+                    ev = int_of(A.ints, Q.en[p]);
+                }
+                PyObject* d = wv && ev ? attrs_dict(&A, wv, ev) : NULL;
+                bad = !d || PyDict_SetItem(T.sin[u], PyList_GET_ITEM(names, vb + cb), d) ||
+                      PyDict_SetItem(T.pin[vb + cb], un, d);
+                Py_XDECREF(d);
+            }
+        }
+        Py_XDECREF(wv);
+        Py_XDECREF(ev);
+        if (bad) goto done;
+    }
+    out = PyTuple_Pack(3, T.node, T.succ, T.pred);
 done:
     layout_free(&L);
-    cols_release(&C);
-    if (bs.obj) PyBuffer_Release(&bs);
-    if (be.obj) PyBuffer_Release(&be);
+    pairs_release(&Q);
     if (bal.obj) PyBuffer_Release(&bal);
-    if (ints) {
-        for (int i = 0; i < kIntHi - kIntLo; ++i) Py_XDECREF(ints[i]);
-        PyMem_Free(ints);
-    }
     PyMem_Free(dout);
     PyMem_Free(din);
-    PyMem_Free(sin);
-    PyMem_Free(pin);
-    Py_XDECREF(node);
-    Py_XDECREF(succ);
-    Py_XDECREF(pred);
-    Py_XDECREF(tmpl);
-    Py_XDECREF(kw);
-    Py_XDECREF(ke);
+    tops_free(&T);
+    attrs_free(&A);
     return out;
 }
 
@@ -652,13 +659,13 @@ typedef struct {
 static void* scc_main(void* arg) {
     SccJob* j = (SccJob*)arg;
     const int32_t N = j->n;
-    int32_t* index = (int32_t*)malloc(sizeof(int32_t) * (size_t)(N ? N : 1));
-    int32_t* low = (int32_t*)malloc(sizeof(int32_t) * (size_t)(N ? N : 1));
-    int32_t* stk = (int32_t*)malloc(sizeof(int32_t) * (size_t)(N ? N : 1));
-    int32_t* cv = (int32_t*)malloc(sizeof(int32_t) * (size_t)(N ? N : 1));  /* call stack: node */
-    int64_t* cp = (int64_t*)malloc(sizeof(int64_t) * (size_t)(N ? N : 1));  /* call stack: next edge */
-    uint8_t* on = (uint8_t*)malloc((size_t)(N ? N : 1));
-    uint8_t* alone = (uint8_t*)calloc((size_t)(N ? N : 1), 1);
+    int32_t* index = (int32_t*)malloc(sizeof(int32_t) * nz(N));
+    int32_t* low = (int32_t*)malloc(sizeof(int32_t) * nz(N));
+    int32_t* stk = (int32_t*)malloc(sizeof(int32_t) * nz(N));
+    int32_t* cv = (int32_t*)malloc(sizeof(int32_t) * nz(N));  /* call stack: node */
+    int64_t* cp = (int64_t*)malloc(sizeof(int64_t) * nz(N));  /* call stack: next edge */
+    uint8_t* on = (uint8_t*)malloc(nz(N));
+    uint8_t* alone = (uint8_t*)calloc(nz(N), 1);
     if (!index || !low || !stk || !cv || !cp || !on || !alone) goto out;
     j->ok = 1;
     while (!__atomic_load_n(j->stop, __ATOMIC_ACQUIRE)) {
@@ -740,260 +747,6 @@ out:
     return NULL;
 }
 
-/* A node's predecessor dict, built as a prefix of its in-edges in insertion order (kept pairs with b == its read in
-   list order, then the copies of a): the cursor (pg, pt: pair group and tail copy) advances while the next in-edge's
-   fate is known (its tail's successor row has passed it: dec), inserting the live ones. */
-typedef struct {
-    const Layout* L;
-    const int32_t* a;
-    const int64_t* blist;
-    const int64_t* bgoff;
-    const int64_t* rread;
-    const int64_t* indeg;   /* in-edges of the node, live or not (the dict's presize) */
-    const uint8_t* dec;     /* per edge: its fate is known (its tail's row has passed it) */
-    PyObject* const* dptr;
-    PyObject* names;
-    PyObject** pin;
-    int64_t* pg;            /* -1: complete */
-    int64_t* pt;
-    int64_t n_pred;
-} PredCtx;
-
-static int pred_advance(PredCtx* X, int64_t v) {
-    int64_t g = X->pg[v];
-    if (g < 0) return 0;
-    const Py_ssize_t rv = (Py_ssize_t)X->rread[v];
-    const int64_t gend = X->bgoff[rv + 1];
-    const int64_t cv = v - X->L->first[rv];
-    int64_t t = X->pt[v];
-    while (g < gend) {
-        const int64_t q = X->blist[g];
-        const int64_t tend = X->L->first[X->a[q] + 1];
-        for (; t < tend; ++t) {
-            const int64_t e = X->L->off[t] + X->L->pstart[q] + cv;
-            if (!X->dec[e]) {
-                X->pg[v] = g;
-                X->pt[v] = t;
-                return 0;
-            }
-            PyObject* d = X->dptr[e];
-            if (d) {
-                if (!X->pin[v] && !(X->pin[v] = _PyDict_NewPresized(X->indeg[v]))) return -1;
-                if (PyDict_SetItem(X->pin[v], PyList_GET_ITEM(X->names, t), d)) return -1;
-            }
-        }
-        if (++g < gend) t = X->L->first[X->a[X->blist[g]]];
-    }
-    if (!X->pin[v] && !(X->pin[v] = PyDict_New())) return -1;
-    X->pg[v] = -1;
-    ++X->n_pred;
-    return 0;
-}
-
-/* A node's successor dict, built the same way as a prefix of its out-edges in row order (kept pairs with a == its
-   read in list order, then the copies of b): an out-edge's fate is known once it is removed (alive 0: removals are
-   final), once its head is on no cycle (published by the replay or the component helper: no cycle can hold the
-   edge, so it is never removed), or once the tail itself is published (all its out-edges final).  Each edge passed
-   is marked decided and lets its head's predecessor dict advance. */
-typedef struct {
-    PredCtx* P;
-    const int32_t* counts;
-    const int32_t* b;
-    const int32_t* sc;
-    const int32_t* en;
-    const uint8_t* alive;
-    const uint8_t* pub;     /* per node: published (on no cycle) */
-    const int64_t* outdeg;  /* out-edges of the node, live or not (the dict's presize) */
-    PyObject** rows;
-    PyObject** dptr;
-    uint8_t* dec;
-    int64_t* rg;            /* row cursor: pair group (-1: complete) */
-    int32_t* rc;            /*             copy of b */
-    PyObject** ints;
-    PyObject *tmpl, *kw, *ke;
-    Py_ssize_t iw, ie;
-    PyObject** spec;        /* per edge: its attribute dict made ahead of its row (spec_advance), or NULL */
-    int own;                /* dptr holds a reference (only when some (a, b) pair is listed twice, below) */
-    int64_t n_rows;         /* complete rows */
-    int64_t n_dec;          /* decided edges */
-    int64_t n_ins;          /* live edges inserted */
-    int64_t n_spec;         /* attribute dicts made ahead */
-    int64_t n_spec_used;    /* ... and inserted */
-} RowCtx;
-
-/* advance u's row; `all`: u is published (every edge decided).  1 if it moved, 0 if not, -1 on error */
-static int row_advance(RowCtx* R, int64_t u, int all) {
-    int64_t g = R->rg[u];
-    if (g < 0) return 0;
-    const Layout* L = R->P->L;
-    const Py_ssize_t r = (Py_ssize_t)R->P->rread[u];
-    const int64_t gend = L->goff[r + 1];
-    int32_t cb = R->rc[u];
-    int moved = 0;
-    while (g < gend) {
-        const int64_t p = L->plist[g];
-        const int64_t e0 = L->off[u] + L->pstart[p];
-        const int64_t vb = L->first[R->b[p]];
-        const int32_t nb = R->counts[R->b[p]];
-        for (; cb < nb; ++cb) {
-            const int64_t e = e0 + cb;
-            const int live = __atomic_load_n(&R->alive[e], __ATOMIC_ACQUIRE);
-            if (live && !all && !R->pub[vb + cb]) {
-                R->rg[u] = g;
-                R->rc[u] = cb;
-                return moved;
-            }
-            if (live) {
-                if (!R->rows[u] && !(R->rows[u] = _PyDict_NewPresized(R->outdeg[u]))) return -1;
-                PyObject* d = R->spec[e];
-                if (d) {
-                    R->spec[e] = NULL;
-                    ++R->n_spec_used;
-                } else {
-                    PyObject* wv = int_of(R->ints, R->sc[p]);
-                    PyObject* ev = int_of(R->ints, R->en[p]);
-                    d = wv && ev ? new_attr(R->tmpl, R->kw, R->ke, R->iw, R->ie, wv, ev) : NULL;
-                    Py_XDECREF(wv);
-                    Py_XDECREF(ev);
-                }
-                const int bad = !d || PyDict_SetItem(R->rows[u], PyList_GET_ITEM(R->P->names, vb + cb), d);
-                if (bad) {
-                    Py_XDECREF(d);
-                    return -1;
-                }
-                /* dptr[e] is read by the head's predecessor cursor, which may still be short of e.  The row holds
-                   the dict, so dptr borrows it -- unless some (a, b) pair is listed twice (not a list
-                   overlapGraphs.py:43-52 makes, but OverlapEdges accepts it): the second replaces the row's entry
-                   and would free the first dict, so then dptr keeps a reference, released at the exit */
-                if (!R->own) Py_DECREF(d);
-                R->dptr[e] = d;
-                ++R->n_ins;
-            }
-            R->dec[e] = 1;
-            ++R->n_dec;
-            moved = 1;
-            if (pred_advance(R->P, vb + cb)) return -1;
-        }
-        ++g;
-        cb = 0;
-    }
-    if (!R->rows[u] && !(R->rows[u] = PyDict_New())) return -1;
-    R->rg[u] = -1;
-    ++R->n_rows;
-    return 1;
-}
-
-/* Idle work while the replay runs: the attribute dicts of the still-undecided live out-edges of the nodes from *su on,
-   made ahead of their rows (row_advance takes them), up to `budget` of them.  Making an edge's dict is about half of
-   what inserting it costs, and the edges whose fate the replay decides last -- the graph's last cycles -- are
-   otherwise all built after it has ended; an edge removed after its dict was made only costs that dict (released at
-   the end).  Each node once, in node order.  Returns the dicts made (0: every node passed), -1 on error. */
-static int64_t spec_advance(RowCtx* R, int64_t* su, int64_t n_nodes, int64_t budget) {
-    const Layout* L = R->P->L;
-    int64_t made = 0;
-    while (*su < n_nodes && made < budget) {
-        const int64_t u = (*su)++;
-        int64_t g = R->rg[u];
-        if (g < 0 || R->pub[u]) continue;  /* (row complete, or published: built next) */
-        const Py_ssize_t r = (Py_ssize_t)R->P->rread[u];
-        const int64_t gend = L->goff[r + 1];
-        int32_t cb = R->rc[u];
-        for (; g < gend; ++g, cb = 0) {
-            const int64_t p = L->plist[g];
-            const int64_t e0 = L->off[u] + L->pstart[p];
-            const int32_t nb = R->counts[R->b[p]];
-            for (; cb < nb; ++cb) {
-                const int64_t e = e0 + cb;
-                if (R->spec[e] || !__atomic_load_n(&R->alive[e], __ATOMIC_ACQUIRE)) continue;
-                PyObject* wv = int_of(R->ints, R->sc[p]);
-                PyObject* ev = int_of(R->ints, R->en[p]);
-                PyObject* d = wv && ev ? new_attr(R->tmpl, R->kw, R->ke, R->iw, R->ie, wv, ev) : NULL;
-                Py_XDECREF(wv);
-                Py_XDECREF(ev);
-                if (!d) return -1;
-                R->spec[e] = d;
-                ++made;
-            }
-        }
-    }
-    R->n_spec += made;
-    return made;
-}
-
-/* Idle work once every node has had its dicts made ahead: release the made-ahead dicts of edges the replay has
-   removed since, `budget` entries of the edge array per call, cycling over it, so that few are left to release after
-   the replay.  Returns the dicts released. */
-static int64_t spec_reap(RowCtx* R, int64_t* re, int64_t n_edges, int64_t budget) {
-    int64_t freed = 0;
-    for (int64_t k = 0; k < budget && n_edges > 0; ++k) {
-        const int64_t e = (*re)++;
-        if (*re >= n_edges) *re = 0;
-        PyObject* d = R->spec[e];
-        if (d && !__atomic_load_n(&R->alive[e], __ATOMIC_ACQUIRE)) {
-            R->spec[e] = NULL;
-            Py_DECREF(d);
-            ++freed;
-        }
-    }
-    return freed;
-}
-
-/* The dicts the result is made of, ahead of their contents: every node's successor and predecessor dict not made yet
-   (presized to its out- and in-edges, live or not) and the node-ordered top-level dicts (node attributes, succ,
-   pred) holding them -- the rows and predecessor dicts are then filled in place.  Idle work while the replay runs
-   (otherwise the last step after it), and made before the builder's collections of the young generations, which then
-   take these 150 K dicts out of the final one's way.  0, or -1 with an exception set. */
-static int make_tops(PyObject* names, int64_t n, PyObject** rows, PyObject** pin, const int64_t* outdeg,
-                     const int64_t* indeg, PyObject** node, PyObject** succ, PyObject** pred) {
-    PyObject* nd = PyDict_New();
-    PyObject* sd = PyDict_New();
-    PyObject* pd = PyDict_New();
-    if (!nd || !sd || !pd) goto fail;
-    for (Py_ssize_t i = 0; i < (Py_ssize_t)n; ++i) {
-        if (!rows[i] && !(rows[i] = _PyDict_NewPresized(outdeg[i]))) goto fail;
-        if (!pin[i] && !(pin[i] = _PyDict_NewPresized(indeg[i]))) goto fail;
-        PyObject* name = PyList_GET_ITEM(names, i);
-        PyObject* x = PyDict_New();
-        const int bad = !x || PyDict_SetItem(nd, name, x) || PyDict_SetItem(sd, name, rows[i]) ||
-                        PyDict_SetItem(pd, name, pin[i]);
-        Py_XDECREF(x);
-        if (bad) goto fail;
-    }
-    *node = nd;
-    *succ = sd;
-    *pred = pd;
-    return 0;
-fail:
-    Py_XDECREF(nd);
-    Py_XDECREF(sd);
-    Py_XDECREF(pd);
-    return -1;
-}
-
-/* build_overlap_stream(names, counts, a, b, score, end, keep, shared, replay_fn, off, heads, weights)
- *     -> (node, succ, pred, removed, n_removed)
- * remove_cycles_from_graph on a graph that is still columns, with the replay and the dicts overlapped: the replay
- * (replay_fn = the address of libovl's ovl_remove_cycles_stream) runs on a second thread over the CSR (off,
- * heads, weights: OverlapEdges.csr()), and this thread builds each node's successor dict as soon as the replay
- * publishes that node's out-edges as final (they can no longer be removed), with the edges' attribute dicts, and
- * each node's predecessor dict as soon as every tail of its in-edges is final: its in-edges in global insertion
- * order (pairs with b = its read in list order, then the copies of a: overlapGraphs.py:43-60); then the
- * node-ordered top-level dicts.  The result is build_overlap's for the alive mask of the replay; removed holds
- * the replay's removed CSR indices (int64) in removal order. */
-/* The collector.  The builder runs with the collector off (millions of new objects), so the first allocation after it
-   is back on collects the young generation: every row and predecessor dict built, traversing their millions of
-   entries (~0.12 s at the target point on the box, the caller's time).  The builder instead collects the young
-   generations itself (gc.collect(1): generations 0 and 1, so the next automatic collection stays a generation-0
-   one) in idle time while the replay still runs, when these shares of the edges are decided, leaving only the
-   dicts built after the last one for that first collection.  At most kGcMid times: each adds one to generation 2's
-   count, whose threshold (10) arms a full collection. */
-static const int kGcMid = 3;
-static const double kGcAt[3] = {0.30, 0.50, 0.65};
-
-/* the streamed builder's sweeps of its open rows, at most one per this many ms (target point, this container's CPU,
-   three runs each: 0 -> 1 ms, build_overlap_stream 1.69-1.79 -> 1.49-1.60 s) */
-static const double kSweepMs = 1.0;
-
 /* OVL_TRACE_STREAM=1 (diagnostics): one stderr line per build_overlap_stream with the millisecond offsets of its
    phases (s setup done, r replay finished as seen here, with the share of the nodes whose rows were built by
    then, b dicts built, t top-level dicts), the replay thread's own time and the CPUs both threads ran on */
@@ -1036,6 +789,588 @@ static void* replay_main(void* arg) {
     return NULL;
 }
 
+/* build_overlap_stream(names, counts, a, b, score, end, keep, shared, replay_fn, off, heads, weights)
+ *     -> (node, succ, pred, removed, n_removed)
+ * remove_cycles_from_graph on a graph that is still columns, with the replay and the dicts overlapped: the replay
+ * (replay_fn = the address of libovl's ovl_remove_cycles_stream) runs on a second thread over the CSR (off,
+ * heads, weights: OverlapEdges.csr()), and this thread builds each node's successor dict as soon as the replay
+ * publishes that node's out-edges as final (they can no longer be removed), with the edges' attribute dicts, and
+ * each node's predecessor dict as soon as every tail of its in-edges is final: its in-edges in global insertion
+ * order (pairs with b = its read in list order, then the copies of a: overlapGraphs.py:43-60); then the
+ * node-ordered top-level dicts.  The result is build_overlap's for the alive mask of the replay; removed holds
+ * the replay's removed CSR indices (int64) in removal order. */
+/* Everything one build_overlap_stream call owns.  The phases below fill it in, in the order the entry function
+   lists them, each returning 0, or -1 with an exception set; stream_free releases it on every exit. */
+typedef struct {
+    PyObject* names;          /* (borrowed) */
+    PairCols Q;
+    Py_buffer off, heads, w;  /* the caller's CSR */
+    int64_t N, E;             /* its nodes and edges: the layout's too, once stream_layout has checked them */
+    Layout L;
+    Attrs A;
+    PyObject* gc_collect;
+    /* the replay and the component helper: job and scc are theirs to read and write while they run */
+    ReplayJob job;
+    SccJob scc;
+    pthread_t th, scc_th;
+    int started, scc_started;
+    int scc_on;  /* OVL_STREAM_SCC (tests, A/B): 0 rows only as the replay publishes them (no component helper);
+                    2 the replay waits for the helper's first pass (every node alone in the whole graph's
+                    components goes first) */
+    /* in-edges in insertion order: each node's read; the kept pairs grouped by b (list order within a group); a
+       node's in-edges, live or not (its predecessor dict's presize), and out-edges (its row's) */
+    int64_t *rread, *bgoff, *blist, *pending, *outdeg;
+    PyObject **rows, **pin;  /* per node: its successor and predecessor dict (references; NULL: not made yet) */
+    PyObject** dptr;         /* per edge: its attribute dict once inserted, for the head's predecessor cursor */
+    PyObject** spec;         /* per edge: its attribute dict made ahead of its row (spec_advance), or NULL */
+    int own_refs;            /* dptr's entries are references (only when some (a, b) pair is listed twice) */
+    uint8_t* dec;            /* per edge: its fate is known (its tail's row has passed it) */
+    uint8_t* pubd;           /* per node: published (on no cycle) */
+    int64_t *pg, *pt;        /* predecessor cursor: pair group (-1: complete) and tail copy */
+    int64_t* rg;             /* row cursor: pair group (-1: complete) */
+    int32_t* rc;             /*             copy of b */
+    int64_t* openl;          /* the nodes whose rows are open */
+    int64_t spec_u, reap_e;  /* spec_advance's next node, spec_reap's next edge */
+    PyObject *node, *succ, *pred;
+    /* counts, for the final check and the trace line: complete predecessor dicts and rows, decided edges, live
+       edges inserted, attribute dicts made ahead and of those inserted; nodes the replay published, nodes the helper
+       published first, sweeps, collections */
+    int64_t n_pred, n_rows, n_dec, n_ins, n_spec, n_spec_used, k_done, n_from_scc, n_sweeps;
+    int n_gc;
+    int trace;  /* OVL_TRACE_STREAM */
+    double t0, t_setup, t_replay, t_built, t_tops, t_gc;
+    int64_t k_at_replay, dec_at_replay, ins_at_replay;
+} StreamBuild;
+
+/* A node's predecessor dict, built as a prefix of its in-edges in insertion order (kept pairs with b == its read in
+   list order, then the copies of a): the cursor (pg, pt: pair group and tail copy) advances while the next in-edge's
+   fate is known (its tail's successor row has passed it: dec), inserting the live ones. */
+static int pred_advance(StreamBuild* S, int64_t v) {
+    int64_t g = S->pg[v];
+    if (g < 0) return 0;
+    const Py_ssize_t rv = (Py_ssize_t)S->rread[v];
+    const int64_t gend = S->bgoff[rv + 1];
+    const int64_t cv = v - S->L.first[rv];
+    int64_t t = S->pt[v];
+    while (g < gend) {
+        const int64_t q = S->blist[g];
+        const int64_t tend = S->L.first[S->Q.a[q] + 1];
+        for (; t < tend; ++t) {
+            const int64_t e = S->L.off[t] + S->L.pstart[q] + cv;
+            if (!S->dec[e]) {
+                S->pg[v] = g;
+                S->pt[v] = t;
+                return 0;
+            }
+            PyObject* d = S->dptr[e];
+            if (d) {
+                if (!S->pin[v] && !(S->pin[v] = _PyDict_NewPresized(S->pending[v]))) return -1;
+                if (PyDict_SetItem(S->pin[v], PyList_GET_ITEM(S->names, t), d)) return -1;
+            }
+        }
+        if (++g < gend) t = S->L.first[S->Q.a[S->blist[g]]];
+    }
+    if (!S->pin[v] && !(S->pin[v] = PyDict_New())) return -1;
+    S->pg[v] = -1;
+    ++S->n_pred;
+    return 0;
+}
+
+/* A node's successor dict, built the same way as a prefix of its out-edges in row order (kept pairs with a == its
+   read in list order, then the copies of b): an out-edge's fate is known once it is removed (alive 0: removals are
+   final), once its head is on no cycle (published by the replay or the component helper: no cycle can hold the
+   edge, so it is never removed), or once the tail itself is published (all its out-edges final).  Each edge passed
+   is marked decided and lets its head's predecessor dict advance.  `all`: u is published (every edge decided).
+   1 if the row moved, 0 if not, -1 on error. */
+static int row_advance(StreamBuild* S, int64_t u, int all) {
+    int64_t g = S->rg[u];
+    if (g < 0) return 0;
+    const Layout* L = &S->L;
+    const Py_ssize_t r = (Py_ssize_t)S->rread[u];
+    const int64_t gend = L->goff[r + 1];
+    int32_t cb = S->rc[u];
+    int moved = 0;
+    while (g < gend) {
+        const int64_t p = L->plist[g];
+        const int64_t e0 = L->off[u] + L->pstart[p];
+        const int64_t vb = L->first[S->Q.b[p]];
+        const int32_t nb = S->Q.counts[S->Q.b[p]];
+        for (; cb < nb; ++cb) {
+            const int64_t e = e0 + cb;
+            const int live = __atomic_load_n(&S->job.alive[e], __ATOMIC_ACQUIRE);
+            if (live && !all && !S->pubd[vb + cb]) {
+                S->rg[u] = g;
+                S->rc[u] = cb;
+                return moved;
+            }
+            if (live) {
+                if (!S->rows[u] && !(S->rows[u] = _PyDict_NewPresized(S->outdeg[u]))) return -1;
+                PyObject* d = S->spec[e];
+                if (d) {
+                    S->spec[e] = NULL;
+                    ++S->n_spec_used;
+                } else
+                    d = attrs_edge(&S->A, S->Q.sc[p], S->Q.en[p]);
+                const int bad = !d || PyDict_SetItem(S->rows[u], PyList_GET_ITEM(S->names, vb + cb), d);
+                if (bad) {
+                    Py_XDECREF(d);
+                    return -1;
+                }
+                /* dptr[e] is read by the head's predecessor cursor, which may still be short of e.  The row holds
+                   the dict, so dptr borrows it -- unless some (a, b) pair is listed twice (not a list
+                   overlapGraphs.py:43-52 makes, but OverlapEdges accepts it): the second replaces the row's entry
+                   and would free the first dict, so then dptr keeps a reference, released at the exit */
+                if (!S->own_refs) Py_DECREF(d);
+                S->dptr[e] = d;
+                ++S->n_ins;
+            }
+            S->dec[e] = 1;
+            ++S->n_dec;
+            moved = 1;
+            if (pred_advance(S, vb + cb)) return -1;
+        }
+        ++g;
+        cb = 0;
+    }
+    if (!S->rows[u] && !(S->rows[u] = PyDict_New())) return -1;
+    S->rg[u] = -1;
+    ++S->n_rows;
+    return 1;
+}
+
+/* Idle work while the replay runs: the attribute dicts of the still-undecided live out-edges of the nodes from spec_u on,
+   made ahead of their rows (row_advance takes them), up to `budget` of them.  Making an edge's dict is about half of
+   what inserting it costs, and the edges whose fate the replay decides last -- the graph's last cycles -- are
+   otherwise all built after it has ended; an edge removed after its dict was made only costs that dict (released at
+   the end).  Each node once, in node order.  Returns the dicts made (0: every node passed), -1 on error. */
+static int64_t spec_advance(StreamBuild* S, int64_t budget) {
+    const Layout* L = &S->L;
+    int64_t made = 0;
+    while (S->spec_u < S->N && made < budget) {
+        const int64_t u = S->spec_u++;
+        int64_t g = S->rg[u];
+        if (g < 0 || S->pubd[u]) continue;  /* (row complete, or published: built next) */
+        const Py_ssize_t r = (Py_ssize_t)S->rread[u];
+        const int64_t gend = L->goff[r + 1];
+        int32_t cb = S->rc[u];
+        for (; g < gend; ++g, cb = 0) {
+            const int64_t p = L->plist[g];
+            const int64_t e0 = L->off[u] + L->pstart[p];
+            const int32_t nb = S->Q.counts[S->Q.b[p]];
+            for (; cb < nb; ++cb) {
+                const int64_t e = e0 + cb;
+                if (S->spec[e] || !__atomic_load_n(&S->job.alive[e], __ATOMIC_ACQUIRE)) continue;
+                PyObject* d = attrs_edge(&S->A, S->Q.sc[p], S->Q.en[p]);
+                if (!d) return -1;
+                S->spec[e] = d;
+                ++made;
+            }
+        }
+    }
+    S->n_spec += made;
+    return made;
+}
+
+/* Idle work once every node has had its dicts made ahead: release the made-ahead dicts of edges the replay has
+   removed since, `budget` entries of the edge array per call, cycling over it, so that few are left to release after
+   the replay.  Returns the dicts released. */
+static int64_t spec_reap(StreamBuild* S, int64_t budget) {
+    int64_t freed = 0;
+    for (int64_t k = 0; k < budget && S->E > 0; ++k) {
+        const int64_t e = S->reap_e++;
+        if (S->reap_e >= S->E) S->reap_e = 0;
+        PyObject* d = S->spec[e];
+        if (d && !__atomic_load_n(&S->job.alive[e], __ATOMIC_ACQUIRE)) {
+            S->spec[e] = NULL;
+            Py_DECREF(d);
+            ++freed;
+        }
+    }
+    return freed;
+}
+
+/* The dicts the result is made of, ahead of their contents: every node's successor and predecessor dict not made yet
+   (presized to its out- and in-edges, live or not) and the node-ordered top-level dicts (node attributes, succ,
+   pred) holding them -- the rows and predecessor dicts are then filled in place.  Idle work while the replay runs
+   (otherwise the last step after it), and made before the builder's collections of the young generations, which then
+   take these 150 K dicts out of the final one's way.  0, or -1 with an exception set. */
+static int make_tops(StreamBuild* S) {
+    PyObject* nd = PyDict_New();
+    PyObject* sd = PyDict_New();
+    PyObject* pd = PyDict_New();
+    if (!nd || !sd || !pd) goto fail;
+    for (Py_ssize_t i = 0; i < (Py_ssize_t)S->N; ++i) {
+        if (!S->rows[i] && !(S->rows[i] = _PyDict_NewPresized(S->outdeg[i]))) goto fail;
+        if (!S->pin[i] && !(S->pin[i] = _PyDict_NewPresized(S->pending[i]))) goto fail;
+        PyObject* name = PyList_GET_ITEM(S->names, i);
+        PyObject* x = PyDict_New();
+        const int bad = !x || PyDict_SetItem(nd, name, x) || PyDict_SetItem(sd, name, S->rows[i]) ||
+                        PyDict_SetItem(pd, name, S->pin[i]);
+        Py_XDECREF(x);
+        if (bad) goto fail;
+    }
+    S->node = nd;
+    S->succ = sd;
+    S->pred = pd;
+    return 0;
+fail:
+    Py_XDECREF(nd);
+    Py_XDECREF(sd);
+    Py_XDECREF(pd);
+    return -1;
+}
+
+/* The collector.  The builder runs with the collector off (millions of new objects), so the first allocation after it
+   is back on collects the young generation: every row and predecessor dict built, traversing their millions of
+   entries (~0.12 s at the target point on the box, the caller's time).  The builder instead collects the young
+   generations itself (gc.collect(1): generations 0 and 1, so the next automatic collection stays a generation-0
+   one) in idle time while the replay still runs, when these shares of the edges are decided, leaving only the
+   dicts built after the last one for that first collection.  At most kGcMid times: each adds one to generation 2's
+   count, whose threshold (10) arms a full collection. */
+static const int kGcMid = 3;
+static const double kGcAt[3] = {0.30, 0.50, 0.65};
+
+/* the streamed builder's sweeps of its open rows, at most one per this many ms (target point, this container's CPU,
+   three runs each: 0 -> 1 ms, build_overlap_stream 1.69-1.79 -> 1.49-1.60 s) */
+static const double kSweepMs = 1.0;
+
+static void stream_join(StreamBuild* S) {
+    if (S->started) {  /* (it owns no Python objects; the gate: if it still waits for the helper's first pass) */
+        __atomic_store_n(&S->job.gate, 1, __ATOMIC_RELEASE);
+        pthread_join(S->th, NULL);
+        S->started = 0;
+    }
+    if (S->scc_started) {  /* (it stops once the replay has finished) */
+        pthread_join(S->scc_th, NULL);
+        S->scc_started = 0;
+    }
+}
+
+/* The one exit of a streamed build.  Both threads are joined before any buffer they read is released -- on every
+   exit, those taken after a thread has started included: an error while the replay runs lets it finish first. */
+static void stream_free(StreamBuild* S) {
+    if (S->started || S->scc_started) {
+        Py_BEGIN_ALLOW_THREADS
+        stream_join(S);
+        Py_END_ALLOW_THREADS
+    }
+    PyMem_RawFree(S->scc.nodes);
+    PyMem_RawFree(S->job.removed);
+    PyMem_RawFree(S->job.alive);
+    PyMem_RawFree(S->job.final_nodes);
+    if (S->rows)
+        for (int64_t i = 0; i < S->N; ++i) Py_XDECREF(S->rows[i]);
+    if (S->pin)
+        for (int64_t i = 0; i < S->N; ++i) Py_XDECREF(S->pin[i]);
+    const double tc0 = S->trace ? now_ms() : 0.0;
+    if (S->dptr && S->own_refs)
+        for (int64_t e = 0; e < S->E; ++e) Py_XDECREF(S->dptr[e]);
+    const double tc1 = S->trace ? now_ms() : 0.0;
+    if (S->spec)  /* (the dicts made ahead for edges the replay then removed) */
+        for (int64_t e = 0; e < S->E; ++e) Py_XDECREF(S->spec[e]);
+    if (S->trace)
+        fprintf(stderr, "ovl_stream exit: references %.1f ms, dicts made ahead and unused %.1f ms\n", tc1 - tc0,
+                now_ms() - tc1);
+    void* const bufs[] = {S->rows, S->pin, S->dptr, S->spec, S->rread, S->bgoff, S->blist, S->pending, S->pg,
+                          S->pt,   S->rg,  S->rc,   S->outdeg, S->pubd, S->dec,  S->openl};
+    for (size_t i = 0; i < sizeof(bufs) / sizeof(bufs[0]); ++i) PyMem_Free(bufs[i]);
+    Py_XDECREF(S->gc_collect);
+    Py_XDECREF(S->node);
+    Py_XDECREF(S->succ);
+    Py_XDECREF(S->pred);
+    attrs_free(&S->A);
+    layout_free(&S->L);
+    pairs_release(&S->Q);
+    if (S->off.obj) PyBuffer_Release(&S->off);
+    if (S->heads.obj) PyBuffer_Release(&S->heads);
+    if (S->w.obj) PyBuffer_Release(&S->w);
+}
+
+/* Phase 1: the replay thread on the caller's CSR.  It needs only the CSR, so it starts first and the columns are
+   laid out while it runs (the CSR is checked against them there; on a mismatch the replay of the caller's CSR
+   still ends, is joined and the call fails). */
+static int stream_start_replay(StreamBuild* S, unsigned long long fn_addr) {
+    if (S->off.len < 8 || S->heads.len / 4 != S->w.len / 8 || S->off.len / 8 - 1 >= ((Py_ssize_t)1 << 31)) {
+        PyErr_SetString(PyExc_ValueError, "names / CSR do not match the columns' graph");
+        return -1;
+    }
+    ReplayJob* j = &S->job;
+    S->E = (int64_t)(S->heads.len / 4);
+    S->N = (int64_t)(S->off.len / 8 - 1);
+    j->fn = (replay_stream_fn)(uintptr_t)fn_addr;
+    j->off = (const int64_t*)S->off.buf;
+    j->heads = (const int32_t*)S->heads.buf;
+    j->w = (const int64_t*)S->w.buf;
+    j->n = (int32_t)S->N;
+    j->removed = RAW_NEW(int64_t, S->E);
+    j->alive = RAW_NEW(uint8_t, S->E);
+    j->final_nodes = RAW_NEW(int32_t, S->N);
+    if (!j->removed || !j->alive || !j->final_nodes) {
+        PyErr_NoMemory();
+        return -1;
+    }
+    /* all ones before either thread starts (the replay sets it too, but on its own thread, where the component
+       helper could read it first) */
+    memset(j->alive, 1, (size_t)S->E);
+    j->cpu_main = sched_getcpu();
+    j->gate = S->scc_on != 2;
+    if (pthread_create(&S->th, NULL, replay_main, j) != 0) {
+        PyErr_SetString(PyExc_RuntimeError, "cannot start the replay thread");
+        return -1;
+    }
+    S->started = 1;
+    if (S->trace) S->t_setup = now_ms() - S->t0;
+    return 0;
+}
+
+/* Phase 2: the columns' layout, checked against the names and the CSR; the in-edge groups; the arrays of dicts;
+   the attribute maker and the collector's entry point. */
+static int stream_layout(StreamBuild* S, PyObject* shared) {
+    const PairCols* Q = &S->Q;
+    Layout* L = &S->L;
+    if (layout(L, Q)) return -1;
+    if (PyList_GET_SIZE(S->names) != L->N || S->N != L->N || S->E != L->E || S->w.len / 8 != L->E ||
+        L->N >= ((Py_ssize_t)1 << 31)) {
+        PyErr_SetString(PyExc_ValueError, "names / CSR do not match the columns' graph");
+        return -1;
+    }
+    S->rows = NEW0(PyObject*, S->N);
+    S->pin = NEW0(PyObject*, S->N);
+    S->dptr = NEW0(PyObject*, S->E);
+    S->spec = NEW0(PyObject*, S->E);
+    S->rread = NEW(int64_t, S->N);
+    S->bgoff = NEW0(int64_t, L->R + 1);
+    S->blist = NEW(int64_t, L->P);
+    S->pending = NEW0(int64_t, S->N);
+    int64_t* fill = NEW(int64_t, L->R);
+    if (!S->rows || !S->pin || !S->dptr || !S->spec || !S->rread || !S->bgoff || !S->blist || !S->pending || !fill) {
+        PyMem_Free(fill);
+        PyErr_NoMemory();
+        return -1;
+    }
+    int64_t *bgoff = S->bgoff, *blist = S->blist;
+    for (Py_ssize_t r = 0; r < L->R; ++r)
+        for (int64_t u = L->first[r]; u < L->first[r + 1]; ++u) S->rread[u] = r;
+    for (Py_ssize_t p = 0; p < L->P; ++p)
+        if (!Q->keep || Q->keep[p]) ++bgoff[Q->b[p] + 1];
+    for (Py_ssize_t r = 0; r < L->R; ++r) bgoff[r + 1] += bgoff[r];
+    memcpy(fill, bgoff, sizeof(int64_t) * (size_t)L->R);
+    for (Py_ssize_t p = 0; p < L->P; ++p)
+        if (!Q->keep || Q->keep[p]) blist[fill[Q->b[p]]++] = p;
+    PyMem_Free(fill);
+    /* (every copy of one read has the same in-edges) */
+    for (Py_ssize_t r = 0; r < L->R; ++r) {
+        int64_t k = 0;
+        for (int64_t g = bgoff[r]; g < bgoff[r + 1]; ++g) k += L->first[Q->a[blist[g]] + 1] - L->first[Q->a[blist[g]]];
+        for (int64_t v = L->first[r]; v < L->first[r + 1]; ++v) S->pending[v] = k;
+    }
+    if (attrs_init(&S->A, shared)) return -1;
+    PyObject* gcm = PyImport_ImportModule("gc");
+    if (!gcm) return -1;
+    S->gc_collect = PyObject_GetAttrString(gcm, "collect");
+    Py_DECREF(gcm);
+    if (!S->gc_collect) return -1;
+    if (S->trace) S->t_setup = now_ms() - S->t0;  /* (s: the builder's setup done, the replay running since the start) */
+    return 0;
+}
+
+/* Phase 3: the component helper (scc_main), unless OVL_STREAM_SCC=0 */
+static int stream_start_helper(StreamBuild* S) {
+    if (!S->scc_on) return 0;
+    SccJob* c = &S->scc;
+    c->off = S->job.off;
+    c->heads = S->job.heads;
+    c->alive = S->job.alive;
+    c->n = (int32_t)S->N;
+    c->stop = &S->job.finished;
+    c->gate = &S->job.gate;
+    c->nodes = RAW_NEW(int32_t, S->N);
+    if (!c->nodes) { PyErr_NoMemory(); return -1; }
+    if (pthread_create(&S->scc_th, NULL, scc_main, c) != 0) {
+        PyErr_SetString(PyExc_RuntimeError, "cannot start the component thread");
+        return -1;
+    }
+    S->scc_started = 1;
+    return 0;
+}
+
+/* Phase 4: every node's row and predecessor cursor at its start, and every row open */
+static int stream_open_rows(StreamBuild* S) {
+    const PairCols* Q = &S->Q;
+    const Layout* L = &S->L;
+    const int64_t N = S->N;
+    S->pg = NEW(int64_t, N);
+    S->pt = NEW(int64_t, N);
+    S->rg = NEW(int64_t, N);
+    S->rc = NEW0(int32_t, N);
+    S->outdeg = NEW0(int64_t, N);
+    S->pubd = NEW0(uint8_t, N);
+    S->dec = NEW0(uint8_t, S->E);
+    S->openl = NEW(int64_t, N);
+    int32_t* stamp = NEW0(int32_t, L->R);
+    if (!S->pg || !S->pt || !S->rg || !S->rc || !S->outdeg || !S->pubd || !S->dec || !S->openl || !stamp) {
+        PyMem_Free(stamp);
+        PyErr_NoMemory();
+        return -1;
+    }
+    for (int64_t v = 0; v < N; ++v) {
+        const Py_ssize_t rv = (Py_ssize_t)S->rread[v];
+        const int64_t g0 = S->bgoff[rv];
+        S->pg[v] = g0;
+        S->pt[v] = g0 < S->bgoff[rv + 1] ? L->first[Q->a[S->blist[g0]]] : 0;
+        S->rg[v] = L->goff[rv];
+        for (int64_t g = L->goff[rv]; g < L->goff[rv + 1]; ++g) S->outdeg[v] += Q->counts[Q->b[L->plist[g]]];
+        S->openl[v] = v;
+    }
+    /* some read's kept pairs list the same b twice? (then dptr owns its references) */
+    int dup = 0;
+    for (Py_ssize_t r = 0; r < L->R && !dup; ++r)
+        for (int64_t g = L->goff[r]; g < L->goff[r + 1]; ++g) {
+            const int32_t bb = Q->b[L->plist[g]];
+            if (stamp[bb] == (int32_t)r + 1) { dup = 1; break; }
+            stamp[bb] = (int32_t)r + 1;
+        }
+    PyMem_Free(stamp);
+    S->own_refs = dup;
+    return 0;
+}
+
+/* The publish loop with nothing to build: make attribute dicts ahead; once every node has had its turn, release
+   those of removed edges (`reap`) and yield the CPU. */
+static int stream_idle(StreamBuild* S, int reap) {
+    const int64_t m = spec_advance(S, 256);
+    if (m < 0) return -1;
+    if (m == 0) {
+        if (reap) (void)spec_reap(S, 16384);
+        Py_BEGIN_ALLOW_THREADS
+        sched_yield();
+        Py_END_ALLOW_THREADS
+    }
+    return 0;
+}
+
+/* Phase 5: successors of each node as its out-edges become final (row order: kept pairs with a == its read in
+   list order, then the copies of b) -- published by the replay (settled or explored nodes) or by the component
+   helper, whichever comes first; predecessors of each node once every tail of its in-edges is.  Ends when the
+   replay has finished and every node it published is built. */
+static int stream_publish(StreamBuild* S) {
+    ReplayJob* job = &S->job;
+    SccJob* scc = &S->scc;
+    const int64_t N = S->N, E = S->E;
+    const int trace = S->trace;
+    uint8_t* pubd = S->pubd;
+    int64_t *openl = S->openl, *rg = S->rg;
+    int64_t k_done = 0, k_scc = 0, n_from_scc = 0, n_sweeps = 0;
+    int64_t n_open = N;
+    int n_gc = 0;           /* collections of the young generations run so far (kGcMid) */
+    double t_sweep = -1e9;  /* the last sweep's start (ms) */
+    S->t_replay = S->t_tops = -1.0;
+    for (int64_t v = 0; v < N; ++v)
+        if (pred_advance(S, v)) return -1;  /* (completes the nodes without in-edges) */
+    for (;;) {
+        if (trace && S->t_replay < 0.0 && __atomic_load_n(&job->finished, __ATOMIC_ACQUIRE)) {
+            S->t_replay = now_ms() - S->t0;
+            S->k_at_replay = S->n_rows;
+            S->dec_at_replay = S->n_dec;
+            S->ins_at_replay = S->n_ins;
+        }
+        int64_t u = -1;
+        if (k_done < __atomic_load_n(&job->n_final, __ATOMIC_ACQUIRE)) {
+            u = job->final_nodes[k_done++];
+        } else if (S->scc_started && k_scc < __atomic_load_n(&scc->n_pub, __ATOMIC_ACQUIRE)) {
+            u = scc->nodes[k_scc++];
+            if (!pubd[u]) ++n_from_scc;
+        }
+        if (u >= 0) {
+            if (pubd[u]) continue;  /* (published by both) */
+            pubd[u] = 1;
+            if (row_advance(S, u, 1) < 0) return -1;
+            continue;
+        }
+        if (__atomic_load_n(&job->finished, __ATOMIC_ACQUIRE)) {
+            if (__atomic_load_n(&job->n_final, __ATOMIC_ACQUIRE) > k_done) continue;
+            break;
+        }
+        /* nothing newly published: advance the open rows as far as their heads allow -- at most once per
+           kSweepMs (a sweep calls row_advance on every open row, hundreds of millions of calls over a run when
+           repeated back to back); in between, and after a sweep that moved nothing, make attribute dicts ahead */
+        if (now_ms() - t_sweep < kSweepMs) {
+            if (!S->node) {  /* first: every row and predecessor dict and the top-level dicts, once */
+                if (make_tops(S)) return -1;
+                if (trace) S->t_tops = now_ms() - S->t0;
+                continue;
+            }
+            if (n_gc < kGcMid && S->n_dec >= (int64_t)(kGcAt[n_gc] * (double)E)) {
+                /* the collector's pass over the dicts built so far, now, beside the replay (see kGcMid) */
+                const double tg = now_ms();
+                PyObject* res = PyObject_CallFunction(S->gc_collect, "i", 1);
+                if (!res) return -1;
+                Py_DECREF(res);
+                S->t_gc += now_ms() - tg;
+                ++n_gc;
+                continue;
+            }
+            if (stream_idle(S, 1)) return -1;
+            continue;
+        }
+        t_sweep = now_ms();
+        int moved = 0;
+        int64_t keep_n = 0;
+        for (int64_t i = 0; i < n_open; ++i) {
+            const int64_t x = openl[i];
+            if (rg[x] < 0) continue;
+            const int m = row_advance(S, x, 0);
+            if (m < 0) return -1;
+            moved |= m;
+            if (rg[x] >= 0) openl[keep_n++] = x;
+            if ((i & 255) == 255 && k_done < __atomic_load_n(&job->n_final, __ATOMIC_ACQUIRE)) {
+                /* (newly published nodes first: keep the rest of the list for the next sweep) */
+                for (int64_t j = i + 1; j < n_open; ++j) openl[keep_n++] = openl[j];
+                break;
+            }
+        }
+        n_open = keep_n;
+        ++n_sweeps;
+        if (!moved && stream_idle(S, 0)) return -1;  /* (nothing to insert yet) */
+    }
+    S->k_done = k_done;
+    S->n_from_scc = n_from_scc;
+    S->n_sweeps = n_sweeps;
+    S->n_gc = n_gc;
+    return 0;
+}
+
+/* Phase 6: both threads joined, the replay's verdict, the top-level dicts if idle time did not make them, the
+   trace line and the result tuple (NULL with an exception set on failure) */
+static PyObject* stream_finish(StreamBuild* S) {
+    const ReplayJob* job = &S->job;
+    const int64_t N = S->N, E = S->E;
+    stream_join(S);
+    if (S->trace) S->t_built = now_ms() - S->t0;
+    if (job->rc != 0 || S->k_done != N || S->n_rows != N || S->n_pred != N) {
+        PyErr_Format(PyExc_RuntimeError, "ovl_remove_cycles_stream failed (rc %d, %lld of %lld nodes final, "
+                     "%lld predecessor dicts)", job->rc, (long long)S->k_done, (long long)N, (long long)S->n_pred);
+        return NULL;
+    }
+    if (!S->node && make_tops(S)) return NULL;
+    PyObject* rem = PyBytes_FromStringAndSize((const char*)job->removed, (Py_ssize_t)(8 * job->n_removed));
+    if (!rem) return NULL;
+    PyObject* out = Py_BuildValue("(OOONL)", S->node, S->succ, S->pred, rem, (long long)job->n_removed);
+    if (S->trace) {
+        const double dec_pct = E ? 100.0 * (double)S->dec_at_replay / (double)E : 0.0;
+        fprintf(stderr,
+                "ovl_stream: s=%.1f r=%.1f (%.0f%% rows, %.0f%% edges, %lld inserted) b=%.1f t=%.1f sweeps=%lld "
+                "scc=%d passes=%d first=%lld replay=%.1f cpus main %d/%d replay %d/%d spec %lld used %lld "
+                "gc %d in %.1f ms tops at %.1f dec %.0f%%\n",
+                S->t_setup, S->t_replay, N ? 100.0 * (double)S->k_at_replay / (double)N : 100.0,
+                E ? dec_pct : 100.0, (long long)S->ins_at_replay, S->t_built, now_ms() - S->t0,
+                (long long)S->n_sweeps, S->scc_on, S->scc.passes, (long long)S->n_from_scc, job->ms, job->cpu_main,
+                sched_getcpu(), job->cpu_start, job->cpu_end, (long long)S->n_spec, (long long)S->n_spec_used,
+                S->n_gc, S->t_gc, S->t_tops, dec_pct);
+    }
+    return out;
+}
+
 static PyObject* build_overlap_stream_impl(PyObject* self, PyObject* args) {
     (void)self;
     PyObject *names, *oc, *oa, *ob, *os, *oe, *ok, *shared, *ooff, *oh, *ow;
@@ -1043,389 +1378,25 @@ static PyObject* build_overlap_stream_impl(PyObject* self, PyObject* args) {
     if (!PyArg_ParseTuple(args, "O!OOOOOOOKOOO", &PyList_Type, &names, &oc, &oa, &ob, &os, &oe, &ok, &shared,
                           &fn_addr, &ooff, &oh, &ow))
         return NULL;
-    Cols C;
-    memset(&C, 0, sizeof(C));
-    Py_buffer bs, be, boff, bh, bw;
-    memset(&bs, 0, sizeof(bs));
-    memset(&be, 0, sizeof(be));
-    memset(&boff, 0, sizeof(boff));
-    memset(&bh, 0, sizeof(bh));
-    memset(&bw, 0, sizeof(bw));
-    Layout L;
-    memset(&L, 0, sizeof(L));
-    ReplayJob job;
-    memset(&job, 0, sizeof(job));
-    pthread_t th, scc_th;
-    int started = 0, scc_started = 0;
-    SccJob scc;
-    memset(&scc, 0, sizeof(scc));
-    /* OVL_STREAM_SCC (tests, A/B): 0 rows only as the replay publishes them (no component helper); 2 the replay
-       waits for the helper's first pass (every node alone in the whole graph's components goes first) */
+    StreamBuild S;
+    memset(&S, 0, sizeof(S));
+    S.names = names;
+    S.own_refs = 1;
     const char* scc_env = getenv("OVL_STREAM_SCC");
-    const int scc_on = scc_env ? atoi(scc_env) : 1;
+    S.scc_on = scc_env ? atoi(scc_env) : 1;
     const char* tr_env = getenv("OVL_TRACE_STREAM");
-    const int trace = tr_env && atoi(tr_env) != 0;
-    const double t0 = trace ? now_ms() : 0.0;
-    double t_setup = 0.0, t_replay = -1.0, t_built = 0.0;
-    int64_t k_at_replay = 0, dec_at_replay = 0, ins_at_replay = 0;
-    PyObject *node = NULL, *succ = NULL, *pred = NULL, *kw = NULL, *ke = NULL, *tmpl = NULL, *out = NULL;
-    PyObject **rows = NULL, **dptr = NULL, **pin = NULL, **spec = NULL;
-    PyObject* gc_collect = NULL;
-    int own_refs = 1;  /* dptr's entries are references (until the columns are known free of repeated pairs) */
-    PyObject** ints = (PyObject**)PyMem_Calloc((size_t)(kIntHi - kIntLo), sizeof(PyObject*));
-    int64_t* rread = NULL;
-    int64_t *bgoff = NULL, *blist = NULL, *pending = NULL, *ready = NULL, *pg = NULL, *pt = NULL, *rg = NULL;
-    int64_t *outdeg = NULL, *openl = NULL;
-    int32_t* rc = NULL;
-    uint8_t *pubd = NULL, *dec = NULL;
-    if (!ints) { PyErr_NoMemory(); goto done; }
-    if (cols_take(&C, oc, oa, ob, ok) || take(os, &bs, 4, "score") || take(oe, &be, 4, "end") ||
-        take(ooff, &boff, 8, "off") || take(oh, &bh, 4, "heads") || take(ow, &bw, 8, "weights"))
-        goto done;
-    if (bs.len != C.a.len || be.len != C.a.len) {
-        PyErr_SetString(PyExc_ValueError, "score and end must have one entry per pair");
-        goto done;
-    }
-    /* the replay needs only the CSR: start it first, and lay out the columns while it runs (the CSR is checked
-       against them below; on a mismatch the replay of the caller's CSR still ends, is joined and the call fails) */
-    if (boff.len < 8 || bh.len / 4 != bw.len / 8 || boff.len / 8 - 1 >= ((Py_ssize_t)1 << 31)) {
-        PyErr_SetString(PyExc_ValueError, "names / CSR do not match the columns' graph");
-        goto done;
-    }
-    {
-        const int64_t E = (int64_t)(bh.len / 4), N = (int64_t)(boff.len / 8 - 1);
-        job.fn = (replay_stream_fn)(uintptr_t)fn_addr;
-        job.off = (const int64_t*)boff.buf;
-        job.heads = (const int32_t*)bh.buf;
-        job.w = (const int64_t*)bw.buf;
-        job.n = (int32_t)N;
-        job.removed = (int64_t*)PyMem_RawMalloc(sizeof(int64_t) * (size_t)(E ? E : 1));
-        job.alive = (uint8_t*)PyMem_RawMalloc((size_t)(E ? E : 1));
-        job.final_nodes = (int32_t*)PyMem_RawMalloc(sizeof(int32_t) * (size_t)(N ? N : 1));
-        if (!job.removed || !job.alive || !job.final_nodes) {
-            PyErr_NoMemory();
-            goto done;
-        }
-        /* all ones before either thread starts (the replay sets it too, but on its own thread, where the component
-           helper could read it first) */
-        memset(job.alive, 1, (size_t)E);
-        job.cpu_main = sched_getcpu();
-        job.gate = scc_on != 2;
-        if (pthread_create(&th, NULL, replay_main, &job) != 0) {
-            PyErr_SetString(PyExc_RuntimeError, "cannot start the replay thread");
-            goto done;
-        }
-        started = 1;
-        if (trace) t_setup = now_ms() - t0;
-    }
-    {
-        const int32_t* counts = (const int32_t*)C.c.buf;
-        const int32_t* a = (const int32_t*)C.a.buf;
-        const int32_t* b = (const int32_t*)C.b.buf;
-        const int32_t* sc = (const int32_t*)bs.buf;
-        const int32_t* en = (const int32_t*)be.buf;
-        const uint8_t* keep = C.has_k ? (const uint8_t*)C.k.buf : NULL;
-        if (layout(&L, counts, C.c.len / 4, a, b, C.a.len / 4, keep)) goto done;
-        const Py_ssize_t n_nodes = PyList_GET_SIZE(names);
-        if (n_nodes != L.N || boff.len / 8 != L.N + 1 || bh.len / 4 != L.E || bw.len / 8 != L.E ||
-            L.N >= ((Py_ssize_t)1 << 31)) {
-            PyErr_SetString(PyExc_ValueError, "names / CSR do not match the columns' graph");
-            goto done;
-        }
-        const int64_t E = L.E, N = L.N;
-        rows = (PyObject**)PyMem_Calloc((size_t)(N ? N : 1), sizeof(PyObject*));
-        pin = (PyObject**)PyMem_Calloc((size_t)(N ? N : 1), sizeof(PyObject*));
-        dptr = (PyObject**)PyMem_Calloc((size_t)(E ? E : 1), sizeof(PyObject*));
-        spec = (PyObject**)PyMem_Calloc((size_t)(E ? E : 1), sizeof(PyObject*));
-        rread = (int64_t*)PyMem_Malloc(sizeof(int64_t) * (size_t)(N ? N : 1));
-        /* in-edges in insertion order: the kept pairs grouped by b (list order within a group) */
-        bgoff = (int64_t*)PyMem_Calloc((size_t)L.R + 1, sizeof(int64_t));
-        blist = (int64_t*)PyMem_Malloc(sizeof(int64_t) * (size_t)(L.P ? L.P : 1));
-        pending = (int64_t*)PyMem_Calloc((size_t)(N ? N : 1), sizeof(int64_t));
-        if (!rows || !pin || !dptr || !spec || !rread || !bgoff || !blist || !pending) {
-            PyErr_NoMemory();
-            goto done;
-        }
-        for (Py_ssize_t r = 0; r < L.R; ++r)
-            for (int64_t u = L.first[r]; u < L.first[r + 1]; ++u) rread[u] = r;
-        for (Py_ssize_t p = 0; p < L.P; ++p)
-            if (!keep || keep[p]) ++bgoff[b[p] + 1];
-        for (Py_ssize_t r = 0; r < L.R; ++r) bgoff[r + 1] += bgoff[r];
-        {
-            int64_t* fill = (int64_t*)PyMem_Malloc(sizeof(int64_t) * (size_t)(L.R ? L.R : 1));
-            if (!fill) { PyErr_NoMemory(); goto done; }
-            memcpy(fill, bgoff, sizeof(int64_t) * (size_t)L.R);
-            for (Py_ssize_t p = 0; p < L.P; ++p)
-                if (!keep || keep[p]) blist[fill[b[p]]++] = p;
-            PyMem_Free(fill);
-        }
-        /* a node's in-edges, live or not (every copy of one read has the same in-edges) */
-        for (Py_ssize_t r = 0; r < L.R; ++r) {
-            int64_t k = 0;
-            for (int64_t g = bgoff[r]; g < bgoff[r + 1]; ++g) k += L.first[a[blist[g]] + 1] - L.first[a[blist[g]]];
-            for (int64_t v = L.first[r]; v < L.first[r + 1]; ++v) pending[v] = k;
-        }
-        kw = PyUnicode_InternFromString("weight");
-        ke = PyUnicode_InternFromString("end_position");
-        if (!kw || !ke) goto done;
-        if (shared && shared != Py_None && PyDict_Check(shared) && PyDict_GET_SIZE(shared) == 2 &&
-            PyDict_Contains(shared, kw) == 1 && PyDict_Contains(shared, ke) == 1) {
-            tmpl = shared;
-            Py_INCREF(tmpl);
-        } else {
-            tmpl = PyDict_New();
-            if (!tmpl || PyDict_SetItem(tmpl, kw, Py_None) || PyDict_SetItem(tmpl, ke, Py_None)) goto done;
-        }
-        Py_ssize_t iw, ie;
-        attr_slots(tmpl, kw, ke, &iw, &ie);
-        {
-            PyObject* gcm = PyImport_ImportModule("gc");
-            if (!gcm) goto done;
-            gc_collect = PyObject_GetAttrString(gcm, "collect");
-            Py_DECREF(gcm);
-            if (!gc_collect) goto done;
-        }
-        if (trace) t_setup = now_ms() - t0;  /* (s: the builder's setup done, the replay running since the start) */
-        /* successors of each node as its out-edges become final (row order: kept pairs with a == its read in
-           list order, then the copies of b) -- published by the replay (settled or explored nodes) or by the
-           component helper (scc_main), whichever comes first; predecessors of each node once every tail of its
-           in-edges is */
-        if (scc_on) {
-            scc.off = job.off;
-            scc.heads = job.heads;
-            scc.alive = job.alive;
-            scc.n = (int32_t)N;
-            scc.stop = &job.finished;
-            scc.gate = &job.gate;
-            scc.nodes = (int32_t*)PyMem_RawMalloc(sizeof(int32_t) * (size_t)(N ? N : 1));
-            if (!scc.nodes) { PyErr_NoMemory(); goto done; }
-            if (pthread_create(&scc_th, NULL, scc_main, &scc) != 0) {
-                PyErr_SetString(PyExc_RuntimeError, "cannot start the component thread");
-                goto done;
-            }
-            scc_started = 1;
-        }
-        int64_t k_done = 0, k_scc = 0, n_pub = 0, n_from_scc = 0, n_sweeps = 0;
-        pg = (int64_t*)PyMem_Malloc(sizeof(int64_t) * (size_t)(N ? N : 1));
-        pt = (int64_t*)PyMem_Malloc(sizeof(int64_t) * (size_t)(N ? N : 1));
-        rg = (int64_t*)PyMem_Malloc(sizeof(int64_t) * (size_t)(N ? N : 1));
-        rc = (int32_t*)PyMem_Calloc((size_t)(N ? N : 1), sizeof(int32_t));
-        outdeg = (int64_t*)PyMem_Calloc((size_t)(N ? N : 1), sizeof(int64_t));
-        pubd = (uint8_t*)PyMem_Calloc((size_t)(N ? N : 1), 1);
-        dec = (uint8_t*)PyMem_Calloc((size_t)(E ? E : 1), 1);
-        openl = (int64_t*)PyMem_Malloc(sizeof(int64_t) * (size_t)(N ? N : 1));
-        if (!pg || !pt || !rg || !rc || !outdeg || !pubd || !dec || !openl) { PyErr_NoMemory(); goto done; }
-        PredCtx X = {&L, a, blist, bgoff, rread, pending, dec, dptr, names, pin, pg, pt, 0};
-        for (int64_t v = 0; v < N; ++v) {
-            const Py_ssize_t rv = (Py_ssize_t)rread[v];
-            pg[v] = bgoff[rv];
-            pt[v] = bgoff[rv] < bgoff[rv + 1] ? L.first[a[blist[bgoff[rv]]]] : 0;
-            rg[v] = L.goff[rv];
-            for (int64_t g = L.goff[rv]; g < L.goff[rv + 1]; ++g) outdeg[v] += counts[b[L.plist[g]]];
-            openl[v] = v;
-        }
-        int64_t n_open = N;
-        /* some read's kept pairs list the same b twice? (then dptr owns its references, RowCtx.own) */
-        int dup = 0;
-        {
-            int32_t* stamp = (int32_t*)PyMem_Calloc((size_t)(L.R ? L.R : 1), sizeof(int32_t));
-            if (!stamp) { PyErr_NoMemory(); goto done; }
-            for (Py_ssize_t r = 0; r < L.R && !dup; ++r)
-                for (int64_t g = L.goff[r]; g < L.goff[r + 1]; ++g) {
-                    const int32_t bb = b[L.plist[g]];
-                    if (stamp[bb] == (int32_t)r + 1) { dup = 1; break; }
-                    stamp[bb] = (int32_t)r + 1;
-                }
-            PyMem_Free(stamp);
-        }
-        own_refs = dup;
-        RowCtx R = {&X, counts, b, sc, en, job.alive, pubd, outdeg, rows, dptr, dec, rg, rc, ints, tmpl, kw, ke, iw, ie,
-                    spec, dup, 0, 0, 0, 0, 0};
-        int64_t spec_u = 0;     /* spec_advance's next node */
-        int64_t reap_e = 0;     /* spec_reap's next edge */
-        int n_gc = 0;           /* collections of the young generations run so far (kGcMid) */
-        double t_tops = -1.0;
-        double t_gc = 0.0;
-        double t_sweep = -1e9;  /* the last sweep's start (ms) */
-        for (int64_t v = 0; v < N; ++v)
-            if (pred_advance(&X, v)) goto done;  /* (completes the nodes without in-edges) */
-        for (;;) {
-            if (trace && t_replay < 0.0 && __atomic_load_n(&job.finished, __ATOMIC_ACQUIRE)) {
-                t_replay = now_ms() - t0;
-                k_at_replay = R.n_rows;
-                dec_at_replay = R.n_dec;
-                ins_at_replay = R.n_ins;
-            }
-            int64_t u = -1;
-            if (k_done < __atomic_load_n(&job.n_final, __ATOMIC_ACQUIRE)) {
-                u = job.final_nodes[k_done++];
-            } else if (scc_started && k_scc < __atomic_load_n(&scc.n_pub, __ATOMIC_ACQUIRE)) {
-                u = scc.nodes[k_scc++];
-                if (!pubd[u]) ++n_from_scc;
-            }
-            if (u >= 0) {
-                if (pubd[u]) continue;  /* (published by both) */
-                pubd[u] = 1;
-                ++n_pub;
-                if (row_advance(&R, u, 1) < 0) goto done;
-                continue;
-            }
-            if (__atomic_load_n(&job.finished, __ATOMIC_ACQUIRE)) {
-                if (__atomic_load_n(&job.n_final, __ATOMIC_ACQUIRE) > k_done) continue;
-                break;
-            }
-            /* nothing newly published: advance the openl rows as far as their heads allow -- at most once per
-               kSweepMs (a sweep calls row_advance on every open row, hundreds of millions of calls over a run when
-               repeated back to back); in between, and after a sweep that moved nothing, make attribute dicts ahead */
-            if (now_ms() - t_sweep < kSweepMs) {
-                if (!node) {  /* first: every row and predecessor dict and the top-level dicts, once */
-                    if (make_tops(names, N, rows, pin, outdeg, pending, &node, &succ, &pred)) goto done;
-                    if (trace) t_tops = now_ms() - t0;
-                    continue;
-                }
-                if (gc_collect && n_gc < kGcMid && R.n_dec >= (int64_t)(kGcAt[n_gc] * (double)E)) {
-                    /* the collector's pass over the dicts built so far, now, beside the replay (see kGcMid) */
-                    const double tg = now_ms();
-                    PyObject* res = PyObject_CallFunction(gc_collect, "i", 1);
-                    if (!res) goto done;
-                    Py_DECREF(res);
-                    t_gc += now_ms() - tg;
-                    ++n_gc;
-                    continue;
-                }
-                const int64_t m = spec_advance(&R, &spec_u, N, 256);
-                if (m < 0) goto done;
-                if (m == 0) {
-                    (void)spec_reap(&R, &reap_e, E, 16384);
-                    Py_BEGIN_ALLOW_THREADS
-                    sched_yield();
-                    Py_END_ALLOW_THREADS
-                }
-                continue;
-            }
-            t_sweep = now_ms();
-            int moved = 0;
-            int64_t keep_n = 0;
-            for (int64_t i = 0; i < n_open; ++i) {
-                const int64_t x = openl[i];
-                if (rg[x] < 0) continue;
-                const int m = row_advance(&R, x, 0);
-                if (m < 0) goto done;
-                moved |= m;
-                if (rg[x] >= 0) openl[keep_n++] = x;
-                if ((i & 255) == 255 && k_done < __atomic_load_n(&job.n_final, __ATOMIC_ACQUIRE)) {
-                    /* (newly published nodes first: keep the rest of the list for the next sweep) */
-                    for (int64_t j = i + 1; j < n_open; ++j) openl[keep_n++] = openl[j];
-                    break;
-                }
-            }
-            n_open = keep_n;
-            ++n_sweeps;
-            if (!moved) {  /* nothing to insert yet: make attribute dicts ahead, else yield */
-                const int64_t m = spec_advance(&R, &spec_u, N, 256);
-                if (m < 0) goto done;
-                if (m == 0) {
-                    Py_BEGIN_ALLOW_THREADS
-                    sched_yield();
-                    Py_END_ALLOW_THREADS
-                }
-            }
-        }
-        const int64_t n_rows = R.n_rows;
-        const int64_t n_pred = X.n_pred;
-        pthread_join(th, NULL);
-        started = 0;
-        if (scc_started) {
-            pthread_join(scc_th, NULL);
-            scc_started = 0;
-        }
-        if (trace) t_built = now_ms() - t0;
-        if (job.rc != 0 || k_done != N || n_rows != N || n_pred != N) {
-            PyErr_Format(PyExc_RuntimeError, "ovl_remove_cycles_stream failed (rc %d, %lld of %lld nodes final, "
-                         "%lld predecessor dicts)", job.rc, (long long)k_done, (long long)N, (long long)n_pred);
-            goto done;
-        }
-        if (!node && make_tops(names, N, rows, pin, outdeg, pending, &node, &succ, &pred)) goto done;
-        PyObject* rem = PyBytes_FromStringAndSize((const char*)job.removed, (Py_ssize_t)(8 * job.n_removed));
-        if (!rem) goto done;
-        out = Py_BuildValue("(OOONL)", node, succ, pred, rem, (long long)job.n_removed);
-        if (trace)
-            fprintf(stderr, "ovl_stream: s=%.1f r=%.1f (%.0f%% rows, %.0f%% edges, %lld inserted) b=%.1f t=%.1f sweeps=%lld scc=%d passes=%d first=%lld "
-                    "replay=%.1f cpus main %d/%d replay %d/%d spec %lld used %lld gc %d in %.1f ms tops at %.1f dec %.0f%%\n", t_setup, t_replay,
-                    N ? 100.0 * (double)k_at_replay / (double)N : 100.0,
-                    E ? 100.0 * (double)dec_at_replay / (double)E : 100.0, (long long)ins_at_replay, t_built, now_ms() - t0, (long long)n_sweeps,
-                    scc_on, scc.passes,
-                    (long long)n_from_scc, job.ms, job.cpu_main, sched_getcpu(), job.cpu_start, job.cpu_end, (long long)R.n_spec, (long long)R.n_spec_used, n_gc, t_gc, t_tops, E ? 100.0 * (double)dec_at_replay / (double)E : 0.0);
-    }
-done:
-    if (started) {  /* an error while the replay runs: let it finish (it owns no Python objects) */
-        __atomic_store_n(&job.gate, 1, __ATOMIC_RELEASE);  /* (if it still waits for the helper's first pass) */
-        Py_BEGIN_ALLOW_THREADS
-        pthread_join(th, NULL);
-        Py_END_ALLOW_THREADS
-    }
-    if (scc_started) {  /* (it stops once the replay has finished) */
-        Py_BEGIN_ALLOW_THREADS
-        pthread_join(scc_th, NULL);
-        Py_END_ALLOW_THREADS
-    }
-    const Py_ssize_t L_N = L.N, L_E = L.E;  /* (layout_free zeroes L) */
-    layout_free(&L);
-    cols_release(&C);
-    if (bs.obj) PyBuffer_Release(&bs);
-    if (be.obj) PyBuffer_Release(&be);
-    if (boff.obj) PyBuffer_Release(&boff);
-    if (bh.obj) PyBuffer_Release(&bh);
-    if (bw.obj) PyBuffer_Release(&bw);
-    if (ints) {
-        for (int i = 0; i < kIntHi - kIntLo; ++i) Py_XDECREF(ints[i]);
-        PyMem_Free(ints);
-    }
-    if (rows) {
-        for (Py_ssize_t i = 0; i < L_N; ++i) Py_XDECREF(rows[i]);
-        PyMem_Free(rows);
-    }
-    if (pin) {
-        for (Py_ssize_t i = 0; i < L_N; ++i) Py_XDECREF(pin[i]);
-        PyMem_Free(pin);
-    }
-    const double tc0 = trace ? now_ms() : 0.0;
-    if (dptr) {
-        if (own_refs)
-            for (Py_ssize_t e = 0; e < L_E; ++e) Py_XDECREF(dptr[e]);
-        PyMem_Free(dptr);
-    }
-    const double tc1 = trace ? now_ms() : 0.0;
-    if (spec) {  /* (the dicts made ahead for edges the replay then removed) */
-        for (Py_ssize_t e = 0; e < L_E; ++e) Py_XDECREF(spec[e]);
-        PyMem_Free(spec);
-    }
-    Py_XDECREF(gc_collect);
-    if (trace) fprintf(stderr, "ovl_stream exit: references %.1f ms, dicts made ahead and unused %.1f ms\n", tc1 - tc0,
-                       now_ms() - tc1);
-    PyMem_Free(rread);
-    PyMem_Free(bgoff);
-    PyMem_Free(blist);
-    PyMem_Free(pending);
-    PyMem_Free(ready);
-    PyMem_Free(pg);
-    PyMem_Free(pt);
-    PyMem_Free(rg);
-    PyMem_Free(rc);
-    PyMem_Free(outdeg);
-    PyMem_Free(pubd);
-    PyMem_Free(dec);
-    PyMem_Free(openl);
-    PyMem_RawFree(scc.nodes);
-    PyMem_RawFree(job.removed);
-    PyMem_RawFree(job.alive);
-    PyMem_RawFree(job.final_nodes);
-    Py_XDECREF(node);
-    Py_XDECREF(succ);
-    Py_XDECREF(pred);
-    Py_XDECREF(tmpl);
-    Py_XDECREF(kw);
-    Py_XDECREF(ke);
+    S.trace = tr_env && atoi(tr_env) != 0;
+    S.t0 = S.trace ? now_ms() : 0.0;
+    PyObject* out = NULL;
+    if (pairs_take(&S.Q, oc, oa, ob, os, oe, ok) == 0 && take(ooff, &S.off, 8, "off") == 0 &&
+        take(oh, &S.heads, 4, "heads") == 0 && take(ow, &S.w, 8, "weights") == 0 &&
+        stream_start_replay(&S, fn_addr) == 0 &&  /* first: the layout runs beside it */
+        stream_layout(&S, shared) == 0 &&
+        stream_start_helper(&S) == 0 &&
+        stream_open_rows(&S) == 0 &&
+        stream_publish(&S) == 0)
+        out = stream_finish(&S);
+    stream_free(&S);
     return out;
 }
 
@@ -1561,9 +1532,6 @@ static PyObject* arena_pool(PyObject* self, PyObject* args) {
 }
 
 // the builder entry points, each inside a pool scope
-static PyObject* build_impl(PyObject* self, PyObject* args);
-static PyObject* build_overlap_impl(PyObject* self, PyObject* args);
-static PyObject* build_overlap_stream_impl(PyObject* self, PyObject* args);
 #define OVL_POOL_SCOPED(name)                                  \
     static PyObject* name(PyObject* self, PyObject* args) {    \
         pool_begin();                                          \
